@@ -1,6 +1,6 @@
 """bench.py -- end-to-end frames/s of the detect + NMS + ReID + track hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload s640-bf16|m1024-bf16|l1280-fp8]
+    python bench.py --gpus N --steps K --warmup W [--workload s640-bf16|m1024-bf16|l1280-fp8] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = one pass of the hot path over one batch of B synthetic frames of ONE camera stream per GPU: letterbox -> YOLOv5
@@ -14,10 +14,20 @@ Workloads (config.workload names the one measured):
               injected after the conv stack has run (<= 256 detections per frame through NMS + ReID + DeepSORT)
   l1280-fp8   BASELINE.json configs[4] -- YOLOv5l, 1280x1280 frames, fp8 (MX-scaled MFMA) detector convs, B = 16, ground-truth
               rectangles injected after the conv stack has run (the seeded random head of the deep variant saturates)
-With the default workload on one GPU the line also carries `extra_points`: the same pipeline at K = 32 and K = 256 detections per
-frame (detection injection; K = 256 with its per-stage split), the fp32 engine (the mode whose CSV equals the
-oracle's exactly), short runs of the m1024-bf16 and l1280-fp8 workloads with their own `roofline`, and `value_host_frames`, the
-PCIe-inclusive rate with the frames in pinned host memory.
+A plain run does only what the headline needs: set up, warm up, time exactly K steps, write the outputs (--dump-outputs) and
+print the line (metric, value, unit, higher_is_better, dtype, ms_per_step, config).  --full adds everything else, as before:
+the `roofline` of the conv kernels (HIP event pairs around every conv launch of the timed steps) and `stage_ms_per_step` (two
+more steps with blocking events), the check of the native counter against the Python VideoCounting after the timed region, and,
+with the default workload on one GPU, `extra_points`: the same pipeline at K = 32 and K = 256 detections per frame (detection
+injection; K = 256 with its per-stage split), the fp32 engine (the mode whose CSV equals the oracle's exactly),
+short runs of the m1024-bf16 and l1280-fp8 workloads with their own `roofline`, `value_host_frames`, the PCIe-inclusive rate
+with the frames in pinned host memory, and `cpu_baseline` (--no-extras, --extras and --no-cpu-baseline trim a --full run).
+
+--dump-outputs DIR writes what the timed path returned for its last timed step (rank 0), in the fixed shapes of the C ABI's
+buffers: rows.npy ([B][CAP_ROWS][6]: [x1, y1, x2, y2, track_id, label] per tracked row of each frame of the last batch, zero past
+the frame's rows), rows_per_frame.npy ([B]), detections_per_frame.npy ([B]) and counts.npy (the all-gathered count tensors after
+the timed steps), all float64.  Inputs are seeded: the same arguments give the same inputs in every run, so two builds can be
+compared output for output.
 """
 import argparse
 import gc
@@ -46,6 +56,7 @@ TRACK = dict(max_dist=0.2, min_confidence=0.25, nms_max_overlap=0.5, max_iou_dis
 PEAK_TFLOPS = {"bf16": 2500.0, "fp8": 5000.0, "f32": 157.3}      # MI355X dense MFMA peaks (MI355X_MICROARCH.md; fp8 = MX-scaled K = 128 form; f32 = v_mfma_f32_16x16x4_f32, the vector rate)
 PEAK_HBM_GBS = 8000.0                              # HBM3E (MI355X_MICROARCH.md)
 ACHIEVABLE_HBM_GBS = 6300.0                        # what a read + write stream reaches (tools/ubench/stream_bw.hip)
+CAP_ROWS = 512                                     # rows per frame of the stream path's output buffer (vc_stream_collect's cap_rows_per_frame)
 ZONE = os.path.join(ROOT, "tests", "golden", "cam_04_halfres.json")
 ZONE_720P = os.path.join(ROOT, "tests", "golden", "cam_04.json")           # the reference's own zone file (demo/sample/cam_04.json, 1280 x 720)
 
@@ -205,6 +216,7 @@ class Stream:
         self.ndet = [0, 0]
         self.nrows = 0
         self.kept = [[] for _ in range(n_cam)]
+        self.last = None                                            # (rows, frame index in the batch, detections per frame) of the last recorded batch
         self.host = None
         self._dev_ptr = {}
         self.t_submit, self.lat = {}, []                            # submit -> rows-on-the-host latency of every recorded batch
@@ -245,9 +257,9 @@ class Stream:
     def run_async(self, i):
         ptr = self._dev_ptr.pop(i) if self.host is not None else self.batch_ptr(i)
         if self.n_cam == 1:
-            self.eng.stream_run_async(self.trackers[0], ptr, self.B, self.H, self.W)
+            self.eng.stream_run_async(self.trackers[0], ptr, self.B, self.H, self.W, cap_rows=CAP_ROWS)
         else:
-            self.eng.stream_run_async_multi(self.trackers, self.cams, ptr, self.B, self.H, self.W)
+            self.eng.stream_run_async_multi(self.trackers, self.cams, ptr, self.B, self.H, self.W, cap_rows=CAP_ROWS)
 
     def collect(self, i, record):
         rows, fidx, nd = self.eng.stream_collect()
@@ -257,6 +269,7 @@ class Stream:
                 self.lat.append(time.perf_counter() - t_sub)
             self.ndet[0] += int(nd.sum()); self.ndet[1] += self.B
             self.nrows += len(rows)
+            self.last = (rows, fidx, nd)
             # VideoCounting.run for one batch behind the C ABI (zone filter, per-track rows), on the host while the GPU works on the
             # next batches; the rows are kept so that the Python VideoCounting can check the result after the timed region
             S = self.n_cam
@@ -294,8 +307,9 @@ class Stream:
         if world > 1:
             torch.distributed.barrier()
 
-    def timed(self, first, steps, world):
-        """(seconds, post-pass ms, gathered counts) for `steps` steps starting at batch `first`, counting post-pass included."""
+    def timed(self, first, steps, world, check=True):
+        """(seconds, post-pass ms, gathered counts) for `steps` steps starting at batch `first`, counting post-pass included.
+        check: afterwards, hold the native counter to the Python VideoCounting over the same rows (outside the timed region)."""
         self.sync(world)
         gc.collect(); gc.disable()                 # a generation-2 collection over the per-track box lists costs 40 ms when it lands in the serial tail
         t0 = time.perf_counter()
@@ -314,6 +328,8 @@ class Stream:
         dt = time.perf_counter() - t0
         gc.enable()
         post_ms = (time.perf_counter() - t_post) * 1e3
+        if not check:
+            return dt, post_ms, all_counts
         # outside the timed region: the Python VideoCounting + csv_records + count_directions over the same rows must agree
         for c in range(self.n_cam):
             counter, table = self.counters[c], tables[c]
@@ -331,21 +347,25 @@ class Stream:
         return dt, post_ms, all_counts
 
 
-def measure(st, warmup, steps, world, peak_tflops, first=0, traffic=None, traffic_src=None):
+def measure(st, warmup, steps, world, peak_tflops, first=0, traffic=None, traffic_src=None, full=True):
     """`warmup` untimed steps, then EXACTLY `steps` timed ones (barrier + synchronize on both sides, max over ranks), with the
     conv launches of the timed steps bracketed by in-flight HIP event pairs on their own streams; afterwards two extra steps with
-    blocking events give the per-stage split.  Returns (seconds, post-pass ms, gathered counts, roofline, stage_ms_per_step)."""
+    blocking events give the per-stage split.  Returns (seconds, post-pass ms, gathered counts, roofline, stage_ms_per_step).
+    full=False: the timed steps alone -- no event pairs, no extra steps, no counting check; roofline and split are None."""
     eng = st.eng
     st.run_steps(first, warmup, False)
     st.sync(world)
-    eng.profile_reset()
-    if not os.environ.get("VC_BENCH_NO_EVENTS"):  # (A/B switch: what the event pairs themselves cost)
-        eng.profile(2)                             # in-flight event pairs around every conv launch of the timed steps (no host waits)
-    dt, post_ms, all_counts = st.timed(first + warmup, steps, world)
+    if full:
+        eng.profile_reset()
+        if not os.environ.get("VC_BENCH_NO_EVENTS"):  # (A/B switch: what the event pairs themselves cost)
+            eng.profile(2)                             # in-flight event pairs around every conv launch of the timed steps (no host waits)
+    dt, post_ms, all_counts = st.timed(first + warmup, steps, world, check=full)
     if world > 1:
         t = torch.tensor([dt], device=st.dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    if not full:
+        return dt, post_ms, all_counts, None, None
     # roofline of the dominant kernel (the conv kernels): HIP events around every conv launch of the TIMED steps, recorded on
     # the stream the kernel is launched on and resolved after the region (the launches overlap with the other two streams, as in
     # the rocprofv3 trace of this command).  The per-stage split comes from two extra steps with blocking events.
@@ -549,17 +569,40 @@ def dropin_point(*a, **kw):
         return {"error": str(ex)[:300]}
 
 
+def dump_outputs(path, last, all_counts):
+    """--dump-outputs: what the timed path handed its caller for the last timed step, as float64 .npy files of fixed shapes (the
+    number of rows varies with the detections, so rows are laid out per frame as vc_stream_collect returns them: 6.3 MB at B = 256)."""
+    rows, fidx, nd = last
+    b = len(nd)
+    m = np.bincount(fidx, minlength=b)
+    slot = np.arange(len(fidx)) - np.repeat(np.cumsum(m) - m, m)      # rows come grouped by frame, in frame order
+    per_frame = np.zeros((b, CAP_ROWS, 6), np.float64)
+    per_frame[fidx, slot] = rows
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("rows", per_frame), ("rows_per_frame", m), ("detections_per_frame", nd), ("counts", all_counts)):
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="s640-bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra operating points (K = 32 / 256, fp32, m1024-bf16, l1280-fp8, host frames)")
-    ap.add_argument("--extras", default="", help="comma-separated subset of the extra operating points to run (default: all)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rows, frame indices, detections per frame, counts) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: roofline + per-stage split, counting check, extra "
+                         "operating points, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra operating points (K = 32 / 256, fp32, m1024-bf16, l1280-fp8, host frames)")
+    ap.add_argument("--extras", default="", help="with --full: comma-separated subset of the extra operating points to run (default: all)")
     ap.add_argument("--cpu-frames", type=int, default=8)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))            # `python bench.py --gpus N`: become N ranks (one per GPU) over RCCL
@@ -581,13 +624,16 @@ def main():
     traffic, traffic_src = None, None
     for rnd in ("r06", "r05", "r04", "r03", "r02", "r01"):
         tp = os.path.join(ROOT, "profiles", f"{rnd}_pmc_traffic.json")
-        if args.workload == "s640-bf16" and os.path.exists(tp):
+        if args.full and args.workload == "s640-bf16" and os.path.exists(tp):
             with open(tp) as f:
                 traffic, traffic_src = json.load(f)["conv_all"]["hbm_bytes_per_launch"], f"profiles/{rnd}_pmc_traffic.json"
             break
-    dt, post_ms, all_counts, roofline, stage_ms = measure(st, args.warmup, args.steps, world, peak_tflops, traffic=traffic, traffic_src=traffic_src)
-    if args.workload == "s640-bf16":
+    dt, post_ms, all_counts, roofline, stage_ms = measure(st, args.warmup, args.steps, world, peak_tflops, traffic=traffic, traffic_src=traffic_src,
+                                                          full=args.full)
+    if args.full and args.workload == "s640-bf16":
         roofline.update(backbone_mfma_busy())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, st.last, all_counts)
 
     out = None
     if rank == 0:
@@ -603,14 +649,15 @@ def main():
                        "weights": "seeded synthetic (no checkpoints available)", "streams": world, "ranks": world,
                        "counts_allgather_shape": list(all_counts.shape), "counts_allgather_via": st.gather_via, "tracked_rows": int(st.nrows),
                        "counting": "vc_counter_add per batch, vc_counter_rows + vc_counts after the last batch (C ABI), inside the timed region", "counting_postpass_ms_total": post_ms, "tracker": "device-resident (one kernel per batch, no host round trip per frame)"},
-            "roofline": roofline,
-            "stage_ms_per_step": stage_ms,
         }
+        if args.full:
+            out["roofline"] = roofline
+            out["stage_ms_per_step"] = stage_ms
     ysd, rsd, frames = st.ysd, st.rsd, st.frames
     eng.close()
     del st
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and args.workload == "s640-bf16" and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and args.workload == "s640-bf16" and not args.no_extras:
         # other operating points of SURVEY.md 8(d), short runs of the same pipeline (extra keys; `value` above is the headline)
         qp = lambda w=wl, **kw: (lambda: quick_point(w, rank, local, dev, world, **kw))
         points = {
@@ -652,7 +699,7 @@ def main():
             out["value_host_frames"] = hp["value"]
             out["value_host_frames_note"] = "same workload with the frames in pinned host memory: every batch is copied over PCIe inside the timed region (vc_stream_stage_host one batch ahead of vc_stream_submit: the copy runs under the detector of the batch before)"
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and args.workload == "s640-bf16":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "s640-bf16":
             out["cpu_baseline"] = cpu_baseline(ysd, rsd, frames, args.cpu_frames)
         print(json.dumps(out))
     if world > 1:
