@@ -179,6 +179,39 @@ int vc_stream_submit_host(vc_engine* e, const uint8_t* frames_host, int b, int h
 int vc_stream_run(vc_engine* e, const int* trackers, int num_classes, const void* frames_dev, int b, int h, int w,
                   int64_t* out_rows6, int cap_rows_per_frame, int* out_m /* b */, int* out_ndet /* b, may be NULL */);
 
+/* ---- 4:2:0 YUV ingest: what a video decoder hands out (the reference gets BGR because cv2.VideoCapture converts on the CPU,
+ * modules/datasets.py:47-61) -------------------------------------------------------------------------------------------- */
+#define VC_PIX_NV12 0      /* Y plane, then one plane of interleaved U,V at half resolution (hardware decoder surfaces) */
+#define VC_PIX_I420 1      /* Y, U and V planes (software decoders) */
+#define VC_YUV_BT601 0
+#define VC_YUV_BT709 1
+/* Geometry in BYTES from the start of a frame; 0 = tightly packed (pitch_y = w; pitch_c = w for NV12, w / 2 for I420; offset_c =
+ * pitch_y * h; offset_v = offset_c + pitch_c * h / 2; frame_stride = end of the last plane).  A decoder surface gives the explicit
+ * form, e.g. pitch 1536 for a 1280-wide frame with the chroma plane at pitch x aligned height.  offset_v is ignored for NV12. */
+typedef struct vc_yuv_desc {
+    int format;            /* VC_PIX_* */
+    int matrix;            /* VC_YUV_BT601 / VC_YUV_BT709 */
+    int full_range;        /* 0: limited (Y 16..235), 1: full (0..255) */
+    int pitch_y, pitch_c;
+    size_t offset_c, offset_v, frame_stride;
+} vc_yuv_desc;
+int vc_yuv_desc_default(vc_yuv_desc* d);   /* NV12, BT.601, limited range, tightly packed */
+/* Arithmetic (integer, 32-bit signed): u = U - 128, v = V - 128, chroma replicated over its 2 x 2 luma block,
+ *   R = clamp((y + (1 << 19) + CVR * v) >> 20), G = clamp((y + (1 << 19) + CVG * v + CUG * u) >> 20), B = clamp((y + (1 << 19) + CUB * u) >> 20)
+ * with y = max(0, Y - 16) * CY (limited) or Y << 20 (full) and constants int(literal * 2^20): OpenCV's COLOR_YUV2BGR_NV12 for
+ * BT.601 limited.  h and w must be even.  Bad geometry (odd size, unknown format / matrix, a pitch below the row width, overlapping
+ * planes) is VC_ERR_ARG before any HIP call.
+ * vc_stream_stage_yuv_host / _dev fill one of the four ingest slots of vc_stream_stage_host with the CONVERTED frames (same slot
+ * rules, same VC_ERR_STATE refusals; BGR and YUV staging may be mixed): *frames_dev_out is an ordinary B x H x W x 3 BGR buffer
+ * for vc_stream_submit / vc_stream_run*.  _host copies the raw YUV (1.5 B per pixel over PCIe; pinned memory for the copy to
+ * overlap) into a per-slot raw buffer on the engine's copy stream and converts from there; _dev converts straight from the
+ * caller's device surfaces, which must stay valid until the vc_stream_run / vc_stream_run_async call of that batch has returned. */
+int vc_stream_stage_yuv_host(vc_engine* e, const vc_yuv_desc* d, const uint8_t* yuv_host, int b, int h, int w, void** frames_dev_out);
+int vc_stream_stage_yuv_dev(vc_engine* e, const vc_yuv_desc* d, const void* yuv_dev, int b, int h, int w, void** frames_dev_out);
+/* The same conversion outside the stream path, on the caller's own device buffers (frames for vc_overlay, measurement): enqueued on
+ * the NULL stream, returns without waiting for it.  bgr_dev: b x h x w x 3 bytes. */
+int vc_yuv_to_bgr_dev(const vc_yuv_desc* d, const void* yuv_dev, int b, int h, int w, void* bgr_dev);
+
 /* Asynchronous form of vc_stream_run: the batch's tracker work is ONE kernel enqueued on the engine's tracker stream (no host
  * thread); the call returns as soon as the batch's ReID and tracker kernel are enqueued.  At most two batches may be outstanding.
  * vc_stream_collect returns the rows of the OLDEST outstanding batch (same layout as vc_stream_run) and blocks until they are
@@ -303,6 +336,8 @@ int vc_cosine_cost_host(const float* gallery, const int* gal_count, int t, int s
 int vc_dsort_nms_host(const double* tlwh, const double* scores, int n, double max_overlap, int* keep, int* n_keep);
 int vc_lap_host(const double* cost, int nr, int nc, int* row4col_rows, int* cols, int* n_assigned);
 int vc_letterbox_host(const uint8_t* rgb, int h, int w, int net_h, int net_w, int precision, float* out_nhwc3);
+/* yuv_to_bgr_kernel (the stream path's ingest conversion) on host arrays: b frames laid out as `d` says -> packed BGR b x h x w x 3 */
+int vc_yuv_to_bgr_host(const vc_yuv_desc* d, const uint8_t* yuv, int b, int h, int w, uint8_t* bgr_out);
 /* VideoCounting.run zone filter (modules/track.py:102-104): inside[i] = any corner of boxes[i] in the polygon. Host only. */
 int vc_zone_filter_host(const double* polygon_xy, int n_points, const int64_t* boxes_xyxy, int n, uint8_t* inside);
 /* candidates (already conf-filtered, in the reference's candidate order): boxes xyxy, conf, class -> kept rows */

@@ -19,6 +19,8 @@ PREC_ID = {"bf16": 0, "f32": 1, "fp8": 2}
 NET_YOLO, NET_REID = 0, 1
 FEAT_DIM = 512
 PROF_CONV, PROF_DETECT_AUX, PROF_REID_AUX, PROF_TRACK = 0, 1, 2, 3
+PIX_ID = {"nv12": 0, "i420": 1}
+YUV_MATRIX_ID = {"bt601": 0, "bt709": 1}
 
 
 class VcError(RuntimeError):
@@ -44,6 +46,12 @@ class ConvDesc(C.Structure):
     _fields_ = [("b", C.c_int), ("h", C.c_int), ("w", C.c_int), ("cin", C.c_int), ("cout", C.c_int), ("kh", C.c_int),
                 ("kw", C.c_int), ("stride", C.c_int), ("pad", C.c_int), ("act", C.c_int), ("res_mode", C.c_int),
                 ("precision", C.c_int)]
+
+
+class YuvDesc(C.Structure):
+    """vc_yuv_desc: byte geometry of 4:2:0 frames, 0 = tightly packed."""
+    _fields_ = [("format", C.c_int), ("matrix", C.c_int), ("full_range", C.c_int), ("pitch_y", C.c_int), ("pitch_c", C.c_int),
+                ("offset_c", C.c_size_t), ("offset_v", C.c_size_t), ("frame_stride", C.c_size_t)]
 
 
 _P = C.POINTER
@@ -88,6 +96,11 @@ SIGNATURES = {
     "vc_stream_submit": [_vp, _vp, _i, _i, _i],
     "vc_stream_stage_host": [_vp, _vp, _i, _i, _i, _P(_vp)],
     "vc_stream_submit_host": [_vp, _vp, _i, _i, _i, _P(_vp)],
+    "vc_yuv_desc_default": [_P(YuvDesc)],
+    "vc_stream_stage_yuv_host": [_vp, _P(YuvDesc), _vp, _i, _i, _i, _P(_vp)],
+    "vc_stream_stage_yuv_dev": [_vp, _P(YuvDesc), _vp, _i, _i, _i, _P(_vp)],
+    "vc_yuv_to_bgr_host": [_P(YuvDesc), _pu8, _i, _i, _i, _pu8],
+    "vc_yuv_to_bgr_dev": [_P(YuvDesc), _vp, _i, _i, _i, _vp],
     "vc_stream_run_async": [_vp, _pi, _i, _vp, _i, _i, _i, _i],
     "vc_stream_collect": [_vp, _pl, _i, _pi, _pi, _i],
     "vc_stream_run_async_multi": [_vp, _pi, _i, _i, _pi, _vp, _i, _i, _i, _i],

@@ -177,6 +177,9 @@ struct vc_engine {
     hipEvent_t ev_ingest[4] = {nullptr, nullptr, nullptr, nullptr};
     unsigned ingest_seq = 0;
     bool ingest_staged[4] = {false, false, false, false};   // copied (or being copied) by vc_stream_stage_host, not yet submitted
+    // YUV ingest (yuv_ingest.hip): raw 4:2:0 bytes of vc_stream_stage_yuv_host, one buffer per ingest slot, allocated by its first call
+    uint8_t* d_yuv_raw[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t yuv_raw_bytes[4] = {0, 0, 0, 0};
     // stream path: three feature / crop buffers -- the batch being tracked (tracker stream), the batch
     // whose ReID is running, and the one after it
     float* d_feat2[3] = {nullptr, nullptr, nullptr};
@@ -276,6 +279,10 @@ int run_detector_dev(vc_engine* e, const uint8_t* d_frames, int B, int h, int w,
 int run_reid_dev(vc_engine* e, const uint8_t* d_frames, int H, int W, int k);                      // crops in e->d_crops -> e->d_feat
 int run_reid_on(vc_engine* e, const uint8_t* d_frames, int H, int W, int k, const int* d_crops, float* feat_out, hipStream_t rs);
 int prof_launch(vc_engine* e, int cat, double flops, double bytes, int status);
+// stream.hip: the slot rules of vc_stream_stage_host (shared with the YUV staging calls): checks, creates the copy stream and the four
+// slots on first use, and hands out the next slot round-robin.  The caller enqueues its work on e->cstream, then calls ingest_publish.
+int ingest_take_slot(vc_engine* e, int b, int h, int w, int* slot);
+int ingest_publish(vc_engine* e, int slot, void** frames_dev_out);
 struct ProfScope {
     vc_engine* e; int cat; double flops, bytes;
     hipStream_t s;

@@ -59,6 +59,43 @@ void marshal(const float* det6, int n, FrameDets& out) {
 
 }  // namespace
 
+namespace vc {
+
+int ingest_take_slot(vc_engine* e, int b, int h, int w, int* slot_out) {
+    VC_CHECK(e->finalized && e->cfg.with_detector, VC_ERR_STATE, "engine not finalized");
+    VC_CHECK(b >= 1 && b <= e->cfg.max_batch && h >= 1 && w >= 1 && h <= e->cfg.max_frame_h && w <= e->cfg.max_frame_w, VC_ERR_CAPACITY,
+             "batch of %d frames %dx%d exceeds max_batch / max_frame_h / max_frame_w", b, h, w);
+    VC_HIP(hipSetDevice(e->cfg.device));
+    const size_t slot_bytes = (size_t)e->cfg.max_batch * e->cfg.max_frame_h * e->cfg.max_frame_w * 3;
+    if (!e->cstream) {
+        VC_HIP(hipStreamCreateWithFlags(&e->cstream, hipStreamNonBlocking));
+        for (int i = 0; i < 4; ++i) {
+            VC_TRY(dev_alloc(e, (void**)&e->d_ingest[i], slot_bytes));
+            VC_HIP(hipEventCreateWithFlags(&e->ev_ingest[i], hipEventDisableTiming));
+        }
+    }
+    // four slots: one batch staged ahead + <= 2 submissions + the batch whose rows are still to be collected
+    const int slot = (int)(e->ingest_seq & 3);
+    VC_CHECK(!e->ingest_staged[slot], VC_ERR_STATE, "four host batches are staged and none has been submitted: call vc_stream_submit");
+    for (const auto& pd : e->pending)
+        VC_CHECK(pd.frames != e->d_ingest[slot], VC_ERR_STATE, "the staging slot's previous batch is still waiting for vc_stream_run: at most four host batches may be alive");
+    for (const auto& job : e->jobs)                      // its crops may still be being cut on the ReID stream
+        VC_CHECK(job.frames != e->d_ingest[slot], VC_ERR_STATE, "the staging slot's previous batch has not been collected: at most four host batches may be alive");
+    ++e->ingest_seq;
+    *slot_out = slot;
+    return VC_OK;
+}
+
+// the slot's work has been enqueued on the copy stream: vc_stream_submit of the returned address starts the detector behind it
+int ingest_publish(vc_engine* e, int slot, void** frames_dev_out) {
+    VC_HIP(hipEventRecord(e->ev_ingest[slot], e->cstream));
+    e->ingest_staged[slot] = true;
+    *frames_dev_out = e->d_ingest[slot];
+    return VC_OK;
+}
+
+}  // namespace vc
+
 extern "C" {
 
 int vc_stream_inject(vc_engine* e, const float* det6, const int* count, int b, int n) {
@@ -107,31 +144,10 @@ int vc_stream_submit(vc_engine* e, const void* frames_dev, int b, int h, int w) 
 // it untouched until the batch's rows have been collected -- plain pageable memory is copied synchronously by the runtime.
 int vc_stream_stage_host(vc_engine* e, const uint8_t* frames_host, int b, int h, int w, void** frames_dev_out) {
     VC_CHECK(e && frames_host && frames_dev_out, VC_ERR_ARG, "null argument");
-    VC_CHECK(e->finalized && e->cfg.with_detector, VC_ERR_STATE, "engine not finalized");
-    VC_CHECK(b >= 1 && b <= e->cfg.max_batch && h >= 1 && w >= 1 && h <= e->cfg.max_frame_h && w <= e->cfg.max_frame_w, VC_ERR_CAPACITY,
-             "batch of %d frames %dx%d exceeds max_batch / max_frame_h / max_frame_w", b, h, w);
-    VC_HIP(hipSetDevice(e->cfg.device));
-    const size_t bytes = (size_t)b * h * w * 3, slot_bytes = (size_t)e->cfg.max_batch * e->cfg.max_frame_h * e->cfg.max_frame_w * 3;
-    if (!e->cstream) {
-        VC_HIP(hipStreamCreateWithFlags(&e->cstream, hipStreamNonBlocking));
-        for (int i = 0; i < 4; ++i) {
-            VC_TRY(dev_alloc(e, (void**)&e->d_ingest[i], slot_bytes));
-            VC_HIP(hipEventCreateWithFlags(&e->ev_ingest[i], hipEventDisableTiming));
-        }
-    }
-    // four slots: one batch staged ahead + <= 2 submissions + the batch whose rows are still to be collected
-    const int slot = (int)(e->ingest_seq & 3);
-    VC_CHECK(!e->ingest_staged[slot], VC_ERR_STATE, "four host batches are staged and none has been submitted: call vc_stream_submit");
-    for (const auto& pd : e->pending)
-        VC_CHECK(pd.frames != e->d_ingest[slot], VC_ERR_STATE, "the staging slot's previous batch is still waiting for vc_stream_run: at most four host batches may be alive");
-    for (const auto& job : e->jobs)                      // its crops may still be being cut on the ReID stream
-        VC_CHECK(job.frames != e->d_ingest[slot], VC_ERR_STATE, "the staging slot's previous batch has not been collected: at most four host batches may be alive");
-    ++e->ingest_seq;
-    VC_HIP(hipMemcpyAsync(e->d_ingest[slot], frames_host, bytes, hipMemcpyHostToDevice, e->cstream));
-    VC_HIP(hipEventRecord(e->ev_ingest[slot], e->cstream));
-    e->ingest_staged[slot] = true;
-    *frames_dev_out = e->d_ingest[slot];
-    return VC_OK;
+    int slot = 0;
+    VC_TRY(ingest_take_slot(e, b, h, w, &slot));
+    VC_HIP(hipMemcpyAsync(e->d_ingest[slot], frames_host, (size_t)b * h * w * 3, hipMemcpyHostToDevice, e->cstream));
+    return ingest_publish(e, slot, frames_dev_out);
 }
 
 int vc_stream_submit_host(vc_engine* e, const uint8_t* frames_host, int b, int h, int w, void** frames_dev_out) {

@@ -1,0 +1,294 @@
+// YUV ingest: 4:2:0 frames as a video decoder hands them out (NV12 surfaces in device memory, I420 planes in host memory) converted
+// on the device into the packed BGR u8 [b][h][w][3] the engine's ingest slots hold (stream.hip: d_ingest[]).  The reference receives
+// BGR because cv2.VideoCapture converts on the CPU behind its back (/root/reference/modules/datasets.py:47-61).
+//
+// The arithmetic is the definition (integer, so every implementation agrees bit for bit; restated in NumPy by tests/yuv_ref.py):
+//   u = U - 128, v = V - 128, chroma replicated over its 2 x 2 luma block (no interpolation), 32-bit signed arithmetic,
+//   R = clamp((y + (1 << 19) + CVR * v) >> 20, 0, 255)
+//   G = clamp((y + (1 << 19) + CVG * v + CUG * u) >> 20, 0, 255)
+//   B = clamp((y + (1 << 19) + CUB * u) >> 20, 0, 255)
+//   limited range: y = max(0, Y - 16) * CY;  full range: y = Y << 20;  constants = int(literal * 2^20), truncated toward zero.
+// BT.601 limited is OpenCV's COLOR_YUV2BGR_NV12 arithmetic as published; OpenCV is not in this image, so parity with it (and with the
+// swscale path inside cv2.VideoCapture) is UNPINNED, like the other cv2 steps.
+//
+// A pure streaming kernel, 1.5 B read and 3 B written per pixel, no LDS, plain vector stores.  One lane owns 16 pixels x 2 rows so
+// that both rows share one chroma fetch: 16 B of Y per row, 16 B of UV (8 B + 8 B for I420), three 16-byte stores per row.  The
+// generic variant (any even w, any pitch) owns the same 16 x 2 block, assembles the same words from byte loads and stores bytes.
+// Every factor fits 24 bits and every sum 31 bits (|chroma term| <= 2.3e6 * 128, y <= 255 << 20), hence the full-rate 24-bit multiplies.
+#include <algorithm>
+
+#include "engine.h"
+
+namespace vc {
+
+struct YuvGeom {                 // a validated vc_yuv_desc with the zeros resolved; all byte quantities
+    int nv12, h, w, pitch_y, pitch_c;
+    size_t off_c, off_v, frame_stride, frame_end;      // frame_end: one past the last byte any plane of a frame occupies
+    int yoff, cy, cvr, cvg, cug, cub;                   // y = max(0, Y - yoff) * cy: full range is yoff = 0, cy = 1 << 20
+};
+
+namespace {
+
+// int(literal * 2^20), truncated toward zero: {CY, CVR, CVG, CUG, CUB} per [matrix][full_range]
+constexpr int yuv_fix(double v) { return (int)(v * 1048576.0); }
+const int kYuvCoef[2][2][5] = {
+    {{yuv_fix(1.164), yuv_fix(1.596), yuv_fix(-0.813), yuv_fix(-0.391), yuv_fix(2.018)},            // BT.601 limited: 1220542 1673527 -852492 -409993 2116026
+     {1 << 20, yuv_fix(1.402), yuv_fix(-0.714136), yuv_fix(-0.344136), yuv_fix(1.772)}},             // BT.601 full
+    {{yuv_fix(1.164), yuv_fix(1.793), yuv_fix(-0.533), yuv_fix(-0.213), yuv_fix(2.112)},            // BT.709 limited
+     {1 << 20, yuv_fix(1.5748), yuv_fix(-0.468124), yuv_fix(-0.187324), yuv_fix(1.8556)}}};          // BT.709 full
+
+struct YuvChroma { int r, g, b; };   // chroma terms of one 2 x 2 block, rounding constant included
+
+__device__ __forceinline__ YuvChroma yuv_chroma(int U, int V, const YuvGeom& k) {
+    const int u = U - 128, v = V - 128;
+    YuvChroma c;
+    c.r = __mul24(k.cvr, v) + (1 << 19);
+    c.g = __mul24(k.cvg, v) + __mul24(k.cug, u) + (1 << 19);
+    c.b = __mul24(k.cub, u) + (1 << 19);
+    return c;
+}
+
+__device__ __forceinline__ uint32_t yuv_pixel(int Y, const YuvChroma& c, const YuvGeom& k) {    // B | G << 8 | R << 16
+    // clamp((x) >> 20, 0, 255) written as clamp(x, 0, (256 << 20) - 1) >> 20: the same value for every x, and the shift is a logical one of
+    // a non-negative number.  The arithmetic-shift-then-clamp form is matched by the compiler to gfx950's packed shift-and-saturate
+    // instruction (two results in one 16-bit half), and the words assembled from it came out with stray high bits on the hardware.
+    const int y = __mul24(max(Y - k.yoff, 0), k.cy), top = (256 << 20) - 1;
+    const uint32_t r = (uint32_t)min(max(y + c.r, 0), top) >> 20, g = (uint32_t)min(max(y + c.g, 0), top) >> 20, b = (uint32_t)min(max(y + c.b, 0), top) >> 20;
+    return b | (g << 8) | (r << 16);
+}
+
+// 16 pixels of one row: yw = 16 Y bytes, cw[j] = U(2j) | V(2j) << 8 | U(2j+1) << 16 | V(2j+1) << 24 -> 48 bytes of BGR as 12 words
+__device__ __forceinline__ void yuv_row16(const uint32_t yw[4], const YuvChroma ch[8], const YuvGeom& k, uint32_t out[12]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t p0 = yuv_pixel(yw[j] & 255, ch[2 * j], k), p1 = yuv_pixel((yw[j] >> 8) & 255, ch[2 * j], k);
+        const uint32_t p2 = yuv_pixel((yw[j] >> 16) & 255, ch[2 * j + 1], k), p3 = yuv_pixel(yw[j] >> 24, ch[2 * j + 1], k);
+        out[3 * j] = p0 | (p1 << 24);
+        out[3 * j + 1] = (p1 >> 8) | (p2 << 16);
+        out[3 * j + 2] = (p2 >> 16) | (p3 << 8);
+    }
+}
+
+__device__ __forceinline__ uint32_t yuv_bytes4(const uint8_t* p, int n) {      // up to four bytes, the first n of them valid
+    uint32_t v = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (i < n) v |= (uint32_t)p[i] << (8 * i);
+    return v;
+}
+
+// grid: one lane per (frame, row pair, 16-pixel column group), flattened in that order so that a wavefront walks along a row pair
+template <bool NV12, bool FAST>
+__global__ __launch_bounds__(256) void yuv_to_bgr_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, YuvGeom k, int ncg, long long total) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= total) return;
+    const int hp = k.h >> 1;
+    const long long rowpair = gid / ncg;
+    const int cg = (int)(gid - rowpair * ncg);
+    const int f = (int)(rowpair / hp), rp = (int)(rowpair - (long long)f * hp);
+    const int x0 = cg * 16;
+    const int npx = min(16, k.w - x0);                      // even; 16 on the fast path
+    const uint8_t* sf = src + (size_t)f * k.frame_stride;
+    const uint8_t* y0p = sf + (size_t)(2 * rp) * k.pitch_y + x0;
+    const uint8_t* y1p = y0p + k.pitch_y;
+
+    uint32_t yw[2][4], cw[4];
+    if (FAST) {
+        const uint4 a = *(const uint4*)y0p, b = *(const uint4*)y1p;
+        yw[0][0] = a.x; yw[0][1] = a.y; yw[0][2] = a.z; yw[0][3] = a.w;
+        yw[1][0] = b.x; yw[1][1] = b.y; yw[1][2] = b.z; yw[1][3] = b.w;
+        if (NV12) {
+            const uint4 c = *(const uint4*)(sf + k.off_c + (size_t)rp * k.pitch_c + x0);
+            cw[0] = c.x; cw[1] = c.y; cw[2] = c.z; cw[3] = c.w;
+        } else {
+            const uint2 u = *(const uint2*)(sf + k.off_c + (size_t)rp * k.pitch_c + (x0 >> 1));
+            const uint2 v = *(const uint2*)(sf + k.off_v + (size_t)rp * k.pitch_c + (x0 >> 1));
+            const uint32_t uu[2] = {u.x, u.y}, vv[2] = {v.x, v.y};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t us = uu[j >> 1] >> (16 * (j & 1)), vs = vv[j >> 1] >> (16 * (j & 1));
+                cw[j] = (us & 255) | ((vs & 255) << 8) | ((us & 0xff00) << 8) | ((vs & 0xff00) << 16);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int n = npx - 4 * j;                      // pixels of this group of four that exist
+            yw[0][j] = yuv_bytes4(y0p + 4 * j, n);
+            yw[1][j] = yuv_bytes4(y1p + 4 * j, n);
+            if (NV12) {
+                cw[j] = yuv_bytes4(sf + k.off_c + (size_t)rp * k.pitch_c + x0 + 4 * j, n);
+            } else {
+                const uint32_t us = yuv_bytes4(sf + k.off_c + (size_t)rp * k.pitch_c + (x0 >> 1) + 2 * j, n >> 1);
+                const uint32_t vs = yuv_bytes4(sf + k.off_v + (size_t)rp * k.pitch_c + (x0 >> 1) + 2 * j, n >> 1);
+                cw[j] = (us & 255) | ((vs & 255) << 8) | ((us & 0xff00) << 8) | ((vs & 0xff00) << 16);
+            }
+        }
+    }
+
+    YuvChroma ch[8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        ch[2 * j] = yuv_chroma(cw[j] & 255, (cw[j] >> 8) & 255, k);
+        ch[2 * j + 1] = yuv_chroma((cw[j] >> 16) & 255, cw[j] >> 24, k);
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        uint32_t o[12];
+        yuv_row16(yw[r], ch, k, o);
+        uint8_t* d = dst + (((size_t)f * k.h + 2 * rp + r) * k.w + x0) * 3;
+        if (FAST) {
+            uint4* d4 = (uint4*)d;
+            d4[0] = make_uint4(o[0], o[1], o[2], o[3]);
+            d4[1] = make_uint4(o[4], o[5], o[6], o[7]);
+            d4[2] = make_uint4(o[8], o[9], o[10], o[11]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 48; ++i)
+                if (i < npx * 3) d[i] = (uint8_t)(o[i >> 2] >> (8 * (i & 3)));
+        }
+    }
+}
+
+}  // namespace
+
+// Validates a descriptor for b frames of h x w and resolves its zeros.  Pure host code: runs before any HIP call.
+int yuv_resolve(const vc_yuv_desc* d, int b, int h, int w, YuvGeom& g) {
+    VC_CHECK(d, VC_ERR_ARG, "null vc_yuv_desc");
+    VC_CHECK(d->format == VC_PIX_NV12 || d->format == VC_PIX_I420, VC_ERR_ARG, "unknown pixel format %d (VC_PIX_NV12 / VC_PIX_I420)", d->format);
+    VC_CHECK(d->matrix == VC_YUV_BT601 || d->matrix == VC_YUV_BT709, VC_ERR_ARG, "unknown colour matrix %d (VC_YUV_BT601 / VC_YUV_BT709)", d->matrix);
+    VC_CHECK(d->full_range == 0 || d->full_range == 1, VC_ERR_ARG, "full_range must be 0 or 1");
+    VC_CHECK(b >= 1 && h >= 2 && w >= 2, VC_ERR_ARG, "bad batch of %d frames %dx%d", b, h, w);
+    VC_CHECK(h % 2 == 0 && w % 2 == 0, VC_ERR_ARG, "4:2:0 frames need an even height and width, got %dx%d", h, w);
+    g.nv12 = d->format == VC_PIX_NV12;
+    g.h = h; g.w = w;
+    const int crow = g.nv12 ? w : w / 2;                                      // bytes of one chroma row
+    g.pitch_y = d->pitch_y ? d->pitch_y : w;
+    g.pitch_c = d->pitch_c ? d->pitch_c : crow;
+    VC_CHECK(g.pitch_y >= w, VC_ERR_ARG, "pitch_y %d is below the row width %d", d->pitch_y, w);
+    VC_CHECK(g.pitch_c >= crow, VC_ERR_ARG, "pitch_c %d is below the chroma row width %d", d->pitch_c, crow);
+    const size_t hc = (size_t)h / 2;
+    const size_t len_y = (size_t)g.pitch_y * (h - 1) + w, len_c = (size_t)g.pitch_c * (hc - 1) + crow;
+    g.off_c = d->offset_c ? d->offset_c : (size_t)g.pitch_y * h;
+    g.off_v = g.nv12 ? 0 : (d->offset_v ? d->offset_v : g.off_c + (size_t)g.pitch_c * hc);
+    const size_t lim = (size_t)1 << 40;                                        // keeps every sum below far from overflow
+    VC_CHECK(g.off_c < lim && g.off_v < lim && d->frame_stride < lim, VC_ERR_ARG, "plane offset or frame stride out of range");
+    VC_CHECK(g.off_c >= len_y, VC_ERR_ARG, "the chroma plane (offset %zu) overlaps the luma plane (%zu bytes)", g.off_c, len_y);
+    g.frame_end = g.off_c + len_c;
+    if (!g.nv12) {
+        VC_CHECK(g.off_v >= len_y, VC_ERR_ARG, "the V plane (offset %zu) overlaps the luma plane (%zu bytes)", g.off_v, len_y);
+        VC_CHECK(g.off_v >= g.off_c + len_c || g.off_c >= g.off_v + len_c, VC_ERR_ARG, "the U and V planes overlap (offsets %zu, %zu)", g.off_c, g.off_v);
+        g.frame_end = std::max(g.frame_end, g.off_v + len_c);
+    }
+    g.frame_stride = d->frame_stride ? d->frame_stride : g.frame_end;
+    VC_CHECK(g.frame_stride >= g.frame_end, VC_ERR_ARG, "frame_stride %zu is below the frame's %zu bytes", g.frame_stride, g.frame_end);
+    const int* c = kYuvCoef[d->matrix][d->full_range];
+    g.yoff = d->full_range ? 0 : 16;
+    g.cy = c[0]; g.cvr = c[1]; g.cvg = c[2]; g.cug = c[3]; g.cub = c[4];
+    return VC_OK;
+}
+
+size_t yuv_batch_bytes(const YuvGeom& g, int b) { return (size_t)(b - 1) * g.frame_stride + g.frame_end; }
+
+// src: b frames laid out as g says, dst: [b][h][w][3], both device memory.  The 16-byte variant needs every address it forms aligned.
+int launch_yuv_to_bgr(const YuvGeom& g, const uint8_t* src, uint8_t* dst, int b, hipStream_t s) {
+    const bool fast = g.w % 16 == 0 && g.pitch_y % 16 == 0 && g.pitch_c % 16 == 0 && g.off_c % 16 == 0 && g.off_v % 16 == 0 &&
+                      g.frame_stride % 16 == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0;
+    const int ncg = (g.w + 15) / 16;
+    const long long total = (long long)b * (g.h / 2) * ncg;
+    const long long blocks = (total + 255) / 256;
+    VC_CHECK(blocks <= 0x7fffffffll, VC_ERR_CAPACITY, "batch too large for one conversion launch");
+    const dim3 grid((unsigned)blocks), block(256);
+    if (g.nv12) {
+        if (fast) hipLaunchKernelGGL((yuv_to_bgr_kernel<true, true>), grid, block, 0, s, src, dst, g, ncg, total);
+        else hipLaunchKernelGGL((yuv_to_bgr_kernel<true, false>), grid, block, 0, s, src, dst, g, ncg, total);
+    } else {
+        if (fast) hipLaunchKernelGGL((yuv_to_bgr_kernel<false, true>), grid, block, 0, s, src, dst, g, ncg, total);
+        else hipLaunchKernelGGL((yuv_to_bgr_kernel<false, false>), grid, block, 0, s, src, dst, g, ncg, total);
+    }
+    VC_HIP(hipGetLastError());
+    return VC_OK;
+}
+
+}  // namespace vc
+
+using namespace vc;
+
+extern "C" {
+
+int vc_yuv_desc_default(vc_yuv_desc* d) {
+    VC_CHECK(d, VC_ERR_ARG, "null argument");
+    memset(d, 0, sizeof(*d));
+    d->format = VC_PIX_NV12; d->matrix = VC_YUV_BT601; d->full_range = 0;
+    return VC_OK;
+}
+
+// Parity entry point.  The device output sits between two guard blocks that the call checks afterwards: a kernel that wrote
+// outside [b][h][w][3] is reported instead of returning a plausible image.
+int vc_yuv_to_bgr_host(const vc_yuv_desc* d, const uint8_t* yuv, int b, int h, int w, uint8_t* bgr_out) {
+    VC_CHECK(yuv && bgr_out, VC_ERR_ARG, "null argument");
+    YuvGeom g;
+    VC_TRY(yuv_resolve(d, b, h, w, g));
+    const size_t in_bytes = yuv_batch_bytes(g, b), out_bytes = (size_t)b * h * w * 3, guard = 256;
+    vc_engine tmp;
+    uint8_t *ds = nullptr, *dd = nullptr;
+    int st = dev_alloc(&tmp, (void**)&ds, in_bytes);
+    if (st == VC_OK) st = dev_alloc(&tmp, (void**)&dd, out_bytes + 2 * guard);
+    if (st == VC_OK && (hipMemcpy(ds, yuv, in_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemset(dd, 0xA5, out_bytes + 2 * guard) != hipSuccess)) {
+        set_error("upload failed");
+        st = VC_ERR_HIP;
+    }
+    if (st == VC_OK) st = launch_yuv_to_bgr(g, ds, dd + guard, b, nullptr);
+    if (st == VC_OK) {
+        uint8_t edge[512];
+        if (hipMemcpy(bgr_out, dd + guard, out_bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(edge, dd, guard, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(edge + guard, dd + guard + out_bytes, guard, hipMemcpyDeviceToHost) != hipSuccess) {
+            set_error("yuv_to_bgr_kernel failed: %s", hipGetErrorString(hipGetLastError()));
+            st = VC_ERR_HIP;
+        }
+        for (size_t i = 0; i < 2 * guard && st == VC_OK; ++i)
+            if (edge[i] != 0xA5) { set_error("yuv_to_bgr_kernel wrote outside its output (guard byte %zu)", i); st = VC_ERR_HIP; }
+    }
+    for (void* q : tmp.allocs) (void)hipFree(q);
+    tmp.allocs.clear();
+    return st;
+}
+
+int vc_yuv_to_bgr_dev(const vc_yuv_desc* d, const void* yuv_dev, int b, int h, int w, void* bgr_dev) {
+    VC_CHECK(yuv_dev && bgr_dev, VC_ERR_ARG, "null argument");
+    YuvGeom g;
+    VC_TRY(yuv_resolve(d, b, h, w, g));
+    return launch_yuv_to_bgr(g, (const uint8_t*)yuv_dev, (uint8_t*)bgr_dev, b, nullptr);
+}
+
+int vc_stream_stage_yuv_host(vc_engine* e, const vc_yuv_desc* d, const uint8_t* yuv_host, int b, int h, int w, void** frames_dev_out) {
+    VC_CHECK(e && yuv_host && frames_dev_out, VC_ERR_ARG, "null argument");
+    YuvGeom g;
+    VC_TRY(yuv_resolve(d, b, h, w, g));
+    int slot = 0;
+    VC_TRY(ingest_take_slot(e, b, h, w, &slot));
+    const size_t bytes = yuv_batch_bytes(g, b);
+    if (bytes > e->yuv_raw_bytes[slot]) {
+        // first YUV batch of this slot (or a pitch wider than any before): everything the copy stream still has in flight reads the old buffer
+        VC_HIP(hipStreamSynchronize(e->cstream));
+        const size_t tight = (size_t)e->cfg.max_batch * e->cfg.max_frame_h * e->cfg.max_frame_w * 3 / 2;
+        e->yuv_raw_bytes[slot] = 0;
+        VC_TRY(dev_realloc(e, (void**)&e->d_yuv_raw[slot], std::max(bytes, tight)));
+        e->yuv_raw_bytes[slot] = std::max(bytes, tight);
+    }
+    VC_HIP(hipMemcpyAsync(e->d_yuv_raw[slot], yuv_host, bytes, hipMemcpyHostToDevice, e->cstream));
+    VC_TRY(launch_yuv_to_bgr(g, e->d_yuv_raw[slot], e->d_ingest[slot], b, e->cstream));
+    return ingest_publish(e, slot, frames_dev_out);
+}
+
+int vc_stream_stage_yuv_dev(vc_engine* e, const vc_yuv_desc* d, const void* yuv_dev, int b, int h, int w, void** frames_dev_out) {
+    VC_CHECK(e && yuv_dev && frames_dev_out, VC_ERR_ARG, "null argument");
+    YuvGeom g;
+    VC_TRY(yuv_resolve(d, b, h, w, g));
+    int slot = 0;
+    VC_TRY(ingest_take_slot(e, b, h, w, &slot));
+    VC_TRY(launch_yuv_to_bgr(g, (const uint8_t*)yuv_dev, e->d_ingest[slot], b, e->cstream));
+    return ingest_publish(e, slot, frames_dev_out);
+}
+
+}  // extern "C"

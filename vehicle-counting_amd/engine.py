@@ -304,6 +304,23 @@ class Engine:
         L.check(L.lib().vc_stream_submit_host(self._h, C.c_void_p(frames_host_ptr), b, h, w, C.byref(out)))
         return out.value
 
+    def stream_stage_yuv_host(self, yuv_host_ptr, b, h, w, desc=None):
+        """Like stream_stage_host for a batch of 4:2:0 YUV frames in (pinned) host memory laid out as `desc` (`yuv_desc(...)`; None:
+        tight NV12, BT.601 limited): the raw bytes cross PCIe (1.5 B per pixel) and are converted on the engine's copy stream;
+        returns the device address of the BGR batch for stream_submit / stream_run*."""
+        out = C.c_void_p()
+        d = desc if desc is not None else yuv_desc()
+        L.check(L.lib().vc_stream_stage_yuv_host(self._h, C.byref(d), C.c_void_p(yuv_host_ptr), b, h, w, C.byref(out)))
+        return out.value
+
+    def stream_stage_yuv_dev(self, yuv_dev_ptr, b, h, w, desc=None):
+        """The same for YUV surfaces already in device memory (a hardware decoder's output): converted in place of the copy.  The
+        surfaces must stay valid until the batch's stream_run / stream_run_async call has returned."""
+        out = C.c_void_p()
+        d = desc if desc is not None else yuv_desc()
+        L.check(L.lib().vc_stream_stage_yuv_dev(self._h, C.byref(d), C.c_void_p(yuv_dev_ptr), b, h, w, C.byref(out)))
+        return out.value
+
     # ---------------------------------------------------------------- frame-sharded front end (one stream on several GPUs)
     def stream_embed(self, frames_dev_ptr, b, h, w):
         """Front half of the fused path for the oldest submission: (rows [n, 7] float64 = frame index in the batch, x1, y1, x2, y2,
@@ -476,6 +493,49 @@ def letterbox(rgb, net_h, net_w, precision="f32"):
     L.check(L.lib().vc_letterbox_host(L.ptr(im, C.c_uint8), im.shape[0], im.shape[1], net_h, net_w,
                                       L.PREC_BF16 if precision == "bf16" else L.PREC_F32, L.ptr(out, C.c_float)))
     return out
+
+
+def yuv_desc(fmt="nv12", matrix="bt601", full_range=False, pitch_y=0, pitch_c=0, offset_c=0, offset_v=0, frame_stride=0):
+    """vc_yuv_desc: layout of 4:2:0 frames in bytes (0 = tightly packed; include/vcount_hip.h)."""
+    if fmt not in L.PIX_ID:
+        raise ValueError(f"unknown pixel format {fmt!r}: one of {sorted(L.PIX_ID)}")
+    if matrix not in L.YUV_MATRIX_ID:
+        raise ValueError(f"unknown colour matrix {matrix!r}: one of {sorted(L.YUV_MATRIX_ID)}")
+    return L.YuvDesc(L.PIX_ID[fmt], L.YUV_MATRIX_ID[matrix], 1 if full_range else 0, int(pitch_y), int(pitch_c), int(offset_c), int(offset_v),
+                     int(frame_stride))
+
+
+def yuv_to_bgr(yuv, b, h, w, fmt="nv12", matrix="bt601", full_range=False, *, desc=None, **geometry):
+    """yuv_to_bgr_kernel on a host array: `yuv` = uint8 bytes of b frames laid out as the descriptor says -> (b, h, w, 3) BGR."""
+    d = desc if desc is not None else yuv_desc(fmt, matrix, full_range, **geometry)
+    src = np.ascontiguousarray(yuv, dtype=np.uint8).reshape(-1)
+    out = np.zeros((b, h, w, 3), np.uint8)
+    if b >= 1 and h >= 2 and w >= 2 and h % 2 == 0 and w % 2 == 0:      # the library refuses anything else; the length check needs a valid geometry
+        need = yuv_batch_bytes(d, b, h, w)
+        if need is not None and src.size < need:
+            raise ValueError(f"yuv holds {src.size} bytes, the descriptor needs {need}")
+    L.check(L.lib().vc_yuv_to_bgr_host(C.byref(d), L.ptr(src, C.c_uint8), b, h, w, L.ptr(out, C.c_uint8)))
+    return out
+
+
+def yuv_to_bgr_dev(yuv_dev_ptr, b, h, w, bgr_dev_ptr, desc=None):
+    """The conversion on the caller's device buffers (integer addresses), enqueued on the null stream; returns without waiting."""
+    d = desc if desc is not None else yuv_desc()
+    L.check(L.lib().vc_yuv_to_bgr_dev(C.byref(d), C.c_void_p(yuv_dev_ptr), b, h, w, C.c_void_p(bgr_dev_ptr)))
+
+
+def yuv_batch_bytes(d, b, h, w):
+    """Bytes that b frames of h x w occupy under descriptor d (the zeros resolved like the library does); None if a pitch is too small."""
+    crow = w if d.format == 0 else w // 2
+    py, pc = d.pitch_y or w, d.pitch_c or crow
+    if py < w or pc < crow:
+        return None
+    off_c = d.offset_c or py * h
+    end = off_c + pc * (h // 2 - 1) + crow
+    if d.format != 0:
+        off_v = d.offset_v or off_c + pc * (h // 2)
+        end = max(end, off_v + pc * (h // 2 - 1) + crow)
+    return (b - 1) * (d.frame_stride or end) + end
 
 
 def nms(boxes, conf, cls, iou=0.45, max_det=300, max_cand=4096):

@@ -40,6 +40,50 @@ class FrameSource:
             yield {"imgs": [f[:, :, ::-1]], "ori_imgs": [f], "frames": [i + 1]}       # BGR->RGB view, 1-based id
 
 
+class YuvFrameSource:
+    """In-memory video as a decoder delivers it: T frames of 4:2:0 YUV (`fmt` "nv12" or "i420"), `data` = uint8 array whose first axis
+    is the frame (or a flat buffer of T whole frames).  Geometry in bytes, 0 = tightly packed (include/vcount_hip.h: vc_yuv_desc):
+    `pitch` is the luma pitch; unless given, the chroma pitch follows it (`pitch` for nv12, `pitch // 2` for i420), the planes
+    follow each other without a gap and a frame ends with the last whole row of its last plane.  Only `CountingPipeline.run_stream` takes it: the conversion to BGR runs on the device."""
+
+    def __init__(self, data, h, w, fmt="nv12", matrix="bt601", full_range=False, pitch=0, pitch_c=0, offset_c=0, offset_v=0,
+                 frame_stride=0, name="cam_04.mp4", fps=10):
+        from .engine import yuv_batch_bytes, yuv_desc
+        h, w, pitch, pitch_c = int(h), int(w), int(pitch), int(pitch_c)
+        if h < 2 or w < 2 or h % 2 or w % 2:
+            raise ValueError(f"4:2:0 frames need an even height and width, got {h}x{w}")
+        if pitch and not pitch_c:
+            if fmt == "i420" and pitch % 2:
+                raise ValueError("an odd luma pitch needs an explicit pitch_c for i420")
+            pitch_c = pitch if fmt == "nv12" else pitch // 2
+        self.desc = yuv_desc(fmt, matrix, full_range, pitch, pitch_c, offset_c, offset_v, frame_stride)
+        frame_bytes = yuv_batch_bytes(self.desc, 1, h, w)
+        if frame_bytes is None:
+            raise ValueError(f"pitch {pitch} / {pitch_c} is below the row width of a {w}-wide {fmt} frame")
+        d = self.desc                                      # default stride: whole rows of the last plane (= the frame's bytes when tight)
+        pc, hc = d.pitch_c or (w if fmt == "nv12" else w // 2), h // 2
+        off_c = d.offset_c or (d.pitch_y or w) * h
+        whole = off_c + pc * hc if fmt == "nv12" else max(off_c + pc * hc, (d.offset_v or off_c + pc * hc) + pc * hc)
+        stride = int(frame_stride) or whole
+        if stride < frame_bytes:
+            raise ValueError(f"frame_stride {stride} is below the frame's {frame_bytes} bytes")
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        if data.ndim == 1:
+            if data.size == 0 or data.size % stride:
+                raise ValueError(f"{data.size} bytes are not a whole number of {stride}-byte frames")
+            data = data.reshape(-1, stride)
+        else:
+            data = data.reshape(len(data), -1)
+        if data.shape[1] != stride:
+            raise ValueError(f"a {h}x{w} {fmt} frame of this geometry has {stride} bytes, got {data.shape[1]}")
+        self.desc.frame_stride = stride
+        self.data, self.h, self.w, self.fmt = data, h, w, fmt
+        self.video_info = {"name": name, "width": w, "height": h, "fps": fps, "num_frames": len(data)}
+
+    def __len__(self):
+        return len(self.data)
+
+
 class CountingPipeline:
     def __init__(self, args, config, cam_config, engine=None, class_names=None, synthetic=False):
         # the ReID checkpoint of the reference's cam_configs.yaml (`checkpoint: .../ckpt.t7`, handed to every DeepSort at
@@ -165,16 +209,26 @@ class CountingPipeline:
         embedded (`stream_run_async` / `stream_collect`); rows are identical, they arrive one batch later.
         host_frames=True: the frames stay in (pinned) host memory, as the reference's loader delivers them, and cross PCIe batch by
         batch -- batch n+2 is staged (`stream_stage_host`) while the detector works on batch n+1, so a video of any length needs four
-        batches of device memory; otherwise the whole clip is uploaded once."""
+        batches of device memory; otherwise the whole clip is uploaded once.
+        A `YuvFrameSource` takes the same modes: its 4:2:0 frames are converted to BGR on the device as they are staged
+        (`stream_stage_yuv_host` from pinned YUV, half the PCIe bytes of BGR, or `stream_stage_yuv_dev` from the uploaded clip)."""
         import torch
         tracker, counter = self._stages(cam_name, source.video_info, zone_path)
         obj = {"frames": [], "tracks": [], "labels": [], "boxes": []}
-        frames = source.frames
-        t, h, w, _ = frames.shape
+        yuv = isinstance(source, YuvFrameSource)
+        if yuv:
+            frames, t, h, w = source.data, len(source.data), source.h, source.w
+        else:
+            frames = source.frames
+            t, h, w, _ = frames.shape
         starts = list(range(0, t, batch))
         size = lambda n: min(batch, t - starts[n])
         ptr = {}
-        if host_frames:
+        if yuv:                                             # every batch goes through an ingest slot: staged two ahead in both modes
+            keep = torch.from_numpy(frames).pin_memory() if host_frames else torch.from_numpy(frames).to(f"cuda:{self.engine.cfg.device}")
+            convert = self.engine.stream_stage_yuv_host if host_frames else self.engine.stream_stage_yuv_dev
+            stage = lambda n: ptr.__setitem__(n, convert(keep[starts[n]:starts[n] + size(n)].data_ptr(), size(n), h, w, source.desc))
+        elif host_frames:
             host = torch.from_numpy(frames).pin_memory()
             stage = lambda n: ptr.__setitem__(n, self.engine.stream_stage_host(host[starts[n]:starts[n] + size(n)].data_ptr(), size(n), h, w))
         else:

@@ -62,3 +62,39 @@ def synth_frames(n_frames, H, W, n_obj=8, seed=SEED, bounce=False):
             f[y1:y2, x1:x2] = tex[i][np.clip(ty, 0, 15)][:, np.clip(tx, 0, 15)]
         frames[t] = np.clip(f, 0, 255).astype(np.uint8)
     return frames
+
+
+# forward matrices (Kr, Kb) of the two standards; tests and tools only -- the product converts YUV -> BGR on the device
+_KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
+
+
+def bgr_to_yuv420(frames_bgr, fmt="nv12", matrix="bt601", full_range=False):
+    """(T, H, W, 3) uint8 BGR -> (T, H * W * 3 // 2) uint8 tightly packed 4:2:0 frames: the Y plane, then interleaved U,V rows (nv12)
+    or the U plane and the V plane (i420).  Float arithmetic with rounding, chroma = mean of the 2 x 2 block.  H and W must be even."""
+    f = np.asarray(frames_bgr, dtype=np.float64)
+    t, h, w, _ = f.shape
+    if h % 2 or w % 2:
+        raise ValueError(f"4:2:0 needs an even frame size, got {h}x{w}")
+    if fmt not in ("nv12", "i420"):
+        raise ValueError(f"unknown pixel format {fmt!r}")
+    kr, kb = _KR_KB[matrix]
+    b, g, r = f[..., 0], f[..., 1], f[..., 2]
+    y = kr * r + (1 - kr - kb) * g + kb * b                        # 0..255
+    cb = (b - y) / (2 * (1 - kb))                                  # -127.5..127.5
+    cr = (r - y) / (2 * (1 - kr))
+    mean = lambda p: p.reshape(t, h // 2, 2, w // 2, 2).mean(axis=(2, 4))
+    cb, cr = mean(cb), mean(cr)
+    if full_range:
+        yq, uq, vq = y, cb + 128, cr + 128
+    else:
+        yq, uq, vq = 16 + y * 219 / 255, 128 + cb * 224 / 255, 128 + cr * 224 / 255
+    q = lambda p: np.clip(np.rint(p), 0, 255).astype(np.uint8)
+    yq, uq, vq = q(yq), q(uq), q(vq)
+    out = np.empty((t, h * w * 3 // 2), np.uint8)
+    out[:, : h * w] = yq.reshape(t, -1)
+    if fmt == "nv12":
+        out[:, h * w:] = np.stack([uq, vq], axis=-1).reshape(t, -1)
+    else:
+        out[:, h * w: h * w * 5 // 4] = uq.reshape(t, -1)
+        out[:, h * w * 5 // 4:] = vq.reshape(t, -1)
+    return out
