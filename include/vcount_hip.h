@@ -280,6 +280,45 @@ int vc_allgather_counts(vc_engine* e, const int32_t* local, int n, int32_t* out)
  * the way the reference's draw_* helpers are called.  Pixel parity with OpenCV's rasteriser / fonts is not claimed. */
 int vc_overlay(vc_engine* e, void* frames_dev, int b, int h, int w, const int32_t* prims12, const int32_t* frame_first);
 
+/* ---- annotated video out: BGR -> 4:2:0 YUV egress and the asynchronous render path ----------------------------------------------
+ * The reference's second artefact (VideoWriter.write_full_to_video -> visualize_merged, modules/datasets.py:132-145) leaves through
+ * an encoder, and an encoder takes 4:2:0 YUV.  bgr_to_yuv_kernel is the inverse of the ingest conversion, laid out by the same
+ * vc_yuv_desc under the same rules (bad geometry is VC_ERR_ARG before any HIP call).  Arithmetic (integer, 32-bit signed):
+ *   Y = clamp((KYR*R + KYG*G + KYB*B + (1 << 19) + (YOFF << 20)) >> 20)  per pixel, YOFF = 16 (limited) or 0 (full range);
+ *   U = clamp((KUR*Rm + KUG*Gm + KUB*Bm + (1 << 19) + (128 << 20)) >> 20), V alike with KV*, per 2 x 2 block, where
+ *   Rm, Gm, Bm = (sum over the block + 2) >> 2; constants int(round(literal * 2^20)).
+ * Bytes of the destination that belong to no plane (pitch padding, gaps between planes and frames) are NOT written.
+ * vc_bgr_to_yuv_dev runs on the caller's device buffers (bgr_dev: b x h x w x 3 bytes), enqueued on the NULL stream, and returns
+ * without waiting for it. */
+int vc_bgr_to_yuv_dev(const vc_yuv_desc* d, const void* bgr_dev, int b, int h, int w, void* yuv_dev);
+
+/* Render context: per batch  source -> BGR work buffer -> overlay (the vc_overlay lists) -> bgr_to_yuv -> the caller's surface, all
+ * enqueued, nothing waited for.  It belongs to an engine (device; vc_engine_destroy destroys the contexts that are left) but is
+ * independent of the detector -- an engine with with_detector = 0, with_reid = 0 serves -- and of the stream path: it uses neither
+ * the four ingest slots nor the pending submissions.  It owns two streams (in, out) and, per batch in flight (`depth`, 1..4), a
+ * raw-input buffer, a BGR work buffer and a YUV output buffer, each allocated on its first use. */
+typedef struct vc_render vc_render;
+#define VC_SRC_BGR_HOST 0  /* b x h x w x 3 BGR in (pinned) host memory */
+#define VC_SRC_BGR_DEV 1   /* the same in device memory: copied into the work buffer, the caller's frames are never painted */
+#define VC_SRC_YUV_HOST 2  /* 4:2:0 frames laid out as `desc` in (pinned) host memory: 1.5 B per pixel over PCIe, converted on the device */
+#define VC_SRC_YUV_DEV 3   /* decoder surfaces in device memory */
+typedef struct vc_render_src {
+    int kind;              /* VC_SRC_* */
+    const void* data;
+    vc_yuv_desc desc;      /* VC_SRC_YUV_* only */
+} vc_render_src;
+int vc_render_create(vc_engine* e, int max_batch, int max_h, int max_w, int depth, vc_render** out);
+int vc_render_destroy(vc_render* r);
+/* Enqueues one batch and returns at once.  prims12 / frame_first: the lists of vc_overlay, both NULL = no overlay; they are COPIED
+ * by this call and may be reused when it returns.  out: a device surface (out_is_dev = 1) or (pinned) host memory that receives the
+ * plane bytes only, laid out as out_desc.  The source frames and `out` must stay valid until the batch has been collected.
+ * Refusals, all before anything is enqueued: bad geometry of either descriptor or bad lists VC_ERR_ARG; a batch or frame larger
+ * than the context VC_ERR_CAPACITY; `depth` batches already outstanding VC_ERR_STATE. */
+int vc_render_submit(vc_render* r, const vc_render_src* src, int b, int h, int w, const int32_t* prims12, const int32_t* frame_first,
+                     const vc_yuv_desc* out_desc, void* out, int out_is_dev);
+/* Blocks until the OLDEST outstanding batch is complete in its `out`; VC_ERR_STATE with nothing outstanding. */
+int vc_render_collect(vc_render* r);
+
 /* Host half of vc_allgather_rows: RCCL gathers equal-sized blocks, so every rank contributes `max_rows` rows (its own counts[r] rows
  * followed by padding) and the receive buffer is rank-major [world][max_rows][row_bytes].  This compacts such a padded buffer into
  * the first sum(counts) rows of `out` in rank-major order -- for frame chunks dealt round-robin to the ranks that is frame order
@@ -338,6 +377,9 @@ int vc_lap_host(const double* cost, int nr, int nc, int* row4col_rows, int* cols
 int vc_letterbox_host(const uint8_t* rgb, int h, int w, int net_h, int net_w, int precision, float* out_nhwc3);
 /* yuv_to_bgr_kernel (the stream path's ingest conversion) on host arrays: b frames laid out as `d` says -> packed BGR b x h x w x 3 */
 int vc_yuv_to_bgr_host(const vc_yuv_desc* d, const uint8_t* yuv, int b, int h, int w, uint8_t* bgr_out);
+/* bgr_to_yuv_kernel (the render path's egress conversion) on host arrays: packed BGR b x h x w x 3 -> b frames laid out as `d` says.
+ * Only plane bytes of yuv_out change. */
+int vc_bgr_to_yuv_host(const vc_yuv_desc* d, const uint8_t* bgr, int b, int h, int w, uint8_t* yuv_out);
 /* VideoCounting.run zone filter (modules/track.py:102-104): inside[i] = any corner of boxes[i] in the polygon. Host only. */
 int vc_zone_filter_host(const double* polygon_xy, int n_points, const int64_t* boxes_xyxy, int n, uint8_t* inside);
 /* candidates (already conf-filtered, in the reference's candidate order): boxes xyxy, conf, class -> kept rows */

@@ -21,6 +21,7 @@ FEAT_DIM = 512
 PROF_CONV, PROF_DETECT_AUX, PROF_REID_AUX, PROF_TRACK = 0, 1, 2, 3
 PIX_ID = {"nv12": 0, "i420": 1}
 YUV_MATRIX_ID = {"bt601": 0, "bt709": 1}
+RENDER_SRC_ID = {"bgr_host": 0, "bgr_dev": 1, "yuv_host": 2, "yuv_dev": 3}
 
 
 class VcError(RuntimeError):
@@ -52,6 +53,11 @@ class YuvDesc(C.Structure):
     """vc_yuv_desc: byte geometry of 4:2:0 frames, 0 = tightly packed."""
     _fields_ = [("format", C.c_int), ("matrix", C.c_int), ("full_range", C.c_int), ("pitch_y", C.c_int), ("pitch_c", C.c_int),
                 ("offset_c", C.c_size_t), ("offset_v", C.c_size_t), ("frame_stride", C.c_size_t)]
+
+
+class RenderSrc(C.Structure):
+    """vc_render_src: one batch of source frames for vc_render_submit."""
+    _fields_ = [("kind", C.c_int), ("data", C.c_void_p), ("desc", YuvDesc)]
 
 
 _P = C.POINTER
@@ -101,6 +107,12 @@ SIGNATURES = {
     "vc_stream_stage_yuv_dev": [_vp, _P(YuvDesc), _vp, _i, _i, _i, _P(_vp)],
     "vc_yuv_to_bgr_host": [_P(YuvDesc), _pu8, _i, _i, _i, _pu8],
     "vc_yuv_to_bgr_dev": [_P(YuvDesc), _vp, _i, _i, _i, _vp],
+    "vc_bgr_to_yuv_host": [_P(YuvDesc), _pu8, _i, _i, _i, _pu8],
+    "vc_bgr_to_yuv_dev": [_P(YuvDesc), _vp, _i, _i, _i, _vp],
+    "vc_render_create": [_vp, _i, _i, _i, _i, _P(_vp)],
+    "vc_render_destroy": [_vp],
+    "vc_render_submit": [_vp, _P(RenderSrc), _i, _i, _i, _pi, _pi, _P(YuvDesc), _vp, _i],
+    "vc_render_collect": [_vp],
     "vc_stream_run_async": [_vp, _pi, _i, _vp, _i, _i, _i, _i],
     "vc_stream_collect": [_vp, _pl, _i, _pi, _pi, _i],
     "vc_stream_run_async_multi": [_vp, _pi, _i, _i, _pi, _vp, _i, _i, _i, _i],

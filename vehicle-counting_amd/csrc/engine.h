@@ -108,7 +108,18 @@ struct TrackStage {
     std::vector<int> last_task_of;           // per entry of tracker_dets: device index of the tracker's last task
 };
 
+// A validated vc_yuv_desc with the zeros resolved (yuv_ingest.hip: yuv_resolve); all byte quantities.  Shared by the ingest
+// conversion (yuv_ingest.hip), the egress conversion (yuv_egress.hip) and the render path (render.hip).
+struct YuvGeom {
+    int nv12, h, w, pitch_y, pitch_c;
+    size_t off_c, off_v, frame_stride, frame_end;      // frame_end: one past the last byte any plane of a frame occupies
+    int yoff, cy, cvr, cvg, cug, cub;                   // decode: y = max(0, Y - yoff) * cy: full range is yoff = 0, cy = 1 << 20
+    int matrix, full_range;                             // as the descriptor named them (the egress kernel picks its own constants)
+};
+
 }  // namespace vc
+
+struct vc_render;
 
 struct vc_engine {
     vc_engine_config cfg{};
@@ -243,6 +254,7 @@ struct vc_engine {
     void* d_gather_feat = nullptr; size_t gather_feat_bytes = 0;
     void* h_gather = nullptr; size_t h_gather_bytes = 0;
     void* d_overlay = nullptr; size_t overlay_bytes = 0;      // primitive lists of vc_overlay (overlay.hip)
+    std::vector<vc_render*> renders;                          // live render contexts (render.hip); vc_engine_destroy destroys what is left
 
     // ---- measurement ----------------------------------------------------------------------------------
     bool profiling = false;
@@ -283,6 +295,16 @@ int prof_launch(vc_engine* e, int cat, double flops, double bytes, int status);
 // slots on first use, and hands out the next slot round-robin.  The caller enqueues its work on e->cstream, then calls ingest_publish.
 int ingest_take_slot(vc_engine* e, int b, int h, int w, int* slot);
 int ingest_publish(vc_engine* e, int slot, void** frames_dev_out);
+// yuv_ingest.hip / yuv_egress.hip: descriptor validation (pure host code) and the two conversions, both enqueued on `s`
+int yuv_resolve(const vc_yuv_desc* d, int b, int h, int w, YuvGeom& g);
+size_t yuv_batch_bytes(const YuvGeom& g, int b);
+int launch_yuv_to_bgr(const YuvGeom& g, const uint8_t* src, uint8_t* dst, int b, hipStream_t s);
+int launch_bgr_to_yuv(const YuvGeom& g, const uint8_t* src_bgr, uint8_t* dst_yuv, int b, hipStream_t s);
+// overlay.hip: the checks of vc_overlay on the host lists, and overlay_kernel over device-resident lists on `s` (no host wait)
+int overlay_check_lists(int b, const int32_t* prims12, const int32_t* frame_first);
+int launch_overlay(uint8_t* frames_dev, int b, int h, int w, const void* d_prims, const int* d_first, hipStream_t s);
+// render.hip
+void render_destroy_all(vc_engine* e);
 struct ProfScope {
     vc_engine* e; int cat; double flops, bytes;
     hipStream_t s;

@@ -74,14 +74,27 @@ __global__ __launch_bounds__(256) void overlay_kernel(uint8_t* frames, int H, in
     }
 }
 
+int overlay_check_lists(int b, const int32_t* prims12, const int32_t* frame_first) {
+    VC_CHECK(prims12 && frame_first && b >= 1, VC_ERR_ARG, "bad argument");
+    VC_CHECK(frame_first[0] == 0, VC_ERR_ARG, "frame_first[0] must be 0");
+    for (int i = 0; i < b; ++i) VC_CHECK(frame_first[i + 1] >= frame_first[i], VC_ERR_ARG, "frame_first must not decrease");
+    return VC_OK;
+}
+
+// d_prims: OvPrim[frame_first[b]], d_first: int[b + 1], both already (being) copied to the device in front of this launch on `s`
+int launch_overlay(uint8_t* frames_dev, int b, int h, int w, const void* d_prims, const int* d_first, hipStream_t s) {
+    hipLaunchKernelGGL(overlay_kernel, dim3(b), dim3(256), 0, s, frames_dev, h, w, (const OvPrim*)d_prims, d_first);
+    VC_HIP(hipGetLastError());
+    return VC_OK;
+}
+
 }  // namespace vc
 
 using namespace vc;
 
 extern "C" int vc_overlay(vc_engine* e, void* frames_dev, int b, int h, int w, const int32_t* prims12, const int32_t* frame_first) {
     VC_CHECK(e && frames_dev && prims12 && frame_first && b >= 1 && h >= 1 && w >= 1, VC_ERR_ARG, "bad argument");
-    VC_CHECK(frame_first[0] == 0, VC_ERR_ARG, "frame_first[0] must be 0");
-    for (int i = 0; i < b; ++i) VC_CHECK(frame_first[i + 1] >= frame_first[i], VC_ERR_ARG, "frame_first must not decrease");
+    VC_TRY(overlay_check_lists(b, prims12, frame_first));
     const int n = frame_first[b];
     if (n == 0) return VC_OK;
     VC_HIP(hipSetDevice(e->cfg.device));
@@ -94,8 +107,7 @@ extern "C" int vc_overlay(vc_engine* e, void* frames_dev, int b, int h, int w, c
     int* d_first = (int*)((char*)e->d_overlay + (size_t)n * sizeof(OvPrim));
     VC_HIP(hipMemcpyAsync(d_prims, prims12, (size_t)n * sizeof(OvPrim), hipMemcpyHostToDevice, e->stream));
     VC_HIP(hipMemcpyAsync(d_first, frame_first, (size_t)(b + 1) * sizeof(int), hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(overlay_kernel, dim3(b), dim3(256), 0, e->stream, (uint8_t*)frames_dev, h, w, d_prims, d_first);
-    VC_HIP(hipGetLastError());
+    VC_TRY(launch_overlay((uint8_t*)frames_dev, b, h, w, d_prims, d_first, e->stream));
     VC_HIP(hipStreamSynchronize(e->stream));
     return VC_OK;
 }

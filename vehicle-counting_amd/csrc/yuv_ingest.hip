@@ -21,12 +21,6 @@
 
 namespace vc {
 
-struct YuvGeom {                 // a validated vc_yuv_desc with the zeros resolved; all byte quantities
-    int nv12, h, w, pitch_y, pitch_c;
-    size_t off_c, off_v, frame_stride, frame_end;      // frame_end: one past the last byte any plane of a frame occupies
-    int yoff, cy, cvr, cvg, cug, cub;                   // y = max(0, Y - yoff) * cy: full range is yoff = 0, cy = 1 << 20
-};
-
 namespace {
 
 // int(literal * 2^20), truncated toward zero: {CY, CVR, CVG, CUG, CUB} per [matrix][full_range]
@@ -183,6 +177,7 @@ int yuv_resolve(const vc_yuv_desc* d, int b, int h, int w, YuvGeom& g) {
     g.frame_stride = d->frame_stride ? d->frame_stride : g.frame_end;
     VC_CHECK(g.frame_stride >= g.frame_end, VC_ERR_ARG, "frame_stride %zu is below the frame's %zu bytes", g.frame_stride, g.frame_end);
     const int* c = kYuvCoef[d->matrix][d->full_range];
+    g.matrix = d->matrix; g.full_range = d->full_range;
     g.yoff = d->full_range ? 0 : 16;
     g.cy = c[0]; g.cvr = c[1]; g.cvg = c[2]; g.cug = c[3]; g.cub = c[4];
     return VC_OK;

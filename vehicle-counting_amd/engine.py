@@ -62,6 +62,8 @@ class Engine:
 
     def close(self):
         if self._h:
+            for r in list(getattr(self, "_renderers", ())):      # their contexts die with the engine: close them first
+                r.close()
             L.lib().vc_engine_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -536,6 +538,90 @@ def yuv_batch_bytes(d, b, h, w):
         off_v = d.offset_v or off_c + pc * (h // 2)
         end = max(end, off_v + pc * (h // 2 - 1) + crow)
     return (b - 1) * (d.frame_stride or end) + end
+
+
+def bgr_to_yuv(bgr, fmt="nv12", matrix="bt601", full_range=False, *, desc=None, **geometry):
+    """bgr_to_yuv_kernel on a host array: (b, h, w, 3) uint8 BGR -> flat uint8 bytes of b frames laid out as the descriptor says
+    (`yuv_batch_bytes` of them).  Bytes that belong to no plane come back as the zero fill."""
+    d = desc if desc is not None else yuv_desc(fmt, matrix, full_range, **geometry)
+    src = np.ascontiguousarray(bgr, dtype=np.uint8)
+    if src.ndim != 4 or src.shape[3] != 3:
+        raise ValueError(f"bgr must be (b, h, w, 3), got {src.shape}")
+    b, h, w, _ = src.shape
+    need = yuv_batch_bytes(d, b, h, w) if b >= 1 and h >= 2 and w >= 2 else None      # the library refuses what has no size
+    out = np.zeros(need if need is not None else 16, np.uint8)
+    L.check(L.lib().vc_bgr_to_yuv_host(C.byref(d), L.ptr(src.reshape(-1), C.c_uint8), b, h, w, L.ptr(out, C.c_uint8)))
+    return out
+
+
+def bgr_to_yuv_dev(bgr_dev_ptr, b, h, w, yuv_dev_ptr, desc=None):
+    """The conversion on the caller's device buffers (integer addresses), enqueued on the null stream; returns without waiting."""
+    d = desc if desc is not None else yuv_desc()
+    L.check(L.lib().vc_bgr_to_yuv_dev(C.byref(d), C.c_void_p(bgr_dev_ptr), b, h, w, C.c_void_p(yuv_dev_ptr)))
+
+
+class Renderer:
+    """A render context of `engine` (vc_render): per batch  source -> overlay -> 4:2:0 YUV -> the caller's surface, asynchronous,
+    `depth` batches in flight.  `submit` enqueues and returns; `collect` waits for the oldest batch.  Usable as a context manager."""
+
+    def __init__(self, engine, max_batch=16, max_hw=(720, 1280), depth=2):
+        self._h = C.c_void_p()
+        self.engine, self.depth = engine, depth
+        L.check(L.lib().vc_render_create(engine._h, max_batch, max_hw[0], max_hw[1], depth, C.byref(self._h)))
+        engine._renderers = getattr(engine, "_renderers", [])
+        engine._renderers.append(self)
+        self._alive = []                                   # per outstanding batch: the arrays its addresses point into
+
+    @staticmethod
+    def _addr(x):
+        return (x.ctypes.data, x) if isinstance(x, np.ndarray) else (int(x), None)
+
+    def submit(self, src, b, h, w, out, *, kind="bgr_host", src_desc=None, prims=None, first=None, out_desc=None, out_is_dev=False):
+        """src / out: integer addresses (torch `data_ptr()`) or C-contiguous uint8 arrays for host memory; kind: "bgr_host",
+        "bgr_dev", "yuv_host" or "yuv_dev" (the YUV kinds with `src_desc`); prims / first: the lists of `overlay.overlay`
+        (None = no overlay; copied by the call); out_desc: layout of `out` (None: tight NV12, BT.601 limited).  Source and
+        destination must stay valid until the batch has been collected."""
+        sa, sk = self._addr(src)
+        oa, ok = self._addr(out)
+        rs = L.RenderSrc(L.RENDER_SRC_ID[kind], sa, src_desc if src_desc is not None else yuv_desc())
+        od = out_desc if out_desc is not None else yuv_desc()
+        p = f = None
+        if prims is not None:
+            p = np.ascontiguousarray(prims, dtype=np.int32).reshape(-1)
+            f = np.ascontiguousarray(first, dtype=np.int32)
+        L.check(L.lib().vc_render_submit(self._h, C.byref(rs), b, h, w, L.ptr(p, C.c_int), L.ptr(f, C.c_int), C.byref(od), C.c_void_p(oa),
+                                         1 if out_is_dev else 0))
+        self._alive.append((sk, ok))
+
+    def collect(self):
+        """Block until the oldest outstanding batch is complete in its destination."""
+        L.check(L.lib().vc_render_collect(self._h))
+        if self._alive:
+            self._alive.pop(0)
+
+    @property
+    def outstanding(self):
+        return len(self._alive)
+
+    def close(self):
+        if self._h:
+            L.lib().vc_render_destroy(self._h)
+            self._h = C.c_void_p()
+            self._alive = []
+            if self in getattr(self.engine, "_renderers", ()):
+                self.engine._renderers.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def nms(boxes, conf, cls, iou=0.45, max_det=300, max_cand=4096):

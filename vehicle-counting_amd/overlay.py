@@ -159,6 +159,16 @@ class PrimList:
             self.draw_one_box(img_hw, box, f"id: {r['track_id']}", f"cls: {r['label']}", r["color"])
 
 
+def track_color(label, track_id):
+    """A fixed (B, G, R) colour per (label, track id) for rows that carry none: the reference draws one from an unseeded RNG when it
+    writes the CSV (Q10), so there is no value to reproduce -- only the need that a track keeps its colour."""
+    x = (int(label) * 0x9E3779B1 + int(track_id) * 0x85EBCA6B + 0x27D4EB2F) & 0xFFFFFFFF
+    x ^= x >> 15
+    x = (x * 0x2C1B3C6D) & 0xFFFFFFFF
+    x ^= x >> 12
+    return (64 + (x & 127), 64 + ((x >> 8) & 127), 64 + ((x >> 16) & 127))
+
+
 def count_frame_directions(rows, count_dict):
     """counting/utils.py:276-297: count[direction][label] += 1 at each track's last frame; the text of the running totals."""
     for r in rows:

@@ -40,6 +40,31 @@ class FrameSource:
             yield {"imgs": [f[:, :, ::-1]], "ori_imgs": [f], "frames": [i + 1]}       # BGR->RGB view, 1-based id
 
 
+def _yuv_geometry(h, w, fmt, matrix, full_range, pitch, pitch_c, offset_c, offset_v, frame_stride):
+    """(vc_yuv_desc, bytes from one frame to the next) of a clip of 4:2:0 frames.  Unless given, the chroma pitch follows the luma
+    pitch (`pitch` for nv12, `pitch // 2` for i420), the planes follow each other without a gap, and a frame ends with the last whole
+    row of its last plane."""
+    from .engine import yuv_batch_bytes, yuv_desc
+    h, w, pitch, pitch_c = int(h), int(w), int(pitch), int(pitch_c)
+    if h < 2 or w < 2 or h % 2 or w % 2:
+        raise ValueError(f"4:2:0 frames need an even height and width, got {h}x{w}")
+    if pitch and not pitch_c:
+        if fmt == "i420" and pitch % 2:
+            raise ValueError("an odd luma pitch needs an explicit pitch_c for i420")
+        pitch_c = pitch if fmt == "nv12" else pitch // 2
+    d = yuv_desc(fmt, matrix, full_range, pitch, pitch_c, offset_c, offset_v, frame_stride)
+    frame_bytes = yuv_batch_bytes(d, 1, h, w)
+    if frame_bytes is None:
+        raise ValueError(f"pitch {pitch} / {pitch_c} is below the row width of a {w}-wide {fmt} frame")
+    pc, hc = d.pitch_c or (w if fmt == "nv12" else w // 2), h // 2    # default stride: whole rows of the last plane (= the frame's bytes when tight)
+    off_c = d.offset_c or (d.pitch_y or w) * h
+    whole = off_c + pc * hc if fmt == "nv12" else max(off_c + pc * hc, (d.offset_v or off_c + pc * hc) + pc * hc)
+    stride = int(frame_stride) or whole
+    if stride < frame_bytes:
+        raise ValueError(f"frame_stride {stride} is below the frame's {frame_bytes} bytes")
+    return d, stride
+
+
 class YuvFrameSource:
     """In-memory video as a decoder delivers it: T frames of 4:2:0 YUV (`fmt` "nv12" or "i420"), `data` = uint8 array whose first axis
     is the frame (or a flat buffer of T whole frames).  Geometry in bytes, 0 = tightly packed (include/vcount_hip.h: vc_yuv_desc):
@@ -48,25 +73,8 @@ class YuvFrameSource:
 
     def __init__(self, data, h, w, fmt="nv12", matrix="bt601", full_range=False, pitch=0, pitch_c=0, offset_c=0, offset_v=0,
                  frame_stride=0, name="cam_04.mp4", fps=10):
-        from .engine import yuv_batch_bytes, yuv_desc
-        h, w, pitch, pitch_c = int(h), int(w), int(pitch), int(pitch_c)
-        if h < 2 or w < 2 or h % 2 or w % 2:
-            raise ValueError(f"4:2:0 frames need an even height and width, got {h}x{w}")
-        if pitch and not pitch_c:
-            if fmt == "i420" and pitch % 2:
-                raise ValueError("an odd luma pitch needs an explicit pitch_c for i420")
-            pitch_c = pitch if fmt == "nv12" else pitch // 2
-        self.desc = yuv_desc(fmt, matrix, full_range, pitch, pitch_c, offset_c, offset_v, frame_stride)
-        frame_bytes = yuv_batch_bytes(self.desc, 1, h, w)
-        if frame_bytes is None:
-            raise ValueError(f"pitch {pitch} / {pitch_c} is below the row width of a {w}-wide {fmt} frame")
-        d = self.desc                                      # default stride: whole rows of the last plane (= the frame's bytes when tight)
-        pc, hc = d.pitch_c or (w if fmt == "nv12" else w // 2), h // 2
-        off_c = d.offset_c or (d.pitch_y or w) * h
-        whole = off_c + pc * hc if fmt == "nv12" else max(off_c + pc * hc, (d.offset_v or off_c + pc * hc) + pc * hc)
-        stride = int(frame_stride) or whole
-        if stride < frame_bytes:
-            raise ValueError(f"frame_stride {stride} is below the frame's {frame_bytes} bytes")
+        h, w = int(h), int(w)
+        self.desc, stride = _yuv_geometry(h, w, fmt, matrix, full_range, pitch, pitch_c, offset_c, offset_v, frame_stride)
         data = np.ascontiguousarray(data, dtype=np.uint8)
         if data.ndim == 1:
             if data.size == 0 or data.size % stride:
@@ -82,6 +90,49 @@ class YuvFrameSource:
 
     def __len__(self):
         return len(self.data)
+
+
+class YuvFrameSink:
+    """Where a rendered clip lands: `n_frames` 4:2:0 frames (`fmt` "nv12" or "i420") of the geometry YuvFrameSource describes, as an
+    encoder takes them.  By default the sink owns host memory for the whole clip (pinned when a GPU is present, zero-filled, so the
+    bytes that belong to no plane stay zero): `data` is the (n_frames, frame_stride) uint8 array, `frame(i)` one frame's bytes.  With
+    `device_ptr` the clip is a caller's device surface of `nbytes` bytes instead; `data` is then None."""
+
+    def __init__(self, h, w, fmt="nv12", matrix="bt601", full_range=False, pitch=0, pitch_c=0, offset_c=0, offset_v=0, frame_stride=0,
+                 n_frames=1, device_ptr=None):
+        h, w, n_frames = int(h), int(w), int(n_frames)
+        if n_frames < 1:
+            raise ValueError(f"a sink needs at least one frame, got {n_frames}")
+        self.desc, stride = _yuv_geometry(h, w, fmt, matrix, full_range, pitch, pitch_c, offset_c, offset_v, frame_stride)
+        self.desc.frame_stride = stride
+        self.h, self.w, self.fmt, self.n_frames, self.frame_stride = h, w, fmt, n_frames, stride
+        self.nbytes = n_frames * stride
+        self.device_ptr = int(device_ptr) if device_ptr is not None else None
+        self.data = self._keep = None
+        if self.device_ptr is None:
+            import torch
+            self._keep = torch.zeros((n_frames, stride), dtype=torch.uint8)
+            if torch.cuda.is_available():
+                self._keep = self._keep.pin_memory()
+            self.data = self._keep.numpy()
+
+    @property
+    def is_device(self):
+        return self.device_ptr is not None
+
+    def __len__(self):
+        return self.n_frames
+
+    def address(self, i=0):
+        """Address of frame i (host or device)."""
+        if not 0 <= i < self.n_frames:
+            raise IndexError(i)
+        return (self.device_ptr if self.is_device else self.data.ctypes.data) + i * self.frame_stride
+
+    def frame(self, i):
+        if self.is_device:
+            raise ValueError("a device sink has no host data")
+        return self.data[i]
 
 
 class CountingPipeline:
@@ -262,6 +313,57 @@ class CountingPipeline:
             if asynchronous and starts:
                 record(starts[-1], *self.engine.stream_collect()[:2])
         return self._finish(counter, obj, cam_name)
+
+    def visualizer(self, rows, zone_path):
+        """The MergedVisualizer of one video: the CSV rows that run* returned, read the way the reference reads its CSV back
+        (counting/utils.py:299-331: direction as an integer), and the zone file.  The reference colours a track from an unseeded
+        RNG (Q10); rows without a colour get `overlay.track_color`, a fixed function of (label, track id)."""
+        from .counting import load_zone_anno
+        from .overlay import MergedVisualizer, track_color
+        polygon, directions = load_zone_anno(zone_path)
+        fixed = []
+        for r in rows:
+            r = dict(r)
+            r["direction"] = int(r["direction"])
+            if not isinstance(r.get("color"), (tuple, list)) or len(r["color"]) != 3:
+                r["color"] = track_color(r["label"], r["track_id"])
+            fixed.append(r)
+        return MergedVisualizer(fixed, directions, polygon, len(self.class_names))
+
+    def render(self, source, rows, cam_name, zone_path, sink, batch=16, depth=2):
+        """The annotated video, the reference's VideoWriter.write_full_to_video (modules/datasets.py:132-145 -> visualize_merged,
+        counting/utils.py:299-331): a second pass over `source` (FrameSource or YuvFrameSource) that paints the overlay of the CSV
+        `rows` on the device and leaves every frame in `sink` (YuvFrameSink) as 4:2:0 YUV -- no frame exists as BGR on the host when
+        the source is YUV.  Frames go `batch` at a time through a Renderer: the primitive lists are built strictly in frame order
+        (the visualiser is stateful), batch n + 1 is submitted before batch n is collected.  Frame ids are 1-based.  Returns the sink."""
+        import torch
+
+        from .engine import Renderer
+        viz = self.visualizer(rows, zone_path)
+        yuv = isinstance(source, YuvFrameSource)
+        if yuv:
+            frames, t, h, w = source.data, len(source.data), source.h, source.w
+        else:
+            frames = source.frames
+            t, h, w, _ = frames.shape
+        if (sink.h, sink.w) != (h, w) or len(sink) < t:
+            raise ValueError(f"the sink holds {len(sink)} frames of {sink.h}x{sink.w}, the source has {t} of {h}x{w}")
+        # the source stays where the sink is: host frames cross PCIe batch by batch, a device sink gets the clip uploaded once
+        # (a decoder's surfaces in a real deployment)
+        keep = torch.from_numpy(frames)
+        keep = keep.to(f"cuda:{self.engine.cfg.device}") if sink.is_device else keep.pin_memory()
+        kind = ("yuv" if yuv else "bgr") + ("_dev" if sink.is_device else "_host")
+        with Renderer(self.engine, max_batch=batch, max_hw=(h, w), depth=depth) as rnd:
+            for f0 in range(0, t, batch):
+                b = min(batch, t - f0)
+                prims, first = viz.batch_prims(list(range(f0 + 1, f0 + b + 1)), (h, w))
+                if rnd.outstanding >= depth:
+                    rnd.collect()
+                rnd.submit(keep[f0:f0 + b].data_ptr(), b, h, w, sink.address(f0), kind=kind, src_desc=source.desc if yuv else None,
+                           prims=prims, first=first, out_desc=sink.desc, out_is_dev=sink.is_device)
+            while rnd.outstanding:
+                rnd.collect()
+        return sink
 
     def run_streams(self, sources, cam_names, zone_paths, batch=16):
         """S videos at once on ONE engine (the reference runs them one after another, each with a new VideoTracker,
