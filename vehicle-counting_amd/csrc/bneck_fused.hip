@@ -324,7 +324,7 @@ __global__ __launch_bounds__(BN_NW * 64) void bneck_fused_kernel(const BnArgs a)
     }
 }
 
-// pm1 = Bottleneck.cv1, pm2 = Bottleneck.cv2 as engine.hip::yolo_c3 builds them
+// pm1 = Bottleneck.cv1, pm2 = Bottleneck.cv2 as engine_plan.hip::yolo_c3 builds them
 bool bneck_fused_applicable(const ConvP& pm1, const ConvP& pm2) {
     if (!(pm1.prec == PREC_BF16 && pm1.kh == 1 && pm1.kw == 1 && pm1.sh == 1 && pm1.sw == 1 && pm1.ph == 0 && pm1.pw == 0 && pm1.Cin == 64 && pm1.Cout == 64 &&
           pm1.act == ACT_SILU && pm1.res_mode == RES_NONE && !pm1.out_f32 && pm1.split == 0))

@@ -1,6 +1,6 @@
 // YOLOv5's first C3 block in one kernel (bf16): C3(64 -> 64, n = 1, shortcut) at 160 x 160 for a 640 x 640 input -- models/common.py::C3 /
 // Bottleneck of ultralytics/yolov5 v6.0 (yolov5s.yaml layer 2 at width 0.5), reached from /root/reference/networks/yolo.py:70:
-//     y1 = SiLU(cv1 x)   y2 = SiLU(cv2 x)          1x1, 64 -> 32 each (one fused launch in the unfused graph: engine.hip::yolo_c3)
+//     y1 = SiLU(cv1 x)   y2 = SiLU(cv2 x)          1x1, 64 -> 32 each (one fused launch in the unfused graph: engine_plan.hip::yolo_c3)
 //     b1 = SiLU(m.cv1 y1)                           1x1, 32 -> 32
 //     m  = y1 + SiLU(m.cv2 b1)                      3x3 / pad 1, 32 -> 32, shortcut added after the activation
 //     out = SiLU(cv3 [m | y2])                      1x1, 64 -> 64
@@ -253,7 +253,7 @@ __global__ __launch_bounds__(C3_NW * 64, 2) void c3_fused_kernel(const C3Args a)
     }
 }
 
-// the four launches of engine.hip::yolo_c3 for n = 1 with a shortcut: cv1 | cv2 (one launch, two destinations), m.cv1, m.cv2, cv3
+// the four launches of engine_plan.hip::yolo_c3 for n = 1 with a shortcut: cv1 | cv2 (one launch, two destinations), m.cv1, m.cv2, cv3
 bool c3_fused_applicable(const ConvP& p12, const ConvP& pm1, const ConvP& pm2, const ConvP& p3) {
     auto pw = [](const ConvP& p, int cin, int cout) {
         return p.prec == PREC_BF16 && p.kh == 1 && p.kw == 1 && p.sh == 1 && p.sw == 1 && p.ph == 0 && p.pw == 0 && p.Cin == cin && p.Cout == cout &&

@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeLevel l0, const
 // Detect.m[i] is a 1x1 conv with 3 x (5 + nc) = 255 outputs per pixel, and non_max_suppression drops every anchor whose objectness is
 // not above conf_thres before it looks at anything else (utils/general.py: `xc = prediction[..., 4] > conf_thres`).  Dense, the three head
 // convs write 0.55 GB of logits per 128 frames at 640 x 640 that the decode reads the three objectness values of and throws away.  Sparse:
-// an 8-channel conv (the three objectness rows of Detect.m[i], engine.hip) over every pixel, this kernel picks the pixels where an
+// an 8-channel conv (the three objectness rows of Detect.m[i], engine_plan.hip) over every pixel, this kernel picks the pixels where an
 // anchor can pass -- the SAME float test as decode_kernel -- and gathers their feature vectors; the full 255-channel conv then runs on
 // the gathered rows only (conv_igemm_kernel with a device-side row count) and decode_sparse_kernel decodes those.  Same dot products in
 // the same order for every surviving anchor: the detections are identical to the dense path's.

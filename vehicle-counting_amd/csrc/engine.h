@@ -1,4 +1,4 @@
-// Engine internals shared between engine.hip (networks), tracker.hip (DeepSORT) and stream.hip (fused path).
+// Engine internals shared between engine.hip / engine_plan.hip / engine_run.hip (networks), tracker.hip (DeepSORT) and stream.hip (fused path).
 #pragma once
 #include <chrono>
 #include <condition_variable>
@@ -131,7 +131,7 @@ struct vc_engine {
     hipStream_t rstream = nullptr;   // ReID of the next batch (stream path), concurrent with detector and tracker
     hipStream_t hstream = nullptr;   // Detect-head ops of the P3 / P4 levels, beside the neck layers that follow them (Op::side)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    void* d_zero = nullptr; size_t zero_bytes = 0; bool want_hc_count = false;   // per-pass counters cleared by one memset (engine.hip)
+    void* d_zero = nullptr; size_t zero_bytes = 0; bool want_hc_count = false;   // per-pass counters cleared by one memset (engine_plan.hip)
     hipEvent_t ev_det[2] = {nullptr, nullptr};
     hipEvent_t ev_reid[3] = {nullptr, nullptr, nullptr};
     bool finalized = false;
@@ -145,7 +145,7 @@ struct vc_engine {
     vc::Net yolo;
     int ch[5] = {0, 0, 0, 0, 0}, rep[4] = {0, 0, 0, 0};
     std::map<std::string, vc::View> ybuf;        // named activation buffers (max shape)
-    vc::View layer_view[24];
+    const vc::YoloPlan* last_plan = nullptr;     // plan of the last detector pass (a node of yolo_plans): layer views for vc_detect_debug_layer
     std::vector<vc::ConvP> s2pw_folded;                          // stride-2 convs whose output the last pass kept on chip (conv3x3s2_halo_kernel<..., F2>)
     std::vector<std::pair<vc::View, vc::View>> up_folded;        // UPSAMPLE ops (source, destination) the last detector pass folded into their consumers
     std::map<std::vector<int>, vc::YoloPlan> yolo_plans;          // key: B, nh, nw, sparse head?
@@ -163,7 +163,6 @@ struct vc_engine {
     int* h_hc_ring = nullptr;                    // pinned [HC_RING][4]: the gathered-row counts of the last HC_RING detector passes (profiling)
     static constexpr int HC_RING = 16384;
     unsigned hc_ring_seq = 0; int hc_ring_cur = 0;
-    bool sparse_pass = false;                    // the pass being built / last run used the sparse head
     float anchors[3][6];                         // Detect anchors in pixels (default: the COCO set of yolov5{s,m,l}.yaml)
     vc::DetectPostBuffers post{};
     float* d_geom = nullptr;                     // [max_batch][5] gain, padw, padh, src_w, src_h
@@ -271,7 +270,7 @@ struct vc_engine {
     double prof_conv_union_ms = 0, prof_conv_span_ms = 0;     // set when the in-flight pairs are resolved (vc_profile_read)
     vc::ProfCat prof[VC_PROF_NCAT];
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::map<std::string, int> tuned;            // conv autotune cache: shape signature -> tile config (engine.hip::tune_key)
+    std::map<std::string, int> tuned;            // conv autotune cache: shape signature -> tile config (engine_run.hip::tune_key)
     bool tuned_dirty = false;
     std::string op_log;                          // per-launch lines "name M N K tile ms" while profiling
     double last_ms = 0;
@@ -287,10 +286,29 @@ namespace vc {
 int dev_alloc(vc_engine* e, void** p, size_t bytes);
 int dev_realloc(vc_engine* e, void** p, size_t bytes);            // frees *p (if it belongs to the engine) and allocates anew
 int host_alloc(vc_engine* e, void** p, size_t bytes);
+inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+// engine_plan.hip: the two networks and their op plans
+extern const float kAnchors[3][6];
+void yolo_define(vc_engine* e);
+int yolo_alloc(vc_engine* e);
+int yolo_build_ops(vc_engine* e, int B, int Hn, int Wn, bool sparse, YoloPlan& plan);
+void reid_define(vc_engine* e);
+int reid_alloc(vc_engine* e);
+int reid_build_ops(vc_engine* e, int k0, int k, ReidPlan& plan);
+int reid_cpad(int prec);                                          // channels of the ReID input buffer
+View mkview(const View& buf, int B, int H, int W, int C, int co);
+// engine_run.hip: running them
+void tune_cache_load(vc_engine* e);
+void tune_cache_save(vc_engine* e);
+void tune_cache_publish(vc_engine* e);
+void plans_retune(vc_engine* e);
+void autoshape_net_size(const int* h, const int* w, int n, int size, int& nh, int& nw);
+LetterboxGeom letterbox_geom(int h0, int w0, int nh, int nw, bool swap_rb);
+int yolo_forward(vc_engine* e, int B, int nh, int nw);
+int reid_forward(vc_engine* e, int k, hipStream_t rs, float* feat_out);
 int run_detector_dev(vc_engine* e, const uint8_t* d_frames, int B, int h, int w, bool swap_rb);   // frames same size, on device
 int run_reid_dev(vc_engine* e, const uint8_t* d_frames, int H, int W, int k);                      // crops in e->d_crops -> e->d_feat
 int run_reid_on(vc_engine* e, const uint8_t* d_frames, int H, int W, int k, const int* d_crops, float* feat_out, hipStream_t rs);
-int prof_launch(vc_engine* e, int cat, double flops, double bytes, int status);
 // stream.hip: the slot rules of vc_stream_stage_host (shared with the YUV staging calls): checks, creates the copy stream and the four
 // slots on first use, and hands out the next slot round-robin.  The caller enqueues its work on e->cstream, then calls ingest_publish.
 int ingest_take_slot(vc_engine* e, int b, int h, int w, int* slot);

@@ -1,11 +1,5 @@
-// Engine: owns the device, the stream, the detector (YOLOv5 v6.0 graph) and the ReID net, builds their
-// execution plans natively and exposes them through the C ABI in include/vcount_hip.h.
-//
-// Graph sources restated here (independently of oracle/yolov5.py, they only meet at the parameter names):
-//   ultralytics/yolov5 v6.0 models/yolov5{s,m,l}.yaml + models/common.py (Conv, Bottleneck, C3, SPPF, Concat) +
-//   models/yolo.py (Detect), loaded by /root/reference/networks/yolo.py:58;
-//   /root/reference/networks/deepsort/deep/model.py:5-98 (BasicBlock, make_layers, Net(reid=True)).
-// Concat never copies: producers write straight into channel slices of the consumer's buffer.
+// Engine: owns the device, the streams, the detector and the ReID net (engine_plan.hip defines them and builds their execution
+// plans, engine_run.hip runs them) and exposes them through the C ABI in include/vcount_hip.h.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -67,8 +61,6 @@ ProfScope::~ProfScope() {
 }
 
 // ------------------------------------------------------------------------------------------------ weights
-static int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
 static int pack_and_upload(vc_engine* e, ConvParam& p, int prec, float act_scale = 1.0f) {
     VC_CHECK(p.set, VC_ERR_STATE, "parameter '%s' was never set", p.name.c_str());
     p.prec = prec;
@@ -125,868 +117,6 @@ static int pack_and_upload(vc_engine* e, ConvParam& p, int prec, float act_scale
     }
     VC_HIP(hipMemcpy(p.d_b, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
     return VC_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ plan helpers
-static View mkview(const View& buf, int B, int H, int W, int C, int co) {
-    View v = buf;
-    v.B = B; v.H = H; v.W = W; v.C = C; v.co = buf.co + co;
-    return v;
-}
-
-static int alloc_buf(vc_engine* e, std::map<std::string, View>& m, const std::string& name, size_t pixels, int C, int es) {
-    View v{};
-    v.cs = C; v.co = 0; v.C = C; v.es = es;
-    VC_TRY(dev_alloc(e, &v.ptr, pixels * C * es));
-    m[name] = v;
-    return VC_OK;
-}
-
-struct PlanBuilder {
-    vc_engine* e;
-    Net* net;
-    std::vector<Op>* ops;
-    int prec;
-    int status = VC_OK;
-
-    // out.H/W are filled from the conv arithmetic; returns the output view with its dims set
-    View conv(const std::string& pname, View in, View out, int k, int s, int p, int act, const View* res = nullptr,
-              int res_mode = RES_NONE, bool out_f32 = false) {
-        auto it = net->index.find(pname);
-        if (it == net->index.end()) { set_error("plan: unknown parameter %s", pname.c_str()); status = VC_ERR_NOTFOUND; return out; }
-        const ConvParam& cp = net->params[it->second];
-        Op op{};
-        op.kind = Op::CONV;
-        op.param = it->second;
-        ConvP& c = op.conv;
-        c.in = in.ptr; c.w = cp.d_w; c.bias = cp.d_b; c.out = out.ptr;
-        c.B = in.B;
-        if (cp.pair_stem) {
-            c.H = in.H; c.W = in.W / 2; c.Cin = 8; c.in_cs = 8; c.in_co = 0;
-            c.kh = cp.kh; c.kw = cp.kw / 2; c.sh = s; c.sw = 1; c.ph = p; c.pw = 1;
-            c.Ho = (in.H + 2 * p - k) / s + 1; c.Wo = (in.W + 2 * p - k) / s + 1;
-        } else {
-            c.H = in.H; c.W = in.W; c.Cin = cp.cin_eff; c.in_cs = in.cs; c.in_co = in.co;
-            c.kh = k; c.kw = k; c.sh = s; c.sw = s; c.ph = p; c.pw = p;
-            c.Ho = (in.H + 2 * p - k) / s + 1; c.Wo = (in.W + 2 * p - k) / s + 1;
-        }
-        c.Cout = cp.O; c.out_cs = out.cs; c.out_co = out.co;
-        c.K = cp.K; c.Kp = cp.Kp;
-        c.act = act; c.res_mode = res_mode; c.out_f32 = out_f32 ? 1 : 0; c.prec = cp.prec;
-        c.scale = cp.d_scale; c.act_scale = e->act_scale; c.inv_act_scale = 1.0f / e->act_scale; c.out_bf16 = 0;
-        if (res) { c.res = res->ptr; c.res_cs = res->cs; c.res_co = res->co; }
-        c.M = c.B * c.Ho * c.Wo;
-        c.cfg = -1;
-        op.C = cp.I * cp.kh * cp.kw;          // logical K for algorithmic FLOPs
-        ops->push_back(op);
-        out.B = in.B; out.H = c.Ho; out.W = c.Wo; out.C = cp.O;
-        return out;
-    }
-};
-
-// ------------------------------------------------------------------------------------------------ YOLOv5 v6.0
-static const double kYoloMult[3][2] = {{0.33, 0.50}, {0.67, 0.75}, {1.0, 1.0}};   // depth, width (s, m, l)
-static const float kAnchors[3][6] = {{10, 13, 16, 30, 33, 23}, {30, 61, 62, 45, 59, 119}, {116, 90, 156, 198, 373, 326}};
-
-static void yolo_c3_params(Net& n, int idx, int cin, int cout, int reps) {
-    const std::string p = "model." + std::to_string(idx);
-    const int h = cout / 2;
-    const int a = n.add(p + ".cv1.conv", h, cin, 1, 1);
-    const int b = n.add(p + ".cv2.conv", h, cin, 1, 1);
-    n.add(p + ".cv3.conv", cout, 2 * h, 1, 1);
-    const int f = n.add(p + ".cv12", 2 * h, cin, 1, 1);        // cv1 and cv2 read the same input: one launch, two destinations
-    n.params[f].fuse_a = a; n.params[f].fuse_b = b; n.params[f].hidden = true;
-    for (int j = 0; j < reps; ++j) {
-        n.add(p + ".m." + std::to_string(j) + ".cv1.conv", h, h, 1, 1);
-        n.add(p + ".m." + std::to_string(j) + ".cv2.conv", h, h, 3, 3);
-    }
-}
-
-static void yolo_define(vc_engine* e) {
-    const double gd = kYoloMult[e->cfg.yolo_variant][0], gw = kYoloMult[e->cfg.yolo_variant][1];
-    const int base[5] = {64, 128, 256, 512, 1024};
-    for (int i = 0; i < 5; ++i) e->ch[i] = (int)std::ceil(base[i] * gw / 8.0) * 8;
-    const int r[4] = {3, 6, 9, 3};
-    for (int i = 0; i < 4; ++i) e->rep[i] = std::max((int)std::nearbyint(r[i] * gd), 1);
-    Net& n = e->yolo;
-    const int* c = e->ch;
-    n.add("model.0.conv", c[0], 3, 6, 6);
-    n.params.back().pair_stem = (e->aux_prec == PREC_BF16);       // the stem stays bf16 in the fp8 mode
-    n.add("model.1.conv", c[1], c[0], 3, 3); yolo_c3_params(n, 2, c[1], c[1], e->rep[0]);
-    n.add("model.3.conv", c[2], c[1], 3, 3); yolo_c3_params(n, 4, c[2], c[2], e->rep[1]);
-    n.add("model.5.conv", c[3], c[2], 3, 3); yolo_c3_params(n, 6, c[3], c[3], e->rep[2]);
-    n.add("model.7.conv", c[4], c[3], 3, 3); yolo_c3_params(n, 8, c[4], c[4], e->rep[3]);
-    n.add("model.9.cv1.conv", c[4] / 2, c[4], 1, 1);
-    n.add("model.9.cv2.conv", c[4], c[4] * 2, 1, 1);
-    n.add("model.10.conv", c[3], c[4], 1, 1); yolo_c3_params(n, 13, 2 * c[3], c[3], e->rep[0]);
-    n.add("model.14.conv", c[2], c[3], 1, 1); yolo_c3_params(n, 17, 2 * c[2], c[2], e->rep[0]);
-    n.add("model.18.conv", c[2], c[2], 3, 3); yolo_c3_params(n, 20, 2 * c[2], c[3], e->rep[0]);
-    n.add("model.21.conv", c[3], c[3], 3, 3); yolo_c3_params(n, 23, 2 * c[3], c[4], e->rep[0]);
-    const int no = 3 * (e->cfg.num_classes + 5);
-    for (int i = 0; i < 3; ++i) {
-        const int h = n.add("model.24.m." + std::to_string(i), no, c[2 + i], 1, 1);
-        const int o = n.add("model.24.m." + std::to_string(i) + ".obj", 8, c[2 + i], 1, 1);      // sparse head: the three objectness rows, padded to 8
-        n.params[o].obj_of = h; n.params[o].hidden = true;
-    }
-}
-
-static int yolo_alloc(vc_engine* e) {
-    const int es = elem_size(e->prec), aes = elem_size(e->aux_prec);
-    const int S = round_up(e->cfg.img_size, 32);
-    const size_t B = e->cfg.max_batch;
-    auto px = [&](int stride) { return B * (size_t)(S / stride) * (S / stride); };
-    const int* c = e->ch;
-    auto& m = e->ybuf;
-    auto c3 = [&](int idx, int stride, int cout) -> int {
-        const std::string p = "c3_" + std::to_string(idx);
-        const int h = cout / 2;
-        VC_TRY(alloc_buf(e, m, p + ".a", px(stride), h, es));
-        VC_TRY(alloc_buf(e, m, p + ".b", px(stride), h, es));
-        VC_TRY(alloc_buf(e, m, p + ".t", px(stride), h, es));
-        VC_TRY(alloc_buf(e, m, p + ".cat", px(stride), 2 * h, es));
-        return VC_OK;
-    };
-    VC_TRY(alloc_buf(e, m, "in", px(1), 4, aes));
-    VC_TRY(alloc_buf(e, m, "l0", px(2), c[0], aes));
-    if (e->prec == PREC_FP8) VC_TRY(alloc_buf(e, m, "l0q", px(2), c[0], es));       // the bf16 stem output converted to fp8
-    VC_TRY(alloc_buf(e, m, "l1", px(4), c[1], es)); VC_TRY(c3(2, 4, c[1])); VC_TRY(alloc_buf(e, m, "l2", px(4), c[1], es));
-    VC_TRY(alloc_buf(e, m, "l3", px(8), c[2], es)); VC_TRY(c3(4, 8, c[2])); VC_TRY(alloc_buf(e, m, "cat16", px(8), 2 * c[2], es));
-    VC_TRY(alloc_buf(e, m, "l5", px(16), c[3], es)); VC_TRY(c3(6, 16, c[3])); VC_TRY(alloc_buf(e, m, "cat12", px(16), 2 * c[3], es));
-    VC_TRY(alloc_buf(e, m, "l7", px(32), c[4], es)); VC_TRY(c3(8, 32, c[4])); VC_TRY(alloc_buf(e, m, "l8", px(32), c[4], es));
-    VC_TRY(alloc_buf(e, m, "sppcat", px(32), 2 * c[4], es));
-    VC_TRY(alloc_buf(e, m, "l9", px(32), c[4], es));
-    VC_TRY(alloc_buf(e, m, "cat22", px(32), 2 * c[3], es));
-    VC_TRY(c3(13, 16, c[3])); VC_TRY(alloc_buf(e, m, "l13", px(16), c[3], es));
-    VC_TRY(alloc_buf(e, m, "cat19", px(16), 2 * c[2], es));
-    VC_TRY(c3(17, 8, c[2])); VC_TRY(alloc_buf(e, m, "l17", px(8), c[2], es));
-    VC_TRY(c3(20, 16, c[3])); VC_TRY(alloc_buf(e, m, "l20", px(16), c[3], es));
-    VC_TRY(c3(23, 32, c[4])); VC_TRY(alloc_buf(e, m, "l23", px(32), c[4], es));
-    const int no = 3 * (e->cfg.num_classes + 5);
-    const int lcs = round_up(no, 8);
-    const int strides[3] = {8, 16, 32};
-    for (int i = 0; i < 3; ++i) VC_TRY(dev_alloc(e, (void**)&e->d_logits[i], px(strides[i]) * lcs * sizeof(float)));
-    if (e->prec == PREC_BF16) {
-        // sparse head: per level an 8-channel objectness plane and room for EVERY pixel of the batch in the gathered list (a
-        // pooled B x max_candidates capacity could overflow on one busy frame where the dense head, which only counts anchors with
-        // obj x cls > conf against max_candidates per frame, succeeds; 0.6 GB at B = 128 / 640 x 640 of 288 GB buys "cannot overflow")
-        for (int i = 0; i < 3; ++i) {
-            const size_t ppf = (size_t)(S / strides[i]) * (S / strides[i]);
-            e->hc_cap[i] = (int)(B * ppf);
-            VC_TRY(dev_alloc(e, &e->d_obj[i], px(strides[i]) * 8 * 2));
-            VC_TRY(dev_alloc(e, (void**)&e->d_hc_list[i], (size_t)e->hc_cap[i] * sizeof(int)));
-            VC_TRY(dev_alloc(e, &e->d_hc_x[i], (size_t)e->hc_cap[i] * c[2 + i] * 2));
-            VC_TRY(dev_alloc(e, &e->d_hc_logits[i], (size_t)e->hc_cap[i] * lcs * 2));
-        }
-        e->want_hc_count = true;                            // carved out of the zero block below (one memset per pass clears all three)
-        VC_TRY(host_alloc(e, (void**)&e->h_hc_ring, (size_t)vc_engine::HC_RING * 4 * sizeof(int)));
-        memset(e->h_hc_ring, 0, (size_t)vc_engine::HC_RING * 4 * sizeof(int));
-    }
-    // post-processing
-    const size_t mc = e->cfg.max_candidates, md = e->cfg.max_det;
-    auto& pb = e->post;
-    VC_TRY(dev_alloc(e, (void**)&pb.cand_box, B * mc * 4 * sizeof(float)));
-    VC_TRY(dev_alloc(e, (void**)&pb.cand_conf, B * mc * sizeof(float)));
-    VC_TRY(dev_alloc(e, (void**)&pb.cand_cls, B * mc * sizeof(int)));
-    VC_TRY(dev_alloc(e, (void**)&pb.cand_idx, B * mc * sizeof(int)));
-    // per-pass counters in ONE block: [sparse-head row counts, 64 B][cand_count][overflow] -- a single memset at the head of the detector's
-    // chain of dependent launches instead of three
-    e->zero_bytes = 64 + 2 * B * sizeof(int);
-    VC_TRY(dev_alloc(e, (void**)&e->d_zero, e->zero_bytes));
-    if (e->want_hc_count) e->d_hc_count = (int*)e->d_zero;
-    pb.cand_count = (int*)((char*)e->d_zero + 64);
-    VC_TRY(dev_alloc(e, (void**)&pb.sort_box, B * mc * 4 * sizeof(float)));
-    VC_TRY(dev_alloc(e, (void**)&pb.sort_conf, B * mc * sizeof(float)));
-    VC_TRY(dev_alloc(e, (void**)&pb.sort_cls, B * mc * sizeof(int)));
-    VC_TRY(dev_alloc(e, (void**)&pb.mask, B * mc * (mc / 64) * sizeof(unsigned long long)));
-    VC_TRY(dev_alloc(e, (void**)&pb.det, B * md * 6 * sizeof(float)));
-    VC_TRY(dev_alloc(e, (void**)&pb.det_count, B * sizeof(int)));
-    pb.overflow = pb.cand_count + B;
-    VC_TRY(dev_alloc(e, (void**)&e->d_geom, B * 5 * sizeof(float)));
-    VC_TRY(host_alloc(e, (void**)&e->h_geom, 2 * B * 5 * sizeof(float)));
-    for (int k = 0; k < 2; ++k) {
-        VC_TRY(host_alloc(e, (void**)&e->h_det2[k], B * md * 6 * sizeof(float)));
-        VC_TRY(host_alloc(e, (void**)&e->h_det_count2[k], B * sizeof(int)));
-    }
-    VC_TRY(host_alloc(e, (void**)&e->h_det, B * md * 6 * sizeof(float)));
-    VC_TRY(host_alloc(e, (void**)&e->h_det_count, B * sizeof(int)));
-    return VC_OK;
-}
-
-// C3(c1 -> c2, n x Bottleneck(e=1.0, shortcut), cv3 over concat(m(cv1 x), cv2 x)); models/common.py::C3
-static View yolo_c3(PlanBuilder& pb, vc_engine* e, int idx, View x, View out, int cout, int reps, bool shortcut) {
-    const std::string p = "model." + std::to_string(idx), bn = "c3_" + std::to_string(idx);
-    const int h = cout / 2;
-    auto& m = e->ybuf;
-    View cat = mkview(m[bn + ".cat"], x.B, x.H, x.W, 2 * h, 0);
-    View y = pb.conv(p + ".cv12", x, mkview(m[bn + ".a"], x.B, x.H, x.W, h, 0), 1, 1, 0, ACT_SILU);
-    {   // channels [h, 2h) of the fused launch are C3.cv2 -> second half of the concat buffer
-        ConvP& c = pb.ops->back().conv;
-        View second = mkview(cat, x.B, x.H, x.W, h, h);
-        c.out2 = second.ptr; c.out2_cs = second.cs; c.out2_co = second.co; c.split = h;
-    }
-    y.C = h;
-    for (int j = 0; j < reps; ++j) {
-        View t = pb.conv(p + ".m." + std::to_string(j) + ".cv1.conv", y, mkview(m[bn + ".t"], x.B, x.H, x.W, h, 0), 1, 1, 0, ACT_SILU);
-        View dst = j == reps - 1 ? mkview(cat, x.B, x.H, x.W, h, 0) : mkview(m[bn + ((j % 2 == 0) ? ".b" : ".a")], x.B, x.H, x.W, h, 0);
-        y = pb.conv(p + ".m." + std::to_string(j) + ".cv2.conv", t, dst, 3, 1, 1, ACT_SILU, shortcut ? &y : nullptr,
-                    shortcut ? RES_AFTER_ACT : RES_NONE);
-    }
-    return pb.conv(p + ".cv3.conv", cat, out, 1, 1, 0, ACT_SILU);
-}
-
-static int yolo_build_ops(vc_engine* e, int B, int Hn, int Wn, std::vector<Op>& ops) {
-    PlanBuilder pb{e, &e->yolo, &ops, e->prec};
-    auto& m = e->ybuf;
-    const int* c = e->ch;
-    auto full = [&](const char* name, int stride, int C) { return mkview(m[name], B, Hn / stride, Wn / stride, C, 0); };
-    View* lv = e->layer_view;
-    View x = full("in", 1, 4);
-    lv[0] = x = pb.conv("model.0.conv", x, full("l0", 2, c[0]), 6, 2, 2, ACT_SILU);
-    if (e->prec == PREC_FP8) {             // 3-channel stem in bf16 (K = 108), its output quantised once for the fp8 layers
-        Op op{}; op.kind = Op::TO_FP8; op.a = x; op.b = full("l0q", 2, c[0]); op.b.B = x.B; op.b.H = x.H; op.b.W = x.W; ops.push_back(op);
-        x = op.b;
-    }
-    lv[1] = x = pb.conv("model.1.conv", x, full("l1", 4, c[1]), 3, 2, 1, ACT_SILU);
-    lv[2] = x = yolo_c3(pb, e, 2, x, full("l2", 4, c[1]), c[1], e->rep[0], true);
-    lv[3] = x = pb.conv("model.3.conv", x, full("l3", 8, c[2]), 3, 2, 1, ACT_SILU);
-    if (pb.status == VC_OK) ops.back().sole_reader_next = 1;      // "l3" is read by C3.cv1 | cv2 of layer 4 (the next op) and by nothing else
-    View cat16 = full("cat16", 8, 2 * c[2]);
-    lv[4] = x = yolo_c3(pb, e, 4, x, mkview(cat16, B, Hn / 8, Wn / 8, c[2], c[2]), c[2], e->rep[1], true);
-    lv[5] = x = pb.conv("model.5.conv", x, full("l5", 16, c[3]), 3, 2, 1, ACT_SILU);
-    if (pb.status == VC_OK) ops.back().sole_reader_next = 1;
-    View cat12 = full("cat12", 16, 2 * c[3]);
-    lv[6] = x = yolo_c3(pb, e, 6, x, mkview(cat12, B, Hn / 16, Wn / 16, c[3], c[3]), c[3], e->rep[2], true);
-    lv[7] = x = pb.conv("model.7.conv", x, full("l7", 32, c[4]), 3, 2, 1, ACT_SILU);
-    if (pb.status == VC_OK) ops.back().sole_reader_next = 1;
-    lv[8] = x = yolo_c3(pb, e, 8, x, full("l8", 32, c[4]), c[4], e->rep[3], true);
-    {   // SPPF (models/common.py::SPPF, k=5)
-        View sc = full("sppcat", 32, 2 * c[4]);
-        pb.conv("model.9.cv1.conv", x, mkview(sc, B, Hn / 32, Wn / 32, c[4] / 2, 0), 1, 1, 0, ACT_SILU);
-        Op op{}; op.kind = Op::SPPF; op.a = sc; op.C = c[4] / 2; ops.push_back(op);
-        lv[9] = x = pb.conv("model.9.cv2.conv", sc, full("l9", 32, c[4]), 1, 1, 0, ACT_SILU);
-    }
-    View cat22 = full("cat22", 32, 2 * c[3]);
-    lv[10] = x = pb.conv("model.10.conv", x, mkview(cat22, B, Hn / 32, Wn / 32, c[3], c[3]), 1, 1, 0, ACT_SILU);
-    { Op op{}; op.kind = Op::UPSAMPLE; op.a = x; op.b = mkview(cat12, B, Hn / 16, Wn / 16, c[3], 0); ops.push_back(op); lv[11] = op.b; }
-    lv[12] = cat12;
-    lv[13] = x = yolo_c3(pb, e, 13, cat12, full("l13", 16, c[3]), c[3], e->rep[0], false);
-    View cat19 = full("cat19", 16, 2 * c[2]);
-    lv[14] = x = pb.conv("model.14.conv", x, mkview(cat19, B, Hn / 16, Wn / 16, c[2], c[2]), 1, 1, 0, ACT_SILU);
-    { Op op{}; op.kind = Op::UPSAMPLE; op.a = x; op.b = mkview(cat16, B, Hn / 8, Wn / 8, c[2], 0); ops.push_back(op); lv[15] = op.b; }
-    lv[16] = cat16;
-    // Detect.m[i]: 1x1 conv + bias (models/yolo.py::Detect).  fp32 mode: fp32 logits.  bf16 mode: bf16 logits like every other
-    // activation, and the launch covers round_up(no, 8) output channels (the packed weight / bias rows past `no` are zero) so
-    // that the 255-channel head takes the 16-byte-store epilogue; FLOPs are still counted for `no` channels (Op::cout_logical).
-    const int no = 3 * (e->cfg.num_classes + 5), lcs = round_up(no, 8);
-    e->sparse_pass = e->prec == PREC_BF16 && e->opt.sparse_head && !e->want_pred_debug && e->d_hc_count;
-    // sparse Detect head (detect_post.hip): objectness conv over every pixel -> gather the pixels that can pass conf_thres -> the
-    // full head on the gathered rows (row count on the device).  The work reported is what RUNS (the gathered rows); the dense
-    // head's figures travel beside it as dense_* (round 3 credited the launch with the dense head's work: a 6 us launch showed
-    // 3.4 x the chip's peak in the per-layer table).  The ops of level i follow the layer that produces its map: P3's and P4's are
-    // marked Op::side and run on the head stream beside layers 18 - 23 (three short dependent launches per level, 0.11 ms of
-    // objectness conv alone at 80^2, that used to sit at the END of the detector's chain of ~63 dependent launches).
-    auto sparse_head = [&](int i, const View& x) {
-        if (!e->sparse_pass || pb.status != VC_OK) return;
-        const size_t first = ops.size();
-        const std::string hp = "model.24.m." + std::to_string(i);
-        const double es = 2.0, Mh = (double)x.B * x.H * x.W;
-        View ov{}; ov.ptr = e->d_obj[i]; ov.cs = 8; ov.co = 0;
-        pb.conv(hp + ".obj", x, ov, 1, 1, 0, ACT_NONE);
-        if (pb.status != VC_OK) return;
-        ops.back().flops_override = 2.0 * Mh * 3 * x.C;                                    // the three objectness rows (the launch covers 8 zero-padded channels)
-        ops.back().bytes_override = (Mh * x.C + 8.0 * x.C) * es + Mh * 8 * es;
-        ops.back().dense_flops = 0; ops.back().dense_bytes = 0;                            // the dense head has no such launch: its work is on the head conv below
-        { Op op{}; op.kind = Op::HEAD_COMPACT; op.level = i; op.a = x; ops.push_back(op); }
-        View gx{}; gx.ptr = e->d_hc_x[i]; gx.B = 1; gx.H = 1; gx.W = e->hc_cap[i]; gx.C = x.C; gx.cs = x.C; gx.co = 0;
-        View go{}; go.ptr = e->d_hc_logits[i]; go.cs = lcs; go.co = 0;
-        pb.conv(hp, gx, go, 1, 1, 0, ACT_NONE);
-        if (pb.status != VC_OK) return;
-        Op& hop = ops.back();
-        hop.cout_logical = hop.conv.Cout; hop.conv.Cout = lcs;
-        hop.conv.m_dev = e->d_hc_count + i;
-        // executed: the head on the gathered rows only (row count on the device, read back after the pass)
-        hop.rows_level = i;
-        hop.flops_override = 0; hop.bytes_override = (double)no * x.C * es;                // weights
-        hop.flops_per_row = 2.0 * no * x.C; hop.bytes_per_row = (x.C + (double)lcs) * es;  // one gathered feature row in, one logit row out
-        hop.dense_flops = 2.0 * Mh * no * x.C;
-        hop.dense_bytes = (Mh * x.C + (double)no * x.C) * es + Mh * lcs * es;              // the dense head's in + weights + out
-        if (i < 2) for (size_t j = first; j < ops.size(); ++j) ops[j].side = 1;
-    };
-    View p3 = lv[17] = yolo_c3(pb, e, 17, cat16, full("l17", 8, c[2]), c[2], e->rep[0], false);
-    sparse_head(0, p3);
-    lv[18] = pb.conv("model.18.conv", p3, mkview(cat19, B, Hn / 16, Wn / 16, c[2], 0), 3, 2, 1, ACT_SILU);
-    lv[19] = cat19;
-    View p4 = lv[20] = yolo_c3(pb, e, 20, cat19, full("l20", 16, c[3]), c[3], e->rep[0], false);
-    sparse_head(1, p4);
-    lv[21] = pb.conv("model.21.conv", p4, mkview(cat22, B, Hn / 32, Wn / 32, c[3], 0), 3, 2, 1, ACT_SILU);
-    lv[22] = cat22;
-    View p5 = lv[23] = yolo_c3(pb, e, 23, cat22, full("l23", 32, c[4]), c[4], e->rep[0], false);
-    sparse_head(2, p5);
-    const View heads[3] = {p3, p4, p5};
-    for (int i = 0; i < 3 && !e->sparse_pass; ++i) {
-        View o{}; o.ptr = e->d_logits[i]; o.cs = lcs; o.co = 0;
-        const bool wide = e->prec == PREC_F32;
-        pb.conv("model.24.m." + std::to_string(i), heads[i], o, 1, 1, 0, ACT_NONE, nullptr, RES_NONE, wide);
-        if (!wide && pb.status == VC_OK) { Op& op = ops.back(); op.cout_logical = op.conv.Cout; op.conv.Cout = lcs; }
-        if (e->prec == PREC_FP8 && pb.status == VC_OK) ops.back().conv.out_bf16 = 1;        // logits leave the fp8 domain as bf16
-    }
-    return pb.status;
-}
-
-// Pick the fastest tile configuration for a conv launch by timing every candidate once per (layer shape, problem-size
-// bucket).  Results are identical across the implicit-GEMM configurations (same K order, fp32 accumulate); the halo-staged 3x3
-// variants sum the K tiles slice-major and can differ from them in the last bf16 bit of a few values.
-// VC_TUNE_CACHE=<file> persists the choices across processes (used for clean rocprofv3 passes: a first run writes the file, the
-// profiled run reads it and launches no tuning candidates; also what makes a bf16 engine bit-reproducible across processes).
-// Within a process the choices are shared by all engines of a device (g_tuned): a second engine neither re-times the candidates
-// nor picks the other member of a near-tie, so two engines of one process agree bit for bit.
-static std::string tune_key(const ConvP& c) {
-    int bucket = 1;
-    while (bucket < c.M) bucket <<= 1;
-    char k[160];
-    snprintf(k, sizeof(k), "p%d_ci%d_co%d_k%dx%d_s%d_h%d_w%d_K%d_m%d_sp%d%s", c.prec, c.Cin, c.Cout, c.kh, c.kw, c.sh, c.H, c.W, c.K, bucket, c.split,
-             c.in_up ? "_up" : "");      // (the upsample fold-in runs on a subset of the tile configurations)
-    return k;
-}
-
-static std::mutex g_tune_mu;
-static std::map<std::string, int> g_tuned;          // "d<device>_<tune_key>" -> tile configuration
-
-static void tune_cache_load(vc_engine* e) {
-    const char* path = getenv("VC_TUNE_CACHE");
-    if (!path) return;
-    FILE* f = fopen(path, "r");
-    if (!f) return;
-    char k[200];
-    int cfg;
-    while (fscanf(f, "%199s %d", k, &cfg) == 2) e->tuned[k] = cfg;
-    fclose(f);
-}
-
-static void tune_cache_save(vc_engine* e) {
-    const char* path = getenv("VC_TUNE_CACHE");
-    if (!path || !e->tuned_dirty) return;
-    FILE* f = fopen(path, "w");
-    if (!f) return;
-    for (const auto& kv : e->tuned) fprintf(f, "%s %d\n", kv.first.c_str(), kv.second);
-    fclose(f);
-}
-
-static int tuned_cfg(vc_engine* e, const ConvP& c, hipStream_t s) {
-    static const bool enabled = !(getenv("VC_AUTOTUNE") && atoi(getenv("VC_AUTOTUNE")) == 0);
-    if (!enabled) return -1;
-    const std::string key = tune_key(c);
-    auto it = e->tuned.find(key);
-    if (it != e->tuned.end()) return it->second;
-    const std::string gkey = "d" + std::to_string(e->cfg.device) + "_" + key;
-    {
-        std::lock_guard<std::mutex> lk(g_tune_mu);
-        auto g = g_tuned.find(gkey);
-        if (g != g_tuned.end()) { e->tuned[key] = g->second; e->tuned_dirty = true; return g->second; }
-    }
-    int best = -1;
-    float best_ms = 1e30f;
-    static const bool stream_on = getenv("VC_CONV_STREAM") && atoi(getenv("VC_CONV_STREAM")) != 0;   // conv1x1_stream_kernel: wins alone, loses beside the ReID queue (conv_igemm.hip)
-    for (int cfg = 0; cfg < conv_num_cfgs(); ++cfg) {
-        if (conv_stream_cfg(cfg) && !stream_on) continue;
-        if (launch_conv_cfg(c, cfg, s) != VC_OK) continue;          // warm-up (instruction cache, L2)
-        float tmin = 1e30f;
-        for (int rep = 0; rep < 3; ++rep) {
-            hipEventRecord(e->ev0, s);
-            launch_conv_cfg(c, cfg, s);
-            hipEventRecord(e->ev1, s);
-            hipEventSynchronize(e->ev1);
-            float ms = 0.f;
-            hipEventElapsedTime(&ms, e->ev0, e->ev1);
-            tmin = std::min(tmin, ms);
-        }
-        static const bool tlog = getenv("VC_TUNE_LOG") != nullptr;      // diagnostics: every candidate's time
-        if (tlog) fprintf(stderr, "[vc tune] %s cfg %d %.4f ms\n", key.c_str(), cfg, tmin);
-        if (tmin < best_ms) { best_ms = tmin; best = cfg; }
-    }
-    e->tuned[key] = best;
-    e->tuned_dirty = true;
-    {
-        std::lock_guard<std::mutex> lk(g_tune_mu);
-        g_tuned.emplace(gkey, best);
-    }
-    return best;
-}
-
-// in-flight profiling of one conv launch (see vc_engine::prof_async): the launch itself reports its start / stop timestamps
-// into an event pair (hipExtLaunchKernel), no host wait
-static void conv_timer_arm(vc_engine* e, ConvP& cp, double flops, double bytes, const Op& op) {
-    if (!e->prof_async || e->profiling || e->prof_used >= e->prof_pairs.size()) return;
-    vc_engine::ProfPair& pp = e->prof_pairs[e->prof_used++];
-    pp.flops = flops; pp.bytes = bytes;
-    pp.rows = op.rows_level >= 0 && e->h_hc_ring ? e->h_hc_ring + (size_t)e->hc_ring_cur * 4 + op.rows_level : nullptr;
-    pp.flops_per_row = op.flops_per_row; pp.bytes_per_row = op.bytes_per_row;
-    pp.flops_dense = op.dense_flops >= 0 ? op.dense_flops : -1; pp.bytes_dense = op.dense_bytes >= 0 ? op.dense_bytes : -1;   // -1: same as executed
-    cp.ev_start = pp.a; cp.ev_stop = pp.b;
-}
-
-static int run_ops_body(vc_engine* e, std::vector<Op>& ops, int aux_cat, hipStream_t s_main, bool& side_used);
-// *side_used (nullable) = the ops forked onto the head stream.  The join (head stream -> main stream) is recorded HERE, on the error path too:
-// a pass that failed after the fork must not leave head ops running beside the next pass's memset of the counters they write.
-static int run_ops(vc_engine* e, std::vector<Op>& ops, int aux_cat, hipStream_t s_main, bool* side_used = nullptr) {
-    bool forked = false;
-    const int st = run_ops_body(e, ops, aux_cat, s_main, forked);
-    if (forked) {                                            // the P3 / P4 head ops ran on the head stream: whatever follows on the main stream waits for them
-        const hipError_t e1 = hipEventRecord(e->ev_join, e->hstream);
-        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(s_main, e->ev_join, 0) : e1;
-        if (st == VC_OK && e2 != hipSuccess) { set_error("head stream join failed: %s", hipGetErrorString(e2)); return VC_ERR_HIP; }
-    }
-    if (side_used) *side_used = forked;
-    return st;
-}
-static int run_ops_body(vc_engine* e, std::vector<Op>& ops, int aux_cat, hipStream_t s_main, bool& side_used) {
-    // Op::side ops go to the head stream (detector passes only; not while every launch is bracketed by blocking events): the first of a run
-    // of them waits for everything the main stream has been given so far, the caller joins the head stream before it reads their results
-    const bool side_ok = s_main == e->dstream && e->hstream && e->opt.head_side && !e->profiling;
-    bool prev_side = false;
-    const Op* pending_up = nullptr;          // an UPSAMPLE op whose consumer (the next op) reads the half-size map itself
-    for (size_t oi = 0; oi < ops.size(); ++oi) {
-        Op& op = ops[oi];
-        const bool on_side = side_ok && op.side;
-        if (on_side && !prev_side) {
-            VC_HIP(hipEventRecord(e->ev_fork, s_main));
-            VC_HIP(hipStreamWaitEvent(e->hstream, e->ev_fork, 0));
-            side_used = true;
-        }
-        prev_side = on_side;
-        hipStream_t s = on_side ? e->hstream : s_main;
-        switch (op.kind) {
-            case Op::CONV: {
-                const double es = elem_size(op.conv.prec);
-                const double fl = op.flops_override >= 0 ? op.flops_override : 2.0 * op.conv.M * (double)(op.cout_logical ? op.cout_logical : op.conv.Cout) * op.C;
-                double by = op.bytes_override >= 0 ? op.bytes_override
-                                                   : ((double)op.conv.B * op.conv.H * op.conv.W * op.conv.Cin + (double)op.conv.Cout * op.conv.K) * es +
-                                                         (double)op.conv.M * op.conv.Cout * (op.conv.out_f32 ? 4 : es);
-                if (pending_up) by -= 0.75 * (double)op.conv.M * pending_up->a.C * es;   // (folded upsample: three quarters of that half of the input are never read)
-                ConvP cp = op.conv;
-                if (pending_up) {                                             // Upsample + Concat folded into this pointwise conv (conv_igemm_kernel<..., UP>)
-                    const View& u = pending_up->a;
-                    cp.in_up = u.ptr; cp.up_C = u.C; cp.up_cs = u.cs; cp.up_co = u.co;
-                    pending_up = nullptr;
-                }
-                double fl_exec = -1;                                          // executed FLOPs when they differ from `fl` (device-side row count)
-                static const bool stem_direct_on = !(getenv("VC_STEM_DIRECT") && atoi(getenv("VC_STEM_DIRECT")) == 0);
-                static const bool reid_stem_on = !(getenv("VC_REID_STEM_FUSED") && atoi(getenv("VC_REID_STEM_FUSED")) == 0);
-                const Op* nx = oi + 1 < ops.size() ? &ops[oi + 1] : nullptr;
-                conv_timer_arm(e, cp, fl, by, op);
-                const int front_fused_mode = e->opt.front_fused;   // 0 off, 1 stream path, 2 always
-                const bool front_ok = stem_direct_on && front_fused_mode > 0 && nx && nx->kind == Op::CONV && front_fused_applicable(cp, nx->conv);
-                bool u8_src = e->stem_src && cp.in == e->ybuf["in"].ptr;   // the letterbox was skipped for this pass (run_detector_dev)
-                if (u8_src && !(stem_direct_on && (stem_u8_applicable(cp, e->stem_geom) || (front_ok && front_fused_resize_ok(e->stem_geom))))) {
-                    // run_detector_dev decided the fold-in from the engine's widths, this op list decides which kernel runs: should they ever
-                    // disagree (a plan or layout change), the letterbox kernel runs now and the pass goes on from its tensor
-                    ProfScope ps(e, VC_PROF_DETECT_AUX, 0, 0, s);
-                    VC_TRY(launch_letterbox(e->stem_src, e->ybuf["in"].ptr, cp.B, e->stem_geom, e->aux_prec, s));
-                    e->stem_src = nullptr; e->in_stale = false;
-                    u8_src = false;
-                }
-                const bool fuse_front = front_ok && (front_fused_mode == 2 || u8_src);
-                const bool c3_fused_on = e->opt.c3_fused != 0;
-                const bool fuse_c3 = c3_fused_on && oi + 3 < ops.size() && ops[oi + 1].kind == Op::CONV && ops[oi + 2].kind == Op::CONV && ops[oi + 3].kind == Op::CONV &&
-                                     c3_fused_applicable(cp, ops[oi + 1].conv, ops[oi + 2].conv, ops[oi + 3].conv);
-                if (fuse_c3) {                                                // the first C3 block in one kernel (c3_fused.hip): y1, y2, b1, m stay in LDS
-                    double flc = fl;
-                    for (int j = 1; j <= 3; ++j) flc += 2.0 * ops[oi + j].conv.M * (double)ops[oi + j].conv.Cout * ops[oi + j].C;
-                    const ConvP& o3 = ops[oi + 3].conv;
-                    double wbytes = 0;
-                    for (int j = 0; j <= 3; ++j) wbytes += (double)ops[oi + j].conv.Cout * ops[oi + j].conv.K * es;
-                    const double byc = (double)cp.B * cp.H * cp.W * cp.Cin * es + wbytes + (double)o3.M * o3.Cout * es;
-                    cp.cfg = 103; cp.ablate = e->opt.c3_ablate;
-                    if (cp.ev_start && e->prof_used > 0) { e->prof_pairs[e->prof_used - 1].flops = flc; e->prof_pairs[e->prof_used - 1].bytes = byc; }   // the pair armed above times all four layers
-                    {
-                        ProfScope ps(e, VC_PROF_CONV, flc, byc, s);
-                        VC_TRY(launch_c3_fused(cp, ops[oi + 1].conv, ops[oi + 2].conv, ops[oi + 3].conv, s));
-                    }
-                    if (e->profiling && e->op_log.size() < (1u << 20)) {
-                        char line[256];
-                        snprintf(line, sizeof(line), "conv M=%d N=%d K=%d k=1x1 s=1 cfg=103 ms=%.4f tflops=%.1f\n", cp.M, 64, 64, e->last_ms, flc / (e->last_ms * 1e-3) / 1e12);
-                        e->op_log += line;
-                    }
-                    oi += 3;                                                  // m.cv1, m.cv2 and cv3 are done
-                    break;
-                }
-                if (e->opt.reid_block_fused != 0 && nx && nx->kind == Op::CONV && reid_block_fused_applicable(cp, nx->conv)) {   // a 64-channel ReID BasicBlock in one kernel (reid_block_fused.hip)
-                    const ConvP& o2 = nx->conv;
-                    const double flb = fl + 2.0 * o2.M * (double)o2.Cout * nx->C;
-                    const double byb = ((double)cp.B * cp.H * cp.W * cp.Cin + (double)cp.Cout * cp.K + (double)o2.Cout * o2.K) * es + (double)o2.M * o2.Cout * es;   // x in, both weights, y out
-                    cp.cfg = 106;
-                    if (cp.ev_start && e->prof_used > 0) { e->prof_pairs[e->prof_used - 1].flops = flb; e->prof_pairs[e->prof_used - 1].bytes = byb; }
-                    {
-                        ProfScope ps(e, VC_PROF_CONV, flb, byb, s);
-                        VC_TRY(launch_reid_block_fused(cp, o2, s));
-                    }
-                    if (e->profiling && e->op_log.size() < (1u << 20)) {
-                        char line[256];
-                        snprintf(line, sizeof(line), "conv M=%d N=%d K=%d k=3x3 s=1 cfg=106 ms=%.4f tflops=%.1f\n", cp.M, 64, 1152, e->last_ms, flb / (e->last_ms * 1e-3) / 1e12);
-                        e->op_log += line;
-                    }
-                    ++oi;                                                     // conv2 is done
-                    break;
-                }
-                const bool bneck_fused_on = e->opt.bneck_fused != 0;
-                if (bneck_fused_on && e->opt.bneck_cv3 != 0 && oi + 2 < ops.size() && ops[oi + 1].kind == Op::CONV && ops[oi + 2].kind == Op::CONV &&
-                    bneck_cv3_fused_applicable(cp, ops[oi + 1].conv, ops[oi + 2].conv)) {   // the last 64-channel Bottleneck of a C3 + the block's cv3 in one kernel
-                    const ConvP &o2 = ops[oi + 1].conv, &o3 = ops[oi + 2].conv;
-                    const double flb = fl + 2.0 * o2.M * (double)o2.Cout * ops[oi + 1].C + 2.0 * o3.M * (double)o3.Cout * ops[oi + 2].C;
-                    const double byb = ((double)cp.B * cp.H * cp.W * (cp.Cin + 64) + (double)cp.Cout * cp.K + (double)o2.Cout * o2.K + (double)o3.Cout * o3.K) * es + (double)o3.M * o3.Cout * es;
-                    cp.cfg = 105;
-                    if (cp.ev_start && e->prof_used > 0) { e->prof_pairs[e->prof_used - 1].flops = flb; e->prof_pairs[e->prof_used - 1].bytes = byb; }
-                    {
-                        ProfScope ps(e, VC_PROF_CONV, flb, byb, s);
-                        VC_TRY(launch_bneck_cv3_fused(cp, o2, o3, s));
-                    }
-                    if (e->profiling && e->op_log.size() < (1u << 20)) {
-                        char line[256];
-                        snprintf(line, sizeof(line), "conv M=%d N=%d K=%d k=3x3 s=1 cfg=105 ms=%.4f tflops=%.1f\n", cp.M, 128, 768, e->last_ms, flb / (e->last_ms * 1e-3) / 1e12);
-                        e->op_log += line;
-                    }
-                    oi += 2;                                                  // the 3x3 conv and cv3 are done
-                    break;
-                }
-                if (bneck_fused_on && nx && nx->kind == Op::CONV && bneck_fused_applicable(cp, nx->conv)) {   // 64-channel Bottleneck in one kernel (bneck_fused.hip)
-                    const ConvP& o2 = nx->conv;
-                    const double flb = fl + 2.0 * o2.M * (double)o2.Cout * nx->C;
-                    const double byb = (double)cp.B * cp.H * cp.W * cp.Cin * es * (o2.res_mode != RES_NONE ? 1.0 : 1.0) + ((double)cp.Cout * cp.K + (double)o2.Cout * o2.K) * es +
-                                       (double)o2.M * o2.Cout * es;
-                    cp.cfg = 104;
-                    if (cp.ev_start && e->prof_used > 0) { e->prof_pairs[e->prof_used - 1].flops = flb; e->prof_pairs[e->prof_used - 1].bytes = byb; }
-                    {
-                        ProfScope ps(e, VC_PROF_CONV, flb, byb, s);
-                        VC_TRY(launch_bneck_fused(cp, o2, s));
-                    }
-                    if (e->profiling && e->op_log.size() < (1u << 20)) {
-                        char line[256];
-                        snprintf(line, sizeof(line), "conv M=%d N=%d K=%d k=3x3 s=1 cfg=104 ms=%.4f tflops=%.1f\n", cp.M, 64, 640, e->last_ms, flb / (e->last_ms * 1e-3) / 1e12);
-                        e->op_log += line;
-                    }
-                    ++oi;                                                     // the 3x3 conv is done
-                    break;
-                }
-                if (e->opt.fuse_s2_pw != 0 && op.sole_reader_next && nx && nx->kind == Op::CONV && s2halo_pw_applicable(cp, nx->conv)) {
-                    // a 3x3 / s2 conv and the pointwise conv that alone reads it in one launch (conv3x3s2_halo_kernel<..., F2>): YOLOv5s layer 3 + C3.cv1 | cv2 of layer 4
-                    const ConvP& o2 = nx->conv;
-                    const double flb = fl + 2.0 * o2.M * (double)o2.Cout * nx->C;
-                    const double byb = ((double)cp.B * cp.H * cp.W * cp.Cin + (double)cp.Cout * cp.K + (double)o2.Cout * o2.K) * es + (double)o2.M * o2.Cout * es;   // x in, both weights, cv1 | cv2 out
-                    cp.cfg = 107;
-                    if (cp.ev_start && e->prof_used > 0) { e->prof_pairs[e->prof_used - 1].flops = flb; e->prof_pairs[e->prof_used - 1].bytes = byb; }
-                    {
-                        ProfScope ps(e, VC_PROF_CONV, flb, byb, s);
-                        VC_TRY(launch_s2halo_pw(cp, o2, s));
-                    }
-                    if (e->profiling && e->op_log.size() < (1u << 20)) {
-                        char line[256];
-                        snprintf(line, sizeof(line), "conv M=%d N=%d K=%d k=3x3 s=2 cfg=107 ms=%.4f tflops=%.1f\n", cp.M, 128, cp.K + 128, e->last_ms, flb / (e->last_ms * 1e-3) / 1e12);
-                        e->op_log += line;
-                    }
-                    static const bool also_store = getenv("VC_S2PW_STORE") && atoi(getenv("VC_S2PW_STORE")) != 0;   // diagnostics: the fused kernel also stores the 3x3's output
-                    if (!also_store) e->s2pw_folded.push_back(op.conv);                        // its own output stays unwritten (vc_detect_debug_layer produces it on demand)
-                    ++oi;                                                     // the pointwise conv is done
-                    break;
-                }
-                if (fuse_front) {                                             // YOLO layers 0 + 1 in one kernel (front_fused.hip): layer 0 never reaches HBM
-                    const Op& o1 = *nx;
-                    const double fl1 = 2.0 * o1.conv.M * (double)o1.conv.Cout * o1.C;
-                    const double by01 = ((double)cp.B * cp.H * cp.W * cp.Cin + (double)cp.Cout * cp.K + (double)o1.conv.Cout * o1.conv.K) * es + (double)o1.conv.M * o1.conv.Cout * es;
-                    cp.cfg = 102; cp.ablate = e->opt.ff_ablate;
-                    if (cp.ev_start && e->prof_used > 0) { e->prof_pairs[e->prof_used - 1].flops = fl + fl1; e->prof_pairs[e->prof_used - 1].bytes = by01; }   // the pair armed above now times both layers
-                    ProfScope ps(e, VC_PROF_CONV, fl + fl1, by01, s);
-                    VC_TRY(launch_front_fused(cp, o1.conv, u8_src ? e->stem_src : nullptr, e->stem_geom, s));
-                    e->l0_stale = true;                                       // layer 0 lived in LDS only
-                    ++oi;                                                     // the 3x3 conv is done
-                } else if (stem_direct_on && stem_direct_applicable(cp)) {   // YOLO stem, bf16: direct convolution (stem_direct.hip)
-                    cp.cfg = 100;
-                    ProfScope ps(e, VC_PROF_CONV, fl, by, s);
-                    // fp8 engine: the stem also writes the e4m3 copy the next layer reads (TO_FP8 of its own output, folded in)
-                    const View* q8 = nx && nx->kind == Op::TO_FP8 && nx->a.ptr == cp.out && nx->a.co == cp.out_co ? &nx->b : nullptr;
-                    if (u8_src) VC_TRY(launch_stem_direct_u8(cp, e->stem_src, e->stem_geom, s, q8, 1.0f / e->act_scale));   // letterbox folded in
-                    else VC_TRY(launch_stem_direct(cp, s, q8, 1.0f / e->act_scale));
-                    if (q8) ++oi;                                            // the conversion op is done
-                } else if (reid_stem_on && nx && nx->kind == Op::MAXPOOL && nx->a.ptr == cp.out && reid_stem_applicable(cp, nx->b.cs, nx->b.co)) {
-                    cp.cfg = 101;                                            // ReID stem: conv + ReLU + MaxPool in one kernel (reid_stem.hip)
-                    ProfScope ps(e, VC_PROF_CONV, fl, by, s);
-                    VC_TRY(launch_reid_stem_pool(cp, nx->b.ptr, s));
-                    ++oi;                                                    // the pool op is done
-                } else {
-                    if (op.tuned == -2) op.tuned = cp.m_dev ? -1 : tuned_cfg(e, cp, s);   // a device-side row count: the implicit-GEMM heuristic (the only family that honours it)
-                    cp.cfg = op.tuned;
-                    {
-                        ProfScope ps(e, VC_PROF_CONV, fl, by, s);
-                        VC_TRY(launch_conv(cp, s));
-                    }
-                    if (e->profiling && (op.rows_level >= 0 || op.dense_flops >= 0)) {   // blocking profile: the scope has synchronised
-                        ProfCat& pc = e->prof[VC_PROF_CONV];
-                        double fe = fl, be = by;
-                        if (op.rows_level >= 0) {                            // executed work = fixed part + gathered rows x per-row work
-                            int rows = 0;
-                            VC_HIP(hipMemcpy(&rows, e->d_hc_count + op.rows_level, sizeof(int), hipMemcpyDeviceToHost));
-                            rows = std::min(rows, e->hc_cap[op.rows_level]);
-                            fe += rows * op.flops_per_row; be += rows * op.bytes_per_row;
-                            pc.flops += fe - fl; pc.bytes += be - by;
-                            fl_exec = fe;
-                        }
-                        // the scope credited (fl, by) to the dense-equivalent accumulators as well: replace them by the dense head's figures
-                        pc.flops_dense += (op.dense_flops >= 0 ? op.dense_flops : fe) - fl;
-                        pc.bytes_dense += (op.dense_bytes >= 0 ? op.dense_bytes : be) - by;
-                    }
-                }
-                if (e->profiling && e->op_log.size() < (1u << 20)) {
-                    char line[256];
-                    const ConvP& c = op.conv;
-                    snprintf(line, sizeof(line), "%s M=%d N=%d K=%d k=%dx%d s=%d cfg=%d ms=%.4f tflops=%.1f\n", c.M > 0 ? "conv" : "?", c.M, c.Cout, c.K,
-                             c.kh, c.kw, c.sh, cp.cfg, e->last_ms, (fl_exec >= 0 ? fl_exec : fl) / (e->last_ms * 1e-3) / 1e12);
-                    e->op_log += line;
-                }
-                break;
-            }
-            case Op::SPPF: { ProfScope ps(e, aux_cat, 0, 0, s); VC_TRY(launch_sppf_pool(op.a, op.C, e->prec, e->opt.sppf_sep, s)); break; }
-            case Op::UPSAMPLE: {
-                // bf16: when the consumer is the pointwise conv over [upsampled | skip] (C3.cv1 | cv2 of layers 13 / 17) it reads the half-size
-                // map itself; the slice of the concat buffer stays unwritten (vc_detect_debug_layer produces it on demand)
-                const Op* nx = oi + 1 < ops.size() ? &ops[oi + 1] : nullptr;
-                const bool fold = e->opt.fuse_upsample && e->prec == PREC_BF16 && nx && nx->kind == Op::CONV && nx->conv.prec == PREC_BF16 && nx->conv.kh == 1 &&
-                                  nx->conv.kw == 1 && nx->conv.sh == 1 && nx->conv.ph == 0 && !nx->conv.m_dev && nx->conv.in == op.b.ptr && nx->conv.in_co == op.b.co &&
-                                  nx->conv.in_cs == op.b.cs && nx->conv.H == 2 * op.a.H && nx->conv.W == 2 * op.a.W && op.a.C % 64 == 0 && nx->conv.Cin % 64 == 0 &&
-                                  op.a.C < nx->conv.Cin && op.a.cs % 8 == 0 && op.a.co % 8 == 0;
-                if (fold) { pending_up = &op; e->up_folded.push_back({op.a, op.b}); break; }
-                ProfScope ps(e, aux_cat, 0, 0, s);
-                VC_TRY(launch_upsample2x(op.a, op.b, e->prec, s));
-                break;
-            }
-            case Op::MAXPOOL: { ProfScope ps(e, aux_cat, 0, 0, s); VC_TRY(launch_maxpool3s2(op.a, op.b, e->aux_prec, s)); break; }   // ReID only
-            case Op::TO_FP8: { ProfScope ps(e, aux_cat, 0, 0, s); VC_TRY(launch_bf16_to_fp8(op.a, op.b, 1.0f / e->act_scale, s)); break; }
-            case Op::HEAD_COMPACT: {
-                ProfScope ps(e, aux_cat, 0, 0, s);
-                const int i = op.level, M = op.a.B * op.a.H * op.a.W;
-                VC_TRY(launch_head_compact(e->d_obj[i], op.a, M, op.a.H * op.a.W, e->cfg.conf_thres, e->hc_cap[i], e->d_hc_count + i, e->d_hc_list[i], e->d_hc_x[i],
-                                           e->post.overflow, s));
-                break;
-            }
-        }
-    }
-    return VC_OK;
-}
-
-// AutoShape geometry: models/common.py::AutoShape.forward + utils/augmentations.py::letterbox (auto=False)
-static int py_round(double x) { return (int)std::nearbyint(x); }     // banker's rounding like Python 3 round()
-
-static void autoshape_net_size(const int* h, const int* w, int n, int size, int& nh, int& nw) {
-    double mh = 0, mw = 0;
-    for (int i = 0; i < n; ++i) {
-        const double g = (double)size / std::max(h[i], w[i]);
-        mh = std::max(mh, h[i] * g); mw = std::max(mw, w[i] * g);
-    }
-    nh = (int)std::ceil(mh / 32.0) * 32; nw = (int)std::ceil(mw / 32.0) * 32;
-}
-
-static LetterboxGeom letterbox_geom(int h0, int w0, int nh, int nw, bool swap_rb) {
-    LetterboxGeom g{};
-    g.src_h = h0; g.src_w = w0; g.net_h = nh; g.net_w = nw;
-    const double r = std::min((double)nh / h0, (double)nw / w0);
-    g.unpad_w = py_round(w0 * r); g.unpad_h = py_round(h0 * r);
-    const double dw = (nw - g.unpad_w) / 2.0, dh = (nh - g.unpad_h) / 2.0;
-    g.top = py_round(dh - 0.1); g.left = py_round(dw - 0.1);
-    g.swap_rb = swap_rb ? 1 : 0;
-    return g;
-}
-
-static int yolo_forward(vc_engine* e, int B, int nh, int nw) {
-    hipStream_t ds = e->dstream;
-    const bool want_sparse = e->prec == PREC_BF16 && e->opt.sparse_head && !e->want_pred_debug && e->d_hc_count;
-    YoloPlan& plan = e->yolo_plans[{B, nh, nw, want_sparse ? 1 : 0}];
-    if (plan.ops.empty()) {
-        const int st = yolo_build_ops(e, B, nh, nw, plan.ops);
-        if (st != VC_OK) { plan.ops.clear(); return st; }
-        memcpy(plan.layer_view, e->layer_view, sizeof(plan.layer_view));
-        plan.sparse = e->sparse_pass;
-    } else {
-        memcpy(e->layer_view, plan.layer_view, sizeof(plan.layer_view));
-        e->sparse_pass = plan.sparse;
-    }
-    std::vector<Op>& ops = plan.ops;
-    e->l0_stale = false;
-    e->up_folded.clear();
-    e->s2pw_folded.clear();
-    if (e->sparse_pass) {                                    // the compaction sets overflow flags and counts: clear them ahead of the ops
-        e->hc_ring_cur = (int)(e->hc_ring_seq++ % vc_engine::HC_RING);
-        VC_HIP(hipMemsetAsync(e->d_zero, 0, e->zero_bytes, ds));
-    }
-    VC_TRY(run_ops(e, ops, VC_PROF_DETECT_AUX, ds));          // (joins the head stream before it returns: the decode reads the head ops' rows)
-    if (e->sparse_pass && e->prof_async && e->h_hc_ring)     // executed-work accounting: this pass's gathered-row counts, next to the event pairs
-        VC_HIP(hipMemcpyAsync(e->h_hc_ring + (size_t)e->hc_ring_cur * 4, e->d_hc_count, 4 * sizeof(int), hipMemcpyDeviceToHost, ds));
-    // decode + NMS
-    const int nc = e->cfg.num_classes, no = nc + 5, lcs = round_up(3 * no, 8);
-    DecodeLevel lv[3];
-    int base = 0;
-    const int strides[3] = {8, 16, 32};
-    for (int i = 0; i < 3; ++i) {
-        lv[i].logits = e->d_logits[i]; lv[i].bf16 = e->prec == PREC_F32 ? 0 : 1; lv[i].ny = nh / strides[i]; lv[i].nx = nw / strides[i]; lv[i].cs = lcs;
-        lv[i].stride = (float)strides[i];
-        for (int a = 0; a < 3; ++a) { lv[i].anchor_w[a] = e->anchors[i][2 * a]; lv[i].anchor_h[a] = e->anchors[i][2 * a + 1]; }
-        lv[i].base = base;
-        base += 3 * lv[i].ny * lv[i].nx;
-    }
-    e->last_B = B; e->last_nh = nh; e->last_nw = nw; e->last_ntotal = base;
-    float* dbg = nullptr;
-    if (e->want_pred_debug) {
-        if (!e->d_pred_debug) {
-            const int S = round_up(e->cfg.img_size, 32);
-            const size_t nmax = (size_t)3 * ((S / 8) * (S / 8) + (S / 16) * (S / 16) + (S / 32) * (S / 32));
-            VC_TRY(dev_alloc(e, (void**)&e->d_pred_debug, (size_t)e->cfg.max_batch * nmax * no * sizeof(float)));
-        }
-        dbg = e->d_pred_debug;
-    }
-    if (e->sparse_pass) {
-        for (int i = 0; i < 3; ++i) lv[i].logits = e->d_hc_logits[i];
-        ProfScope ps(e, VC_PROF_DETECT_AUX, 0, 0, ds);
-        VC_TRY(launch_decode_sparse(lv, e->d_hc_count, e->d_hc_list, e->hc_cap, nc, e->cfg.conf_thres, e->cfg.max_candidates, e->post, ds));
-    } else {
-        ProfScope ps(e, VC_PROF_DETECT_AUX, 0, 0, ds);
-        VC_TRY(launch_decode(lv, 3, B, nc, e->cfg.conf_thres, e->cfg.max_candidates, e->post, dbg, base, ds));
-    }
-    { ProfScope ps(e, VC_PROF_DETECT_AUX, 0, 0, ds); VC_TRY(launch_nms(B, e->cfg.max_candidates, e->cfg.max_det, e->cfg.iou_thres, e->d_geom, e->post, ds)); }
-    return VC_OK;
-}
-
-int run_detector_dev(vc_engine* e, const uint8_t* d_frames, int B, int h, int w, bool swap_rb) {
-    VC_CHECK(e->finalized && e->cfg.with_detector, VC_ERR_STATE, "detector not finalized");
-    VC_CHECK(B >= 1, VC_ERR_ARG, "a batch needs at least one frame (got %d)", B);
-    VC_CHECK(B <= e->cfg.max_batch, VC_ERR_CAPACITY, "batch %d exceeds max_batch %d", B, e->cfg.max_batch);
-    VC_CHECK(h >= 1 && w >= 1, VC_ERR_ARG, "frame size %d x %d", h, w);
-    int nh, nw;
-    autoshape_net_size(&h, &w, 1, e->cfg.img_size, nh, nw);
-    const LetterboxGeom g = letterbox_geom(h, w, nh, nw, swap_rb);
-    float* hg = e->h_geom + (size_t)(e->geom_seq++ & 1) * e->cfg.max_batch * 5;      // two pinned slots: two submissions may be in flight
-    scale_geom_host(ScaleGeom{nh, nw, h, w}, hg);
-    for (int b = 1; b < B; ++b) memcpy(hg + (size_t)b * 5, hg, 5 * sizeof(float));
-    VC_HIP(hipMemcpyAsync(e->d_geom, hg, (size_t)B * 5 * sizeof(float), hipMemcpyHostToDevice, e->dstream));
-    // bf16, frame already at network scale: the stem reads the u8 frames itself (same arithmetic per pixel, bit-identical stem
-    // output) and the 8-byte-per-pixel letterboxed tensor is neither written nor read back
-    static const bool fuse_on = !(getenv("VC_STEM_U8") && atoi(getenv("VC_STEM_U8")) == 0) && !(getenv("VC_STEM_DIRECT") && atoi(getenv("VC_STEM_DIRECT")) == 0);
-    const bool same_scale = g.unpad_h == g.src_h && g.unpad_w == g.src_w && g.src_w % 2 == 0 && g.left % 2 == 0;
-    // frames that need the resize (1280 x 720 -> 384 x 640, Q8): only front_fused_kernel evaluates it at patch-build time, so the fold-in
-    // needs that kernel to be the one that runs (YOLOv5s widths, bf16 engine, option on) and the tile's source footprint to fit its staging
-    const bool resize_ok = !same_scale && ((uintptr_t)d_frames & 3) == 0 && e->prec == PREC_BF16 && e->opt.front_fused > 0 && e->ch[0] == 32 && e->ch[1] == 64 && front_fused_resize_ok(g);
-    const bool fuse = fuse_on && e->aux_prec == PREC_BF16 && (same_scale || resize_ok) && e->ch[0] % 16 == 0 && e->ch[0] <= 64;
-    e->stem_src = fuse ? d_frames : nullptr;
-    e->stem_geom = g;
-    e->in_stale = fuse;
-    if (!fuse) { ProfScope ps(e, VC_PROF_DETECT_AUX, 0, 0, e->dstream); VC_TRY(launch_letterbox(d_frames, e->ybuf["in"].ptr, B, g, e->aux_prec, e->dstream)); }
-    const int st = yolo_forward(e, B, nh, nw);
-    if (fuse && e->in_stale) e->stem_src = d_frames;    // kept for vc_detect_debug_layer(-1) (not when run_ops fell back to the letterbox kernel)
-    return st;
-}
-
-// ------------------------------------------------------------------------------------------------ ReID net
-static const struct { const char* name; int cin, cout; bool down; } kReidBlocks[8] = {
-    {"layer1.0", 64, 64, false}, {"layer1.1", 64, 64, false}, {"layer2.0", 64, 128, true}, {"layer2.1", 128, 128, false},
-    {"layer3.0", 128, 256, true}, {"layer3.1", 256, 256, false}, {"layer4.0", 256, 512, true}, {"layer4.1", 512, 512, false}};
-
-static void reid_define(vc_engine* e) {
-    Net& n = e->reid;
-    n.add("conv", 64, 3, 3, 3);
-    for (const auto& b : kReidBlocks) {
-        n.add(std::string(b.name) + ".conv1", b.cout, b.cin, 3, 3);
-        n.add(std::string(b.name) + ".conv2", b.cout, b.cout, 3, 3);
-        if (b.down || b.cin != b.cout) n.add(std::string(b.name) + ".downsample", b.cout, b.cin, 1, 1);
-    }
-}
-
-static int reid_cpad(int prec) { return prec == PREC_F32 ? 4 : 8; }
-
-static int reid_alloc(vc_engine* e) {
-    const int es = elem_size(e->aux_prec);
-    const size_t K = e->cfg.max_crops;
-    auto& m = e->rbuf;
-    VC_TRY(alloc_buf(e, m, "in", K * 50 * 50, reid_cpad(e->aux_prec), es));
-    VC_TRY(alloc_buf(e, m, "r0", K * 50 * 50, 64, es));
-    VC_TRY(alloc_buf(e, m, "x0", K * 25 * 25, 64, es));
-    int hw = 25;
-    for (int i = 0; i < 8; ++i) {
-        const auto& b = kReidBlocks[i];
-        if (b.down) hw = (hw - 1) / 2 + 1;
-        const std::string p = b.name;
-        VC_TRY(alloc_buf(e, m, p + ".t", K * hw * hw, b.cout, es));
-        VC_TRY(alloc_buf(e, m, p + ".y", K * hw * hw, b.cout, es));
-        if (b.down || b.cin != b.cout) VC_TRY(alloc_buf(e, m, p + ".d", K * hw * hw, b.cout, es));
-    }
-    VC_TRY(dev_alloc(e, (void**)&e->d_crops, K * 5 * sizeof(int)));
-    VC_TRY(host_alloc(e, (void**)&e->h_crops, K * 5 * sizeof(int)));
-    VC_TRY(dev_alloc(e, (void**)&e->d_feat, K * VC_FEAT_DIM * sizeof(float)));
-    for (int q = 0; q < 3; ++q) {                      // stream path: ReID of batches i+1 / i+2 runs while batch i is tracked
-        VC_TRY(dev_alloc(e, (void**)&e->d_feat2[q], K * VC_FEAT_DIM * sizeof(float)));
-        VC_TRY(dev_alloc(e, (void**)&e->d_crops2[q], K * 5 * sizeof(int)));
-        VC_TRY(host_alloc(e, (void**)&e->h_crops2[q], K * 5 * sizeof(int)));
-    }
-    VC_TRY(host_alloc(e, (void**)&e->h_feat, K * VC_FEAT_DIM * sizeof(float)));
-    VC_TRY(dev_alloc(e, (void**)&e->d_reid_in_nchw, K * 3 * 50 * 50 * sizeof(float)));
-    return VC_OK;
-}
-
-// forward from the pre-filled "in" buffer (k x 50 x 50 x cpad) to feat_out.  A conv launch addresses at most 2^24 output pixels
-// (conv_check), and the first layer has 2500 per crop: more than VC_REID_CHUNK crops run as several passes over slices of "in"
-// (the other activation buffers are reused; the passes are ordered on the stream).
-#define VC_REID_CHUNK 6400
-#define VC_REID_PLAN_CACHE_MAX_K 256       // crop counts whose op plans are kept (k0 is 0 for these: one chunk)
-static int reid_forward_chunk(vc_engine* e, int k0, int k, hipStream_t rs, float* feat_out);
-static int reid_forward(vc_engine* e, int k, hipStream_t rs, float* feat_out) {
-    // ... and its 50 x 50 x 64 output must stay below the 2 GiB a buffer descriptor addresses (fp32: 3200 crops)
-    const int chunk = std::min(VC_REID_CHUNK, (int)(((1ull << 31) - 1) / ((size_t)2500 * 64 * elem_size(e->aux_prec))) / 64 * 64);
-    for (int k0 = 0; k0 < k; k0 += chunk)
-        VC_TRY(reid_forward_chunk(e, k0, std::min(chunk, k - k0), rs, feat_out + (size_t)k0 * VC_FEAT_DIM));
-    return VC_OK;
-}
-static int reid_forward_chunk(vc_engine* e, int k0, int k, hipStream_t rs, float* feat_out) {
-    // The plan cache pays at batch 1 (a few crops per frame, the same counts again and again).  A batch of the stream path has thousands of
-    // distinct crop counts: those build a transient plan (21 ops, tens of microseconds beside a multi-millisecond pass) instead of
-    // filling the map (~10 KB per entry, a full clear at 8192 entries).
-    ReidPlan transient;
-    const bool cached = k <= VC_REID_PLAN_CACHE_MAX_K;
-    ReidPlan& plan = cached ? e->reid_plans[{k0, k}] : transient;
-    std::vector<Op>& ops = plan.ops;
-    if (!ops.empty()) {
-        VC_TRY(run_ops(e, ops, VC_PROF_REID_AUX, rs));
-        ProfScope ps(e, VC_PROF_REID_AUX, 0, 0, rs);
-        return launch_avgpool_l2norm(plan.out, feat_out, e->aux_prec, rs);
-    }
-    PlanBuilder pb{e, &e->reid, &ops, e->aux_prec};
-    auto& m = e->rbuf;
-    View x = mkview(m["in"], k, 50, 50, reid_cpad(e->aux_prec), 0);
-    x.ptr = (char*)x.ptr + (size_t)k0 * 50 * 50 * reid_cpad(e->aux_prec) * elem_size(e->aux_prec);
-    x = pb.conv("conv", x, mkview(m["r0"], k, 50, 50, 64, 0), 3, 1, 1, ACT_RELU);             // model.py:51-55
-    { Op op{}; op.kind = Op::MAXPOOL; op.a = x; op.b = mkview(m["x0"], k, 25, 25, 64, 0); ops.push_back(op); x = op.b; }   // :58
-    for (const auto& b : kReidBlocks) {                                                        // BasicBlock.forward, model.py:30-38
-        const std::string p = b.name;
-        const int s = b.down ? 2 : 1;
-        View t = pb.conv(p + ".conv1", x, mkview(m[p + ".t"], k, 0, 0, b.cout, 0), 3, s, 1, ACT_RELU);
-        View sc = x;
-        if (b.down || b.cin != b.cout) sc = pb.conv(p + ".downsample", x, mkview(m[p + ".d"], k, 0, 0, b.cout, 0), 1, s, 0, ACT_NONE);
-        x = pb.conv(p + ".conv2", t, mkview(m[p + ".y"], k, 0, 0, b.cout, 0), 3, 1, 1, ACT_RELU, &sc, RES_BEFORE_ACT);
-    }
-    if (pb.status != VC_OK) { const int st = pb.status; ops.clear(); return st; }
-    plan.out = x;
-    VC_TRY(run_ops(e, ops, VC_PROF_REID_AUX, rs));
-    { ProfScope ps(e, VC_PROF_REID_AUX, 0, 0, rs); VC_TRY(launch_avgpool_l2norm(x, feat_out, e->aux_prec, rs)); }               // model.py:70,93
-    return VC_OK;
-}
-
-int run_reid_on(vc_engine* e, const uint8_t* d_frames, int H, int W, int k, const int* d_crops, float* feat_out, hipStream_t rs) {
-    VC_CHECK(e->finalized && e->cfg.with_reid, VC_ERR_STATE, "ReID net not finalized");
-    VC_CHECK(k <= e->cfg.max_crops, VC_ERR_CAPACITY, "%d crops exceed max_crops %d", k, e->cfg.max_crops);
-    if (k <= 0) return VC_OK;
-    { ProfScope ps(e, VC_PROF_REID_AUX, 0, 0, rs);
-      VC_TRY(launch_crop_resize(d_frames, H, W, d_crops, k, e->rbuf["in"].ptr, reid_cpad(e->aux_prec), e->aux_prec, rs, e->opt.crop_per_pixel != 0)); }
-    return reid_forward(e, k, rs, feat_out);
-}
-
-// blocking-API flavour (vc_embed, vc_deepsort_update, vc_videotracker_run): tracker stream, shared crop / feature buffers
-int run_reid_dev(vc_engine* e, const uint8_t* d_frames, int H, int W, int k) {
-    VC_HIP(hipStreamSynchronize(e->rstream));          // the activation buffers are shared with the stream path's ReID
-    return run_reid_on(e, d_frames, H, W, k, e->d_crops, e->d_feat, e->stream);
 }
 
 }  // namespace vc
@@ -1249,10 +379,7 @@ int vc_engine_set_option(vc_engine* e, const char* name, int value) {
     else if (n == "c3_ablate") e->opt.c3_ablate = value;
     else if (n == "dot_arena_mb") { VC_CHECK(value >= 0, VC_ERR_ARG, "dot_arena_mb must be >= 0"); e->dot_arena_max_floats = (size_t)value * 262144; }
     else { set_error("unknown option '%s'", name); return VC_ERR_NOTFOUND; }
-    // A cached op resolved its tile configuration for the kernel variant the options selected at its first launch (the upsample fold-in
-    // runs on a subset of the tiles and has its own tune key): every switch sends the ops back to tuned_cfg.
-    for (auto& kv : e->yolo_plans) for (Op& op : kv.second.ops) op.tuned = -2;
-    for (auto& kv : e->reid_plans) for (Op& op : kv.second.ops) op.tuned = -2;
+    plans_retune(e);
     return VC_OK;
 }
 
@@ -1279,14 +406,9 @@ int vc_tune_import(vc_engine* e, const char* text) {
     }
     while (*p == ' ' || *p == '\n' || *p == '\t' || *p == '\r') ++p;
     VC_CHECK(*p == 0, VC_ERR_ARG, "vc_tune_import: malformed text after %d entries", n);
-    {   // the engines of this process on the same device follow (tuned_cfg consults g_tuned before timing anything)
-        std::lock_guard<std::mutex> lk(g_tune_mu);
-        for (const auto& kv : e->tuned) g_tuned["d" + std::to_string(e->cfg.device) + "_" + kv.first] = kv.second;
-    }
+    tune_cache_publish(e);
     if (n) e->tuned_dirty = true;
-    // cached op plans resolved their tile configuration at their first launch: they look the (imported) choice up again
-    for (auto& kv : e->yolo_plans) for (Op& op : kv.second.ops) op.tuned = -2;
-    for (auto& kv : e->reid_plans) for (Op& op : kv.second.ops) op.tuned = -2;
+    plans_retune(e);
     return VC_OK;
 }
 
@@ -1394,7 +516,7 @@ int vc_detect_debug_layer(vc_engine* e, int layer, float* out, size_t cap, int d
     }
     VC_CHECK(!(layer == 0 && e->l0_stale), VC_ERR_STATE,
              "layer 0 was not written by the last pass (front_fused_kernel keeps it in LDS); vc_engine_set_option(e, \"front_fused\", 0) and run again");
-    return read_view_f32(e, e->layer_view[layer], out, cap, dims);
+    return read_view_f32(e, e->last_plan->layer_view[layer], out, cap, dims);
 }
 
 int vc_detect_debug_pred(vc_engine* e, float* out, size_t cap) {

@@ -195,7 +195,7 @@ __global__ __launch_bounds__(RB_NW * 64) void reid_block_fused_kernel(const RbAr
     }
 }
 
-// p1 = BasicBlock.conv1, p2 = BasicBlock.conv2 as engine.hip::reid_forward_chunk builds them (no downsample branch)
+// p1 = BasicBlock.conv1, p2 = BasicBlock.conv2 as engine_plan.hip::reid_build_ops builds them (no downsample branch)
 bool reid_block_fused_applicable(const ConvP& p1, const ConvP& p2) {
     auto conv3 = [](const ConvP& p) {
         return p.prec == PREC_BF16 && p.kh == 3 && p.kw == 3 && p.sh == 1 && p.sw == 1 && p.ph == 1 && p.pw == 1 && p.Cin == 64 && p.Cout == 64 && p.act == ACT_RELU &&

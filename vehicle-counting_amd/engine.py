@@ -141,7 +141,7 @@ class Engine:
         return out
 
     def pretune(self, crop_counts=(32, 64, 128, 256, 512, 1024)):
-        """Run the ReID net once per problem-size bucket so the conv autotuner (engine.hip::tuned_cfg) has picked its tile
+        """Run the ReID net once per problem-size bucket so the conv autotuner (engine_run.hip::tuned_cfg) has picked its tile
         configurations before any timed work; the detector's convs are tuned by the first (warm-up) batch."""
         for k in crop_counts:
             if k <= self.cfg.max_crops and self.cfg.with_reid:
