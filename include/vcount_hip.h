@@ -95,7 +95,10 @@ int vc_engine_finalize(vc_engine* e); /* packs + uploads weights; detector/ReID 
  * VC_FRONT_FUSED, VC_CROP_PER_PIXEL, VC_DOT_ARENA_MB).  Names: "c3_fused", "bneck_fused", "bneck_cv3" (0 / 1), "front_fused" (0 off, 1 stream path,
  * 2 always), "crop_per_pixel", "sparse_head", "reid_block_fused", "fuse_upsample", "sppf_sep", "fuse_s2_pw", "head_side" (0 / 1; head_side: the P3 / P4 Detect-head ops on their own stream
  * beside the neck layers that follow them), "dot_arena_mb" (largest appearance-table arena the tracker may allocate; 0 = compute the
- * appearance rows inside the walk).  The parity tests use it to compare a fused kernel with the launches it replaces. */
+ * appearance rows inside the walk).  The parity tests use it to compare a fused kernel with the launches it replaces.
+ * "embed_kept_only" (default 1, environment VC_EMBED_KEPT_ONLY): crop and embed only the boxes DeepSort.update's own filter keeps
+ * (conf > min_confidence, then DeepSORT's NMS per class, deep_sort.py:31-37).  The reference embeds every box first and drops the rest
+ * afterwards; a dropped box never becomes a Detection, so its feature is never read and the rows are the same.  0 embeds every box. */
 int vc_engine_set_option(vc_engine* e, const char* name, int value);
 
 /* ---- detect: ImageDetect.run ------------------------------------------------------------------ */
@@ -153,7 +156,9 @@ int vc_tracker_debug_costs(vc_engine* e, int cap_entries, double* app, double* i
  * replaces the state (and parameters) of an existing tracker of any engine whose nn_budget_cap >= the snapshot's nn_budget. */
 int vc_tracker_snapshot(vc_engine* e, int tracker_id, void* buf, size_t cap, size_t* size);
 int vc_tracker_restore(vc_engine* e, int tracker_id, const void* buf, size_t size);
-/* DeepSort.update: boxes xyxy (k x 4 f64) + confidences on a BGR frame -> rows [x1,y1,x2,y2,track_id,-1,0]. */
+/* DeepSort.update: boxes xyxy (k x 4 f64) + confidences on a BGR frame -> rows [x1,y1,x2,y2,track_id,-1,0].
+ * Both blocking calls run the update's detection filter (deep_sort.py:31-37) before the crops are cut and, with the option
+ * "embed_kept_only", embed only the boxes it keeps; max_crops and the empty-crop refusal still count every box. */
 int vc_deepsort_update(vc_engine* e, int tracker_id, const uint8_t* bgr, int h, int w, const double* bbox_xyxy,
                        const double* conf, int k, int64_t* out_rows7, int cap_rows, int* out_m);
 /* VideoTracker.run: trackers[c] is the tracker id of class c.  boxes xywh (top-left), labels, scores as
@@ -217,7 +222,12 @@ int vc_yuv_to_bgr_dev(const vc_yuv_desc* d, const void* yuv_dev, int b, int h, i
  * vc_stream_collect returns the rows of the OLDEST outstanding batch (same layout as vc_stream_run) and blocks until they are
  * ready.  Calls that touch tracker state (vc_tracker_*, vc_deepsort_update, vc_videotracker_run) first wait for outstanding batches.
  * A submission that cannot be embedded (more than max_candidates boxes passed conf_thres, more boxes than max_crops, an empty crop)
- * is reported ONCE by the call that finds it and dropped; vc_stream_reset abandons everything in flight. */
+ * is reported ONCE by the call that finds it and dropped; vc_stream_reset abandons everything in flight.
+ * With the option "embed_kept_only" a batch is embedded under the filter (min_confidence, nms_max_overlap) that all trackers of the
+ * most recent vc_stream_run_async* call share -- batches are embedded ahead of the call that names their trackers -- and only the boxes
+ * DeepSort.update would turn into Detections (deep_sort.py:31-37) get a crop and a feature row.  If the trackers a batch is then run
+ * with have other parameters, or disagree among themselves, the batch is embedded again in full before it is tracked: rows never depend
+ * on the option.  max_crops, the empty-crop refusal and out_ndet count every box the detector returned. */
 int vc_stream_run_async(vc_engine* e, const int* trackers, int num_classes, const void* frames_dev, int b, int h, int w,
                         int cap_rows_per_frame);
 int vc_stream_collect(vc_engine* e, int64_t* out_rows6, int cap_rows_per_frame, int* out_m, int* out_ndet, int b);
@@ -229,10 +239,14 @@ int vc_stream_collect(vc_engine* e, int64_t* out_rows6, int cap_rows_per_frame, 
 int vc_stream_run_async_multi(vc_engine* e, const int* trackers /* n_cam x num_classes */, int n_cam, int num_classes, const int* cam_of_frame /* b */,
                               const void* frames_dev, int b, int h, int w, int cap_rows_per_frame);
 int vc_stream_reset(vc_engine* e);
+/* Running 64-bit totals over the stream path and the blocking tracker calls since the engine was created or vc_stream_reset was
+ * called: boxes that reached the ReID stage, and crops the ReID net was run on (a batch embedded twice counts twice). */
+int vc_stream_crop_stats(vc_engine* e, int64_t* boxes_detected, int64_t* crops_embedded);
 
 /* ---- one stream on several GPUs: frame-sharded front end (ordering contract of modules/__init__.py:54-84) -------- */
 /* Front half of the fused path for the OLDEST submission (vc_stream_submit): detections marshalled like networks/yolo.py:72-97 +
- * crops + ReID for every box (deep_sort.py:119-129).  out_rows7: n x [frame index in the batch, x1, y1, x2, y2, conf, label] float64 --
+ * crops + ReID for EVERY box (deep_sort.py:119-129; the caller owns the tracking, so nothing is filtered, and a batch the look-ahead of
+ * an earlier vc_stream_run_async* call embedded under its filter is embedded again in full).  out_rows7: n x [frame index in the batch, x1, y1, x2, y2, conf, label] float64 --
  * the boxes VideoTracker.run works on; frames without boxes contribute nothing (Q1).  *out_feat_dev: DEVICE address of the matching
  * n x 512 float32 embeddings, valid until the third following vc_stream_embed / vc_stream_run* call. */
 int vc_stream_embed(vc_engine* e, const void* frames_dev, int b, int h, int w, double* out_rows7, int cap_rows, int* out_n, const float** out_feat_dev);

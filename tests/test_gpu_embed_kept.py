@@ -1,0 +1,252 @@
+"""GPU: engine option `embed_kept_only` -- crop and embed only the boxes DeepSort.update's own filter keeps (conf > min_confidence, then
+DeepSORT's NMS per class, deep_sort.py:31-37).  The reference embeds every box and drops the rest afterwards (Q5); a dropped box never
+becomes a Detection, so rows must not depend on the option.  Every test compares the option on with the option off on the same calls;
+the first also holds both to VideoTrackerOracle.  The scene is 160 x 160 (the detector still runs; its output is replaced by injected
+boxes), 12 frames in batches of 4, so the look-ahead embeds batches 2 and 3 before their trackers are handed in."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+import vehicle_counting_amd.engine as E  # noqa: E402
+from oracle import deepsort as od  # noqa: E402
+from oracle import reid as orr  # noqa: E402
+from oracle import yolov5 as oy  # noqa: E402
+from vehicle_counting_amd.synth import synth_frames  # noqa: E402
+from vehicle_counting_amd.weights import synth_reid, synth_yolo  # noqa: E402
+
+TRACK_CFG = dict(MAX_DIST=0.2, MIN_CONFIDENCE=0.25, NMS_MAX_OVERLAP=0.5, MAX_IOU_DISTANCE=0.6, MAX_AGE=30, N_INIT=3, NN_BUDGET=60)
+TRACK_KW = dict(max_dist=0.2, min_confidence=0.25, nms_max_overlap=0.5, max_iou_distance=0.6, max_age=30, n_init=3, nn_budget=60)
+T, B, H, W, NC = 12, 4, 160, 160, 3
+
+# [x1, y1, x2, y2, conf, class] in frame 0; every box moves (+2, +1) pixels per frame, so the overlaps below hold in every frame.
+# DeepSORT's overlap is intersection / area of the LOWER-scoring box with the +1 pixel convention, threshold '>' 0.5 (Q6).
+BOXES = [
+    (5, 5, 75, 95, 0.9, 0),        # 0 A: large, kept
+    (20, 20, 50, 60, 0.8, 0),      # 1 B: nested in A, same class: overlap 1 -> dropped
+    (20, 20, 50, 60, 0.8, 1),      # 2 B in another class: kept
+    (10, 40, 110, 140, 0.5, 2),    # 3 low-confidence large box ...
+    (40, 70, 70, 110, 0.95, 2),    # 4 ... around a high-confidence small one: 31 * 41 / (101 * 101) = 0.12 of the large box -> both kept
+    (55, 30, 105, 70, 0.7, 0),     # 5 21 * 41 of its 51 * 41 pixels (41 %) inside A -> kept
+    (100, 100, 130, 140, 0.25, 1),  # 6 conf == min_confidence: '>' fails -> dropped
+    (85, 5, 135, 50, 0.6, 1),      # 7 equal confidence, different geometry, each suppresses the other (1.0 of box 8, 0.72 of box 7):
+    (90, 8, 135, 48, 0.6, 1),      # 8 the stable ascending sort picks the later one; box 7 is dropped
+]
+DROPPED, KEPT_PER_FRAME = {1, 6, 7}, 6
+
+
+def scene():
+    det = np.zeros((T, len(BOXES), 6), np.float32)
+    for f in range(T):
+        det[f] = np.array(BOXES, np.float32)
+        det[f, :, [0, 2]] += 2.0 * f
+        det[f, :, [1, 3]] += 1.0 * f
+    return det, np.full(T, len(BOXES), np.int32)
+
+
+def kept_indices(det_f, min_conf, nms_overlap):
+    """Box indices of one frame that DeepSort.update turns into Detections: the reference's filter, per class, on the rows
+    marshalled like networks/yolo.py:72-97 (oracle.deepsort.DeepSortOracle.update lines :31-37)."""
+    m = oy.marshal_like_reference(det_f)
+    xywh, labels, scores = np.asarray(m["bboxes"], np.float64), np.asarray(m["classes"]), np.asarray(m["scores"], np.float64)
+    kept = []
+    for c in range(NC):
+        idx = [i for i in np.flatnonzero(labels == c) if scores[i] > min_conf]
+        keep = od.dsort_nms(xywh[idx], nms_overlap, scores[idx]) if idx else []      # xywh here is top-left + size = tlwh
+        kept += [int(idx[k]) for k in keep]
+    return sorted(kept)
+
+
+@pytest.fixture(scope="module")
+def case():
+    det, cnt = scene()
+    frames = synth_frames(T, H, W, n_obj=6, seed=1702)
+    kept = [kept_indices(det[f], TRACK_CFG["MIN_CONFIDENCE"], TRACK_CFG["NMS_MAX_OVERLAP"]) for f in range(T)]
+    ovt = od.VideoTrackerOracle(NC, TRACK_CFG, orr.make_embedder(synth_reid(1702)))
+    ref = []
+    for f in range(T):
+        m = oy.marshal_like_reference(det[f])
+        res = ovt.run(frames[f], m["bboxes"], m["classes"], m["scores"])
+        ref.append(np.array([list(b) + [tr, lb] for b, tr, lb in zip(res["boxes"], res["tracks"], res["labels"])], dtype=np.int64).reshape(-1, 6))
+    return frames, det, cnt, kept, ref
+
+
+@pytest.fixture(scope="module")
+def eng():
+    e = E.Engine(synth_yolo("yolov5s", nc=NC, seed=1702, det_scale=4.0, obj_shift=-2.0), synth_reid(1702), precision="f32", num_classes=NC,
+                 img_size=W, max_batch=B, max_frame_hw=(H, W), max_crops=B * len(BOXES), max_tracks=256, nn_budget_cap=60)
+    yield e
+    e.close()
+
+
+@pytest.fixture(scope="module")
+def dev(case):
+    import torch
+    return torch.from_numpy(case[0]).cuda()
+
+
+def fresh(eng, on, **kw):
+    """A clean stream (counters zeroed, remembered filter forgotten), the option set, one new tracker per class."""
+    eng.stream_reset()
+    eng.set_option("embed_kept_only", on)
+    return [eng.tracker_create(**dict(TRACK_KW, **kw)) for _ in range(NC)]
+
+
+def release(eng, *tid_lists):
+    eng.stream_inject(None)
+    eng.set_option("embed_kept_only", 1)
+    for tids in tid_lists:
+        for t in tids:
+            eng.tracker_destroy(t)
+
+
+def stream_rows(eng, tids_of_batch, dev, det, cnt, n_batches, settle=False):
+    """submit(i + 1); run_async(i); collect(i - 1) over the first n_batches batches -- the loop of tests/test_gpu_round3.py::stream_rows
+    with the trackers chosen per batch.  settle: collect(i - 1) comes BEFORE run_async(i) and waits for the GPU first, so that the
+    collect call certainly finds batch i's detector finished and embeds batch i THEN, under the filter of run_async(i - 1)."""
+    import torch
+    out = [None] * (n_batches * B)
+
+    def submit(n):
+        eng.stream_inject(det[n * B:(n + 1) * B], cnt[n * B:(n + 1) * B])
+        eng.stream_submit(dev[n * B:(n + 1) * B].data_ptr(), B, H, W)
+
+    def collect(n):
+        if settle:
+            torch.cuda.synchronize()
+        rows, fidx, nd = eng.stream_collect()
+        assert nd.tolist() == cnt[n * B:(n + 1) * B].tolist()          # detections per frame count EVERY box
+        for f in range(B):
+            out[n * B + f] = rows[fidx == f]
+
+    try:
+        submit(0)
+        for n in range(n_batches):
+            if n + 1 < n_batches:
+                submit(n + 1)
+            if settle and n > 0:
+                collect(n - 1)
+            eng.stream_run_async(tids_of_batch[n], dev[n * B:(n + 1) * B].data_ptr(), B, H, W, cap_rows=64)
+            if not settle and n > 0:
+                collect(n - 1)
+        collect(n_batches - 1)
+    except Exception:
+        eng.stream_reset()
+        raise
+    return out
+
+
+def assert_same_rows(a, b):
+    assert len(a) == len(b)
+    for f, (x, y) in enumerate(zip(a, b)):
+        np.testing.assert_array_equal(x, y, err_msg=f"frame {f}")
+
+
+def test_scene_drops_what_it_says(case):
+    """CPU part of the set-up: in every frame fewer boxes are kept than detected, and each of the three dropped cases really drops."""
+    _, det, cnt, kept, _ = case
+    for f in range(T):
+        assert len(kept[f]) < cnt[f]
+        assert set(range(len(BOXES))) - set(kept[f]) == DROPPED, (f, kept[f])
+        assert len(kept[f]) == KEPT_PER_FRAME
+
+
+def test_rows_do_not_depend_on_the_option_and_match_the_oracle(eng, case, dev):
+    _, det, cnt, kept, ref = case
+    got, stats = {}, {}
+    for on in (1, 0):
+        tids = fresh(eng, on)
+        got[on] = stream_rows(eng, [tids] * 3, dev, det, cnt, 3)
+        stats[on] = eng.stream_crop_stats()
+        release(eng, tids)
+    print("crop stats (boxes, crops): on", stats[1], "off", stats[0])
+    assert_same_rows(got[1], got[0])
+    assert_same_rows(got[1], ref)
+    assert sum(len(r) for r in ref) >= (T - 3) * KEPT_PER_FRAME            # tracks are confirmed from their third frame on
+    assert stats[0] == (int(cnt.sum()), int(cnt.sum()))
+    assert stats[1] == (int(cnt.sum()), sum(len(k) for k in kept))
+
+
+def test_a_batch_embedded_under_another_filter_is_embedded_again(eng, case, dev):
+    """Batch 2 is embedded by the look-ahead under batch 1's filter (NMS_MAX_OVERLAP 0.5) and then run with trackers of 1.0, which keep
+    the nested box and both boxes of the tied pair: every box of batch 2 must be embedded again."""
+    _, det, cnt, kept, _ = case
+    got, stats = {}, {}
+    for on in (1, 0):
+        t05 = fresh(eng, on)
+        t10 = [eng.tracker_create(**dict(TRACK_KW, nms_max_overlap=1.0)) for _ in range(NC)]
+        got[on] = stream_rows(eng, [t05, t10], dev, det, cnt, 2, settle=True)
+        stats[on] = eng.stream_crop_stats()
+        release(eng, t05, t10)
+    print("crop stats (boxes, crops): on", stats[1], "off", stats[0])
+    assert_same_rows(got[1], got[0])
+    boxes = int(cnt[:2 * B].sum())
+    assert stats[0] == (boxes, boxes)
+    assert stats[1] == (boxes, sum(len(k) for k in kept[:2 * B]) + int(cnt[B:2 * B].sum()))   # batch 1 kept + batch 2 kept + batch 2 in full
+
+
+def device_floats(ptr, n):
+    import torch
+
+    class Span:
+        __cuda_array_interface__ = {"shape": (n,), "typestr": "<f4", "data": (ptr, False), "version": 2}
+    return torch.as_tensor(Span(), device="cuda").cpu().numpy().copy()
+
+
+def test_stream_embed_returns_every_box_after_a_filtered_look_ahead(eng, case, dev):
+    _, det, cnt, kept, _ = case
+    got = {}
+    for on in (1, 0):
+        tids = fresh(eng, on)
+        import torch
+        for n in (0, 1):
+            eng.stream_inject(det[n * B:(n + 1) * B], cnt[n * B:(n + 1) * B])
+            eng.stream_submit(dev[n * B:(n + 1) * B].data_ptr(), B, H, W)
+        eng.stream_run_async(tids, dev[:B].data_ptr(), B, H, W, cap_rows=64)
+        torch.cuda.synchronize()
+        eng.stream_collect()                                               # finds batch 2's detector finished: embeds it under tids' filter
+        before = eng.stream_crop_stats()
+        rows7, feat = eng.stream_embed(dev[B:2 * B].data_ptr(), B, H, W)
+        got[on] = (rows7, device_floats(feat, len(rows7) * 512).reshape(-1, 512), before, eng.stream_crop_stats())
+        release(eng, tids)
+    n_all, n_kept = int(cnt[:2 * B].sum()), sum(len(k) for k in kept[:2 * B])
+    assert got[1][2] == (n_all, n_kept) and got[1][3] == (n_all, n_kept + int(cnt[B:2 * B].sum()))     # filtered first, then in full
+    assert got[0][2] == got[0][3] == (n_all, n_all)
+    assert len(got[1][0]) == int(cnt[B:2 * B].sum())
+    np.testing.assert_array_equal(got[1][0], got[0][0])
+    np.testing.assert_array_equal(got[1][1], got[0][1])
+    np.testing.assert_allclose(np.linalg.norm(got[1][1], axis=1), 1.0, atol=1e-5)
+
+
+def test_blocking_videotracker_run(eng, case):
+    frames, det, cnt, kept, _ = case
+    got, stats = {}, {}
+    for on in (1, 0):
+        tids = fresh(eng, on)
+        got[on] = []
+        for f in range(T):
+            m = oy.marshal_like_reference(det[f])
+            got[on].append(eng.videotracker_run(tids, frames[f], m["bboxes"], m["classes"], m["scores"]))
+        stats[on] = eng.stream_crop_stats()
+        release(eng, tids)
+    assert_same_rows(got[1], got[0])
+    assert sum(len(r) for r in got[1]) >= (T - 3) * KEPT_PER_FRAME
+    assert stats[0] == (int(cnt.sum()), int(cnt.sum()))
+    assert stats[1] == (int(cnt.sum()), sum(len(k) for k in kept))
+
+
+def test_first_batch_is_filtered_through_its_own_trackers(eng, case, dev):
+    """No tracker has been handed in before this vc_stream_run: the call that issues the ReID itself uses its own trackers' filter."""
+    _, det, cnt, kept, _ = case
+    got, stats = {}, {}
+    for on in (1, 0):
+        tids = fresh(eng, on)
+        eng.stream_inject(det[:B], cnt[:B])
+        rows, nd = eng.stream_run(tids, dev[:B].data_ptr(), B, H, W, cap_rows=64)
+        got[on] = rows
+        stats[on] = eng.stream_crop_stats()
+        assert nd.tolist() == cnt[:B].tolist()
+        release(eng, tids)
+    assert_same_rows(got[1], got[0])
+    assert stats[0] == (int(cnt[:B].sum()), int(cnt[:B].sum()))
+    assert stats[1] == (int(cnt[:B].sum()), sum(len(k) for k in kept[:B]))

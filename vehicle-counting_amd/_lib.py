@@ -117,6 +117,7 @@ SIGNATURES = {
     "vc_stream_collect": [_vp, _pl, _i, _pi, _pi, _i],
     "vc_stream_run_async_multi": [_vp, _pi, _i, _i, _pi, _vp, _i, _i, _i, _i],
     "vc_stream_reset": [_vp],
+    "vc_stream_crop_stats": [_vp, _P(C.c_int64), _P(C.c_int64)],
     "vc_stream_embed": [_vp, _vp, _i, _i, _i, _pd, _i, _pi, _P(_vp)],
     "vc_allgather_rows": [_vp, _pd, _vp, _i, _pd, _i, _pi, _P(_vp)],
     "vc_videotracker_run_features": [_vp, _pi, _i, _pd, _vp, _i, _i, _i, _pl, _i, _pi, _pl, _i, _pi],

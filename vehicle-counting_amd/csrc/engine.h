@@ -119,6 +119,10 @@ struct YuvGeom {
 
 }  // namespace vc
 
+namespace vc {
+struct Prepared { std::vector<double> tlwh, conf; std::vector<int> feat_rows; };   // filtered + NMS'ed detections of one tracker (tracker.hip)
+}
+
 struct vc_render;
 
 struct vc_engine {
@@ -137,7 +141,7 @@ struct vc_engine {
     bool finalized = false;
     // kernel-selection switches: read from the environment ONCE at engine creation (VC_C3_FUSED, VC_BNECK_FUSED, VC_FRONT_FUSED,
     // VC_CROP_PER_PIXEL, VC_DOT_ARENA_MB), changed afterwards only through vc_engine_set_option -- nothing on the launch path calls getenv per launch
-    struct Options { int c3_fused = 1, bneck_fused = 1, bneck_cv3 = 1, front_fused = 1, crop_per_pixel = 0, sparse_head = 1, ff_ablate = 0, c3_ablate = 0, reid_block_fused = 1, head_side = 1, fuse_upsample = 1, sppf_sep = 1, fuse_s2_pw = 1; } opt;
+    struct Options { int c3_fused = 1, bneck_fused = 1, bneck_cv3 = 1, front_fused = 1, crop_per_pixel = 0, sparse_head = 1, ff_ablate = 0, c3_ablate = 0, reid_block_fused = 1, head_side = 1, fuse_upsample = 1, sppf_sep = 1, fuse_s2_pw = 1, embed_kept_only = 1; } opt;
     std::vector<void*> allocs;       // everything hipMalloc'ed, freed on destroy
     std::vector<void*> host_allocs;  // hipHostMalloc'ed
 
@@ -198,13 +202,23 @@ struct vc_engine {
     unsigned reid_seq = 0;
     std::vector<int> crop_scratch;               // crop list of the batch being validated (stream.hip::issue_reid)
     struct FrameDets { std::vector<double> xyxy, conf; std::vector<int> label; };
+    // DeepSort.update's own detection filter (deep_sort.py:31-37): the two tracker parameters prepare_dets reads.  `stream_flt` is the
+    // one every tracker of the most recent vc_stream_run_async* call agreed on (valid = false: no such call yet, or they disagreed)
+    struct EmbedFilter { bool valid = false; double min_confidence = 0, nms_max_overlap = 0; };
+    EmbedFilter stream_flt;
+    long long boxes_detected = 0, crops_embedded = 0;   // running totals of the stream and blocking paths (vc_stream_crop_stats)
     struct Pending {
         const void* frames; int b, h, w, slot;
         int stage = 0;                   // 0: detector enqueued, 1: ReID enqueued as well
         bool embed_refused = false;      // a look-ahead attempt to embed this batch failed; the call that consumes it reports why (stream.hip)
         int fslot = 0;                   // feature / crop buffer of this batch
         std::vector<FrameDets> fd;       // per frame, as VideoTracker.run sees them
-        std::vector<int> row0;           // first feature row of each frame
+        std::vector<int> row0;           // first feature row of each frame when every box is embedded
+        // embed_kept_only: the batch was embedded under `flt` -- only the boxes prepare_dets keeps own a feature row, and prep[f] holds
+        // frame f's prepare_dets results per label (ascending), feat_rows indexing those compact rows (stream.hip::issue_reid)
+        bool filtered = false;
+        EmbedFilter flt;
+        std::vector<std::vector<std::pair<int, vc::Prepared>>> prep;
         std::vector<float> inj_det; std::vector<int> inj_cnt; int inj_b = 0, inj_n = 0;   // detection injection captured at submit time
     };
     std::vector<Pending> pending;
@@ -331,8 +345,8 @@ struct ProfScope {
 };
 // tracker.hip
 int tracker_init_pool(vc_engine* e);
-struct Prepared { std::vector<double> tlwh, conf; std::vector<int> feat_rows; };   // filtered + NMS'ed detections of one tracker
 void prepare_dets(const double* xyxy, const double* conf, const int* rows, int k, const vc_tracker_params& p, Prepared& out);
+void prepare_dets(const double* xyxy, const double* conf, const int* rows, int k, double min_confidence, double nms_max_overlap, Prepared& out);
 void dsort_nms(const double* tlwh, const double* scores, int n, double max_overlap, std::vector<int>& keep);
 // Build + enqueue one tracker batch on the tracker stream (after `wait`, if given, has fired on the GPU).  frame_groups[f] lists
 // (class label, tracker id, prepared detections) of frame f in class order.  Rows land in stage `st`; track_collect waits for them.

@@ -183,6 +183,7 @@ int vc_engine_create(const vc_engine_config* cfg, vc_engine** out) {
         e->opt.c3_fused = env_int("VC_C3_FUSED", 1); e->opt.bneck_fused = env_int("VC_BNECK_FUSED", 1); e->opt.bneck_cv3 = env_int("VC_BNECK_CV3", 1);
         e->opt.front_fused = env_int("VC_FRONT_FUSED", 1); e->opt.crop_per_pixel = getenv("VC_CROP_PER_PIXEL") ? 1 : 0;
         e->opt.sparse_head = env_int("VC_SPARSE_HEAD", 1); e->opt.reid_block_fused = env_int("VC_REID_BLOCK_FUSED", 1); e->opt.head_side = env_int("VC_HEAD_SIDE", 1); e->opt.fuse_upsample = env_int("VC_FUSE_UPSAMPLE", 1); e->opt.sppf_sep = env_int("VC_SPPF_SEP", 1); e->opt.fuse_s2_pw = env_int("VC_FUSE_S2PW", 1);
+        e->opt.embed_kept_only = env_int("VC_EMBED_KEPT_ONLY", 1);
     }
     memcpy(e->anchors, kAnchors, sizeof(kAnchors));
     int st = VC_OK;
@@ -364,6 +365,7 @@ int vc_engine_finalize(vc_engine* e) {
 int vc_engine_set_option(vc_engine* e, const char* name, int value) {
     VC_CHECK(e && name, VC_ERR_ARG, "null argument");
     const std::string n = name;
+    if (n == "embed_kept_only") { e->opt.embed_kept_only = value; return VC_OK; }     // host-side choice of what is embedded: no kernel selection changes
     if (n == "c3_fused") e->opt.c3_fused = value;
     else if (n == "bneck_fused") e->opt.bneck_fused = value;
     else if (n == "bneck_cv3") e->opt.bneck_cv3 = value;

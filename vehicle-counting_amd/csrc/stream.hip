@@ -4,6 +4,7 @@
 // one batched tracker step over the classes that have boxes (modules/track.py:50-59).
 #include <algorithm>
 #include <cmath>
+#include <map>
 #include <numeric>
 
 #include <chrono>
@@ -160,27 +161,12 @@ int vc_stream_submit_host(vc_engine* e, const uint8_t* frames_host, int b, int h
 
 namespace {
 
-// Second pipeline stage of a submission whose detector has finished: marshal the detections like networks/yolo.py:72-97,
-// cut the crops of every box of the batch (deep_sort.py:89-95,119-129) and enqueue the ReID net on its own stream.
-int issue_reid(vc_engine* e, vc_engine::Pending& pd) {
-    const int md = e->cfg.max_det, b = pd.b, h = pd.h, w = pd.w;
-    const float* h_det = e->h_det2[pd.slot];
-    const int* h_cnt = e->h_det_count2[pd.slot];
-    pd.fd.assign(b, FrameDets{});
-    pd.row0.assign(b, 0);
-    for (int f = 0; f < b; ++f) {
-        VC_CHECK(h_cnt[f] >= 0 || pd.inj_b > 0, VC_ERR_CAPACITY, "frame %d: more than max_candidates (%d) boxes passed conf_thres; raise vc_engine_config.max_candidates", f,
-                 e->cfg.max_candidates);
-        if (pd.inj_b > 0) {
-            const int fi = f % pd.inj_b;
-            marshal(pd.inj_det.data() + (size_t)fi * pd.inj_n * 6, pd.inj_cnt[fi], pd.fd[f]);
-        } else {
-            marshal(h_det + (size_t)f * md * 6, h_cnt[f], pd.fd[f]);
-        }
-    }
-    // every check comes before a feature / crop slot is taken: a refused batch leaves the three-buffer rotation untouched
-    std::vector<int>& crops = e->crop_scratch;
+// The crop of every box of the batch, in (frame, box) order (deep_sort.py:78-95), with the checks that refuse a batch: more boxes than
+// max_crops, an empty crop.  Both count ALL boxes, whatever is embedded afterwards.  pd.row0[f] = first row of frame f in that list.
+int all_crops(vc_engine* e, vc_engine::Pending& pd, std::vector<int>& crops) {
+    const int b = pd.b, h = pd.h, w = pd.w;
     crops.clear();
+    pd.row0.assign(b, 0);
     int k = 0;
     for (int f = 0; f < b; ++f) {
         pd.row0[f] = k;
@@ -201,23 +187,110 @@ int issue_reid(vc_engine* e, vc_engine::Pending& pd) {
             ++k;
         }
     }
-    pd.fslot = (int)(e->reid_seq++ % 3);
+    return VC_OK;
+}
+
+// Upload k crops and enqueue the ReID net for them on the ReID stream, into the batch's feature slot; ev_reid marks its end.
+int enqueue_reid(vc_engine* e, vc_engine::Pending& pd, const int* crops, int k) {
     int* hc = e->h_crops2[pd.fslot];
     if (k > 0) {
-        memcpy(hc, crops.data(), (size_t)k * 5 * sizeof(int));
+        memcpy(hc, crops, (size_t)k * 5 * sizeof(int));
         VC_HIP(hipMemcpyAsync(e->d_crops2[pd.fslot], hc, (size_t)k * 5 * sizeof(int), hipMemcpyHostToDevice, e->rstream));
-        VC_TRY(run_reid_on(e, (const uint8_t*)pd.frames, h, w, k, e->d_crops2[pd.fslot], e->d_feat2[pd.fslot], e->rstream));
+        VC_TRY(run_reid_on(e, (const uint8_t*)pd.frames, pd.h, pd.w, k, e->d_crops2[pd.fslot], e->d_feat2[pd.fslot], e->rstream));
     }
     VC_HIP(hipEventRecord(e->ev_reid[pd.fslot], e->rstream));
+    e->crops_embedded += k;
+    return VC_OK;
+}
+
+// Second pipeline stage of a submission whose detector has finished: marshal the detections like networks/yolo.py:72-97,
+// cut the crops (deep_sort.py:89-95,119-129) and enqueue the ReID net on its own stream.
+// The reference embeds every box and only then, inside DeepSort.update, drops the boxes with conf <= min_confidence and those its own
+// NMS suppresses (deep_sort.py:31-37, per class): a dropped box never becomes a Detection, so its feature row is never read by the cost
+// matrices, the galleries or the output (Q5).  That filter (prepare_dets) reads the boxes, the confidences and two tracker parameters,
+// no tracker state -- so with the engine option embed_kept_only and a filter `flt` (the parameters every tracker of the stream agrees
+// on) it runs HERE, per (frame, label), and only the kept boxes are cropped and embedded: they get consecutive feature rows in (frame,
+// box) order, and the prepare_dets results, their feat_rows pointing at those rows, stay in pd.prep for enqueue_batch_tracking.
+int issue_reid(vc_engine* e, vc_engine::Pending& pd, const vc_engine::EmbedFilter& flt) {
+    const int md = e->cfg.max_det, b = pd.b;
+    const float* h_det = e->h_det2[pd.slot];
+    const int* h_cnt = e->h_det_count2[pd.slot];
+    pd.fd.assign(b, FrameDets{});
+    for (int f = 0; f < b; ++f) {
+        VC_CHECK(h_cnt[f] >= 0 || pd.inj_b > 0, VC_ERR_CAPACITY, "frame %d: more than max_candidates (%d) boxes passed conf_thres; raise vc_engine_config.max_candidates", f,
+                 e->cfg.max_candidates);
+        if (pd.inj_b > 0) {
+            const int fi = f % pd.inj_b;
+            marshal(pd.inj_det.data() + (size_t)fi * pd.inj_n * 6, pd.inj_cnt[fi], pd.fd[f]);
+        } else {
+            marshal(h_det + (size_t)f * md * 6, h_cnt[f], pd.fd[f]);
+        }
+    }
+    // every check comes before a feature / crop slot is taken: a refused batch leaves the three-buffer rotation untouched
+    std::vector<int>& crops = e->crop_scratch;
+    VC_TRY(all_crops(e, pd, crops));
+    int k = (int)(crops.size() / 5);
+    e->boxes_detected += k;
+    pd.filtered = e->opt.embed_kept_only != 0 && flt.valid;
+    pd.flt = flt;
+    pd.prep.clear();
+    if (pd.filtered) {
+        pd.prep.resize(b);
+        std::map<int, std::vector<int>> by_label;
+        std::vector<int> row_of;
+        std::vector<double> bx, cf;
+        int kept = 0;
+        for (int f = 0; f < b; ++f) {
+            const FrameDets& d = pd.fd[f];
+            const int nf = (int)d.conf.size();
+            by_label.clear();
+            for (int i = 0; i < nf; ++i) by_label[d.label[i]].push_back(i);
+            row_of.assign(nf, -1);
+            for (auto& lg : by_label) {
+                const std::vector<int>& g = lg.second;
+                bx.resize(g.size() * 4); cf.resize(g.size());
+                for (size_t i = 0; i < g.size(); ++i) {
+                    memcpy(&bx[i * 4], &d.xyxy[(size_t)g[i] * 4], 4 * sizeof(double));
+                    cf[i] = d.conf[g[i]];
+                }
+                pd.prep[f].emplace_back(lg.first, Prepared{});
+                Prepared& pr = pd.prep[f].back().second;
+                prepare_dets(bx.data(), cf.data(), g.data(), (int)g.size(), flt.min_confidence, flt.nms_max_overlap, pr);   // feat_rows: box index in the frame
+                for (int r : pr.feat_rows) row_of[r] = 0;
+            }
+            for (int i = 0; i < nf; ++i)
+                if (row_of[i] == 0) {
+                    memmove(&crops[(size_t)kept * 5], &crops[(size_t)(pd.row0[f] + i) * 5], 5 * sizeof(int));
+                    row_of[i] = kept++;
+                }
+            for (auto& lp : pd.prep[f])
+                for (int& r : lp.second.feat_rows) r = row_of[r];
+        }
+        k = kept;
+    }
+    pd.fslot = (int)(e->reid_seq++ % 3);
+    VC_TRY(enqueue_reid(e, pd, crops.data(), k));
     pd.stage = 1;
     return VC_OK;
+}
+
+// A batch that was embedded under a filter its consumer does not share (other tracker parameters than the remembered ones, or
+// vc_stream_embed, which hands out every box's features): embed it again, every box, into the same feature slot.  The ReID stream
+// runs it behind the first pass; the wait keeps the first pass's crop upload from reading the pinned list while it is rewritten.
+int reembed_unfiltered(vc_engine* e, vc_engine::Pending& pd) {
+    VC_HIP(hipEventSynchronize(e->ev_reid[pd.fslot]));
+    std::vector<int>& crops = e->crop_scratch;
+    VC_TRY(all_crops(e, pd, crops));
+    pd.filtered = false;
+    pd.prep.clear();
+    return enqueue_reid(e, pd, crops.data(), (int)(crops.size() / 5));
 }
 
 // A submission whose detections cannot be embedded (candidate overflow, more boxes than max_crops, an empty crop) is DROPPED: the
 // error is reported once, by the call that CONSUMES that submission (vc_stream_run* / vc_stream_embed for its frames), and the stream
 // continues with the next one (it used to stay at the front of the queue and fail every following call).
 int issue_reid_or_drop(vc_engine* e, size_t idx) {
-    const int st = issue_reid(e, e->pending[idx]);
+    const int st = issue_reid(e, e->pending[idx], e->stream_flt);
     if (st != VC_OK) e->pending.erase(e->pending.begin() + idx);
     return st;
 }
@@ -228,6 +301,8 @@ int issue_reid_or_drop(vc_engine* e, size_t idx) {
 // submission that cannot be embedded stays queued at stage 0 with `embed_refused` set; take_front runs the same checks again when the
 // caller asks for THAT batch, reports the error there and drops it.  issue_reid checks everything before it takes a feature / crop
 // slot, so the refused attempt leaves no state behind.
+// The trackers of the look-ahead batch have not been handed in yet: it is embedded under the filter REMEMBERED from the most recent
+// vc_stream_run_async* call (e->stream_flt); enqueue_batch_tracking checks that against the trackers the batch really gets.
 void try_issue_next(vc_engine* e) {
     int next = -1;
     int embedded = 0;                                   // batches that own one of the three feature buffers
@@ -239,7 +314,7 @@ void try_issue_next(vc_engine* e) {
     embedded += (int)e->jobs.size();
     if (embedded >= 3) return;
     if (hipEventQuery(e->ev_det[e->pending[next].slot]) != hipSuccess) return;
-    if (issue_reid(e, e->pending[next]) != VC_OK) e->pending[next].embed_refused = true;
+    if (issue_reid(e, e->pending[next], e->stream_flt) != VC_OK) e->pending[next].embed_refused = true;
 }
 
 }  // namespace
@@ -258,15 +333,43 @@ static int enqueue_batch_tracking(vc_engine* e, vc_engine::Pending& pd, const in
                                   int stage, int cap_rows_per_frame, std::vector<int>& ndet) {
     const int b = pd.b;
     ndet.assign(b, 0);
+    for (int f = 0; f < b; ++f) {
+        const int cam = cam_of_frame ? cam_of_frame[f] : 0;
+        VC_CHECK(cam >= 0 && cam < n_cam, VC_ERR_ARG, "frame %d: camera index %d outside [0, %d)", f, cam, n_cam);
+    }
+    if (pd.filtered) {
+        // the remembered filter is never trusted: every tracker the batch uses must have the parameters it was embedded under
+        bool same = true;
+        for (int f = 0; f < b && same; ++f) {
+            const int* trackers = all_trackers + (size_t)(cam_of_frame ? cam_of_frame[f] : 0) * num_classes;
+            for (const auto& lp : pd.prep[f]) {
+                if (lp.first < 0 || lp.first >= num_classes) continue;
+                const int ts = tracker_slot(e->trackers, trackers[lp.first]);
+                if (ts < 0) continue;                                                    // refused below, as before
+                const vc_tracker_params& p = e->trackers[ts]->p;
+                if (p.min_confidence != pd.flt.min_confidence || p.nms_max_overlap != pd.flt.nms_max_overlap) { same = false; break; }
+            }
+        }
+        if (!same) VC_TRY(reembed_unfiltered(e, pd));
+    }
     std::vector<std::vector<FrameClassDets>> frames(b);
     std::vector<std::vector<int>> by_class(num_classes);
     for (int f = 0; f < b; ++f) {
         const int cam = cam_of_frame ? cam_of_frame[f] : 0;
-        VC_CHECK(cam >= 0 && cam < n_cam, VC_ERR_ARG, "frame %d: camera index %d outside [0, %d)", f, cam, n_cam);
         const int* trackers = all_trackers + (size_t)cam * num_classes;
         FrameDets& d = pd.fd[f];
         ndet[f] = (int)d.conf.size();
         if (d.conf.empty()) continue;                                                // Q1
+        if (pd.filtered) {                                                           // prepared before the crops were cut (issue_reid)
+            for (auto& lp : pd.prep[f]) {
+                const int c = lp.first;
+                if (c < 0 || c >= num_classes) continue;
+                const int ts = tracker_slot(e->trackers, trackers[c]);
+                VC_CHECK(ts >= 0, VC_ERR_NOTFOUND, "bad or stale tracker handle %d for class %d", trackers[c], c);
+                frames[f].push_back(FrameClassDets{c, ts, std::move(lp.second)});
+            }
+            continue;
+        }
         for (size_t i = 0; i < d.label.size(); ++i)
             if (d.label[i] >= 0 && d.label[i] < num_classes) by_class[d.label[i]].push_back((int)i);
         for (int c = 0; c < num_classes; ++c) {
@@ -336,6 +439,19 @@ int vc_stream_run_async_multi(vc_engine* e, const int* trackers, int n_cam, int 
     VC_CHECK(e->finalized && e->cfg.with_detector && e->cfg.with_reid, VC_ERR_STATE, "engine not finalized");
     VC_HIP(hipSetDevice(e->cfg.device));
     VC_CHECK(e->jobs.size() < 2, VC_ERR_STATE, "two asynchronous batches are already outstanding: call vc_stream_collect");
+    {
+        // the filter of THIS call's trackers: take_front embeds under it when it issues the ReID itself (first batch of a stream), and
+        // the look-ahead of the following batches remembers it; valid only if every tracker handed in agrees on both parameters
+        vc_engine::EmbedFilter flt;
+        for (int i = 0; i < n_cam * num_classes; ++i) {
+            const int ts = tracker_slot(e->trackers, trackers[i]);
+            if (ts < 0) { flt.valid = false; break; }
+            const vc_tracker_params& p = e->trackers[ts]->p;
+            if (i == 0) { flt.valid = true; flt.min_confidence = p.min_confidence; flt.nms_max_overlap = p.nms_max_overlap; }
+            else if (p.min_confidence != flt.min_confidence || p.nms_max_overlap != flt.nms_max_overlap) { flt.valid = false; break; }
+        }
+        e->stream_flt = flt;
+    }
     vc_engine::Pending pd;
     VC_TRY(take_front(e, frames_dev, b, h, w, pd));
     vc_engine::AsyncJob job;
@@ -377,7 +493,8 @@ int vc_stream_run(vc_engine* e, const int* trackers, int num_classes, const void
 
 // ---- one stream on several GPUs: the stateless front end shards by frame chunk over the ranks -----------------------
 // Front half of the fused path for the OLDEST submission: wait for its detector, marshal the detections like networks/yolo.py:72-97,
-// cut the crops and run the ReID net for every box (deep_sort.py:119-129, Q5), and hand back what VideoTracker.run works on: rows
+// cut the crops and run the ReID net for EVERY box (deep_sort.py:119-129, Q5: no tracker is known here, so embed_kept_only does not
+// apply and the remembered filter is forgotten), and hand back what VideoTracker.run works on: rows
 // [frame index in the batch, x1, y1, x2, y2, conf, label] (float64; a frame without boxes contributes nothing, Q1) plus the device
 // address of the matching [n][512] float32 embeddings.  The embeddings stay valid until the third following vc_stream_embed /
 // vc_stream_run* call (three feature buffers rotate).
@@ -385,8 +502,10 @@ int vc_stream_embed(vc_engine* e, const void* frames_dev, int b, int h, int w, d
     VC_CHECK(e && frames_dev && out_rows7 && out_n && out_feat_dev, VC_ERR_ARG, "null argument");
     VC_CHECK(e->finalized && e->cfg.with_detector && e->cfg.with_reid, VC_ERR_STATE, "engine not finalized");
     VC_HIP(hipSetDevice(e->cfg.device));
+    e->stream_flt = vc_engine::EmbedFilter{};             // this consumer wants every box's features: no filter from here on
     vc_engine::Pending pd;
     VC_TRY(take_front(e, frames_dev, b, h, w, pd));
+    if (pd.filtered) VC_TRY(reembed_unfiltered(e, pd));   // the look-ahead of a vc_stream_run_async* call embedded it under that call's filter
     VC_HIP(hipEventSynchronize(e->ev_reid[pd.fslot]));
     int n = 0;
     for (int f = 0; f < b; ++f) n += (int)pd.fd[f].conf.size();
@@ -469,6 +588,18 @@ int vc_stream_reset(vc_engine* e) {
     e->pending.clear();
     if (e->cstream) VC_HIP(hipStreamSynchronize(e->cstream));         // staged host batches are abandoned with the rest
     for (bool& st : e->ingest_staged) st = false;
+    e->stream_flt = vc_engine::EmbedFilter{};
+    e->boxes_detected = e->crops_embedded = 0;
+    return VC_OK;
+}
+
+// Running totals since engine creation / the last vc_stream_reset, over the stream path and the blocking tracker entry points:
+// boxes handed to the ReID stage, and crops the ReID net was really run on (fewer with embed_kept_only; a batch that had to be embedded
+// a second time counts twice).
+int vc_stream_crop_stats(vc_engine* e, int64_t* boxes_detected, int64_t* crops_embedded) {
+    VC_CHECK(e && boxes_detected && crops_embedded, VC_ERR_ARG, "null argument");
+    *boxes_detected = e->boxes_detected;
+    *crops_embedded = e->crops_embedded;
     return VC_OK;
 }
 

@@ -53,10 +53,17 @@ void dsort_nms(const double* tlwh, const double* scores, int n, double max_overl
 
 // DeepSort.update minus the embedding: confidence filter, tlwh, DeepSORT NMS -> detections in pick order
 void prepare_dets(const double* xyxy, const double* conf, const int* rows, int k, const vc_tracker_params& p, Prepared& out) {
+    prepare_dets(xyxy, conf, rows, k, p.min_confidence, p.nms_max_overlap, out);
+}
+
+// The same on the two parameters it reads: the result depends on the boxes, the confidences and these alone, never on tracker state, so
+// it can run before the crops are cut (embed_kept_only: a box dropped here never becomes a Detection, deep_sort.py:31-37, and its
+// feature row is never read)
+void prepare_dets(const double* xyxy, const double* conf, const int* rows, int k, double min_confidence, double nms_max_overlap, Prepared& out) {
     std::vector<double> tl, cf;
     std::vector<int> fr;
     for (int i = 0; i < k; ++i) {
-        if (!(conf[i] > p.min_confidence)) continue;                 // deep_sort.py:31 (features were computed for all, Q5)
+        if (!(conf[i] > min_confidence)) continue;                   // deep_sort.py:31 (the reference computed features for all, Q5)
         const double* b = xyxy + (size_t)i * 4;
         const double w = b[2] - b[0], h = b[3] - b[1];               // _xyxy_to_xywh :78-87
         const double cx = b[0] + w / 2, cy = b[1] + h / 2;
@@ -65,7 +72,7 @@ void prepare_dets(const double* xyxy, const double* conf, const int* rows, int k
         fr.push_back(rows[i]);
     }
     std::vector<int> keep;
-    dsort_nms(tl.data(), cf.data(), (int)cf.size(), p.nms_max_overlap, keep);
+    dsort_nms(tl.data(), cf.data(), (int)cf.size(), nms_max_overlap, keep);
     out.tlwh.clear(); out.conf.clear(); out.feat_rows.clear();
     for (int i : keep) {
         for (int c = 0; c < 4; ++c) out.tlwh.push_back(tl[(size_t)i * 4 + c]);
@@ -421,20 +428,22 @@ static void crop_corners_i(const double* b, int W, int H, int* c) {  // deep_sor
 
 // Shared by vc_deepsort_update / vc_videotracker_run: one frame already on the device, blocking.
 // groups: per tracker the indices (into xyxy/conf) of its boxes.  Output rows [x1,y1,x2,y2,id,label].
+// The trackers are known here, so DeepSort.update's own filter (prepare_dets: deep_sort.py:31-37) runs BEFORE the crops are cut and,
+// with the engine option embed_kept_only, only the boxes it keeps are embedded: a dropped box never becomes a Detection, so the
+// feature row the reference computes for it (Q5) is never read.  The capacity and empty-crop checks still cover every box.
 int frame_track(vc_engine* e, const uint8_t* d_frame_base, int frame_index, int H, int W, const std::vector<int>& tracker_ids,
                 const std::vector<int>& labels, const std::vector<std::vector<int>>& groups, const double* xyxy, const double* conf,
                 int n, std::vector<int64_t>& rows6) {
     VC_CHECK(n <= e->cfg.max_crops, VC_ERR_CAPACITY, "%d crops exceed max_crops %d", n, e->cfg.max_crops);
+    std::vector<int> crops((size_t)n * 5);
     for (int i = 0; i < n; ++i) {
         double c[4]; int q[4];
         xyxy_to_cxcywh(xyxy + (size_t)i * 4, c);
         crop_corners_i(c, W, H, q);
         VC_CHECK(q[2] > q[0] && q[3] > q[1], VC_ERR_ARG, "box %d gives an empty crop (the reference's cv2.resize raises here)", i);
-        int* h = e->h_crops + (size_t)i * 5;
+        int* h = &crops[(size_t)i * 5];
         h[0] = frame_index; h[1] = q[0]; h[2] = q[1]; h[3] = q[2]; h[4] = q[3];
     }
-    VC_HIP(hipMemcpyAsync(e->d_crops, e->h_crops, (size_t)n * 5 * sizeof(int), hipMemcpyHostToDevice, e->stream));
-    VC_TRY(run_reid_dev(e, d_frame_base, H, W, n));
     std::vector<std::vector<FrameClassDets>> frames(1);
     int total_tracks = 0;
     for (size_t j = 0; j < tracker_ids.size(); ++j) {
@@ -452,6 +461,23 @@ int frame_track(vc_engine* e, const uint8_t* d_frame_base, int frame_index, int 
         prepare_dets(bx.data(), cf.data(), rows.data(), (int)g.size(), e->trackers[ts]->p, fc.dets);
         total_tracks += e->trackers[ts]->known_tracks + (int)fc.dets.conf.size();
         frames[0].push_back(std::move(fc));
+    }
+    int k = n;
+    if (e->opt.embed_kept_only) {                                              // kept boxes get consecutive feature rows, in box order
+        std::vector<int> row_of(n, -1);
+        for (const FrameClassDets& fc : frames[0])
+            for (int r : fc.dets.feat_rows) row_of[r] = 0;
+        k = 0;
+        for (int i = 0; i < n; ++i)
+            if (row_of[i] == 0) { memmove(&crops[(size_t)k * 5], &crops[(size_t)i * 5], 5 * sizeof(int)); row_of[i] = k++; }
+        for (FrameClassDets& fc : frames[0])
+            for (int& r : fc.dets.feat_rows) r = row_of[r];
+    }
+    e->boxes_detected += n; e->crops_embedded += k;
+    if (k > 0) {
+        memcpy(e->h_crops, crops.data(), (size_t)k * 5 * sizeof(int));
+        VC_HIP(hipMemcpyAsync(e->d_crops, e->h_crops, (size_t)k * 5 * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        VC_TRY(run_reid_dev(e, d_frame_base, H, W, k));
     }
     const int cap = std::max(total_tracks, 16);
     VC_TRY(track_enqueue(e, 3, frames, e->d_feat, W, H, cap, nullptr));

@@ -77,13 +77,20 @@ class Engine:
         L.check(L.lib().vc_engine_sync(self._h))
 
     def set_option(self, name, value):
-        """Kernel-selection switch of the live engine ("c3_fused", "bneck_fused", "bneck_cv3", "front_fused", "sparse_head", "reid_block_fused", "crop_per_pixel", "dot_arena_mb"; diagnostics: "ff_ablate", "c3_ablate")."""
+        """Kernel-selection switch of the live engine ("c3_fused", "bneck_fused", "bneck_cv3", "front_fused", "sparse_head", "reid_block_fused", "crop_per_pixel", "dot_arena_mb"; diagnostics: "ff_ablate", "c3_ablate"), or "embed_kept_only" (1: crop and embed only the boxes DeepSort.update's own filter keeps; 0: every box)."""
         L.check(L.lib().vc_engine_set_option(self._h, name.encode(), int(value)))
 
     def stream_reset(self):
         """Abandon everything in flight on the stream path (after an error, or to replay a clip)."""
         L.check(L.lib().vc_stream_reset(self._h))
         self._async_shapes = []
+
+    def stream_crop_stats(self):
+        """(boxes that reached the ReID stage, crops the ReID net was run on): running totals of the stream path and the blocking
+        tracker calls since the engine was created or `stream_reset` was called."""
+        boxes, crops = C.c_int64(), C.c_int64()
+        L.check(L.lib().vc_stream_crop_stats(self._h, C.byref(boxes), C.byref(crops)))
+        return boxes.value, crops.value
 
     # ---------------------------------------------------------------- detect (AutoShape forward)
     def detect(self, imgs_rgb):
