@@ -333,6 +333,35 @@ int vc_render_submit(vc_render* r, const vc_render_src* src, int b, int h, int w
 /* Blocks until the OLDEST outstanding batch is complete in its `out`; VC_ERR_STATE with nothing outstanding. */
 int vc_render_collect(vc_render* r);
 
+/* ---- multi-camera ingest: one batch from per-frame sources of mixed formats ------------------------------------------------------
+ * A batch that interleaves S cameras has S decoders behind it: every frame has its own address and possibly its own pitch, format,
+ * colour matrix and memory space.  The per-frame source is the render path's struct (kind VC_SRC_*, data, desc for the YUV kinds);
+ * all frames of a batch share h x w, BGR frames are tight h * w * 3 bytes, a YUV frame is ONE frame laid out as its desc
+ * (frame_stride is not used).  Per frame the arithmetic is that of yuv_to_bgr_kernel (above); a BGR frame is a byte copy. */
+typedef vc_render_src vc_frame_src;
+/* Fills one of the four ingest slots of vc_stream_stage_host with the b frames as packed BGR (same slot rules, same VC_ERR_STATE /
+ * VC_ERR_CAPACITY refusals; may be mixed freely with the other staging calls): *frames_dev_out goes to vc_stream_submit, which waits
+ * for the slot's event, and then to vc_stream_run*.  Enqueued on the engine's copy stream: one copy per host frame (BGR straight
+ * into its place in the slot, YUV into the slot's raw buffer at its vc_frames_layout_host offset; pinned memory for the copies to
+ * overlap), one copy of the frame table, at most ONE frames_to_bgr_kernel launch whatever b and whatever the mix (none when every
+ * frame is VC_SRC_BGR_HOST), the slot's event.  Device sources must stay valid until the vc_stream_run* call of the batch has
+ * returned, host sources until its rows are collected.  Every refusal comes before a slot is taken or anything is enqueued: b < 1,
+ * a null data, an unknown kind, bad geometry in any frame, an odd h or w when any frame is YUV are VC_ERR_ARG, and the message
+ * names the frame ("frame 3: pitch_y ..."). */
+int vc_stream_stage_frames(vc_engine* e, const vc_frame_src* frames /* b */, int b, int h, int w, void** frames_dev_out);
+/* The validation of vc_stream_stage_frames and the packing of its raw buffer.  Pure host function (no GPU), like vc_gather_offsets:
+ * the CPU tests drive it directly.  raw_off[f]: for a VC_SRC_YUV_HOST frame the byte offset of its copy in the raw buffer -- a
+ * multiple of 16, ascending with f, the ranges [raw_off[f], raw_off[f] + bytes of that one frame) disjoint -- and -1 for every other
+ * kind; *raw_bytes: the end of the last range, 0 when there is none. */
+int vc_frames_layout_host(const vc_frame_src* frames, int b, int h, int w, int64_t* raw_off /* b */, size_t* raw_bytes);
+/* The same kernel outside the stream path, on the caller's own device buffers (measurement; the counterpart of vc_yuv_to_bgr_dev):
+ * frames of the DEVICE kinds only, bgr_dev: b x h x w x 3 bytes, table_dev: b * VC_FRAME_ENTRY_BYTES bytes of device memory for the
+ * frame table.  With `frames` the table is built and copied there (a blocking copy) before the launch; with frames == NULL the
+ * table is launched as the last such call left it -- repeated launches of one batch cost the kernel alone.  Enqueued on the NULL
+ * stream, returns without waiting for it. */
+#define VC_FRAME_ENTRY_BYTES 64
+int vc_frames_to_bgr_dev(const vc_frame_src* frames /* device kinds only, or NULL */, int b, int h, int w, void* bgr_dev, void* table_dev);
+
 /* Host half of vc_allgather_rows: RCCL gathers equal-sized blocks, so every rank contributes `max_rows` rows (its own counts[r] rows
  * followed by padding) and the receive buffer is rank-major [world][max_rows][row_bytes].  This compacts such a padded buffer into
  * the first sum(counts) rows of `out` in rank-major order -- for frame chunks dealt round-robin to the ranks that is frame order
@@ -391,6 +420,10 @@ int vc_lap_host(const double* cost, int nr, int nc, int* row4col_rows, int* cols
 int vc_letterbox_host(const uint8_t* rgb, int h, int w, int net_h, int net_w, int precision, float* out_nhwc3);
 /* yuv_to_bgr_kernel (the stream path's ingest conversion) on host arrays: b frames laid out as `d` says -> packed BGR b x h x w x 3 */
 int vc_yuv_to_bgr_host(const vc_yuv_desc* d, const uint8_t* yuv, int b, int h, int w, uint8_t* bgr_out);
+/* frames_to_bgr_kernel (vc_stream_stage_frames) on host arrays: b frames of the HOST kinds, each at its own address -> packed BGR
+ * b x h x w x 3.  Each frame is uploaded to a device address congruent to its host pointer mod 16, so where the caller puts a frame
+ * decides whether it takes the kernel's 16-byte path or the generic one.  Validation first: bad input is VC_ERR_ARG without a GPU too. */
+int vc_frames_to_bgr_host(const vc_frame_src* frames /* host kinds only */, int b, int h, int w, uint8_t* bgr_out);
 /* bgr_to_yuv_kernel (the render path's egress conversion) on host arrays: packed BGR b x h x w x 3 -> b frames laid out as `d` says.
  * Only plane bytes of yuv_out change. */
 int vc_bgr_to_yuv_host(const vc_yuv_desc* d, const uint8_t* bgr, int b, int h, int w, uint8_t* yuv_out);

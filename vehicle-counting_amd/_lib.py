@@ -60,6 +60,10 @@ class RenderSrc(C.Structure):
     _fields_ = [("kind", C.c_int), ("data", C.c_void_p), ("desc", YuvDesc)]
 
 
+FrameSrc = RenderSrc        # vc_frame_src: the same struct naming ONE frame (vc_stream_stage_frames)
+FRAME_ENTRY_BYTES = 64       # VC_FRAME_ENTRY_BYTES
+
+
 _P = C.POINTER
 _vp, _i, _f, _d = C.c_void_p, C.c_int, C.c_float, C.c_double
 _pf, _pd, _pi, _pl, _pu8 = _P(C.c_float), _P(C.c_double), _P(C.c_int), _P(C.c_int64), _P(C.c_uint8)
@@ -113,6 +117,10 @@ SIGNATURES = {
     "vc_render_destroy": [_vp],
     "vc_render_submit": [_vp, _P(RenderSrc), _i, _i, _i, _pi, _pi, _P(YuvDesc), _vp, _i],
     "vc_render_collect": [_vp],
+    "vc_stream_stage_frames": [_vp, _P(RenderSrc), _i, _i, _i, _P(_vp)],
+    "vc_frames_layout_host": [_P(RenderSrc), _i, _i, _i, _pl, _P(C.c_size_t)],
+    "vc_frames_to_bgr_host": [_P(RenderSrc), _i, _i, _i, _pu8],
+    "vc_frames_to_bgr_dev": [_P(RenderSrc), _i, _i, _i, _vp, _vp],
     "vc_stream_run_async": [_vp, _pi, _i, _vp, _i, _i, _i, _i],
     "vc_stream_collect": [_vp, _pl, _i, _pi, _pi, _i],
     "vc_stream_run_async_multi": [_vp, _pi, _i, _i, _pi, _vp, _i, _i, _i, _i],

@@ -194,6 +194,9 @@ struct vc_engine {
     // YUV ingest (yuv_ingest.hip): raw 4:2:0 bytes of vc_stream_stage_yuv_host, one buffer per ingest slot, allocated by its first call
     uint8_t* d_yuv_raw[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t yuv_raw_bytes[4] = {0, 0, 0, 0};
+    // frame-table ingest (yuv_ingest.hip: vc_stream_stage_frames): per slot a pinned table of max_batch entries and its device mirror, allocated by the first call
+    void* h_frame_tab[4] = {nullptr, nullptr, nullptr, nullptr};
+    void* d_frame_tab[4] = {nullptr, nullptr, nullptr, nullptr};
     // stream path: three feature / crop buffers -- the batch being tracked (tracker stream), the batch
     // whose ReID is running, and the one after it
     float* d_feat2[3] = {nullptr, nullptr, nullptr};

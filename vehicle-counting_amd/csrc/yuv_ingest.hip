@@ -144,6 +144,119 @@ __global__ __launch_bounds__(256) void yuv_to_bgr_kernel(const uint8_t* __restri
     }
 }
 
+// ---- frame table: one batch whose frames each come from their own place (S decoders' surface pools: own addresses, own pitch, format,
+// colour matrix, memory space).  One launch per batch, driven by a table in device memory with one entry per frame (256 frames do not
+// fit kernel arguments).  blockIdx.y is the frame, so the entry is workgroup-uniform and neither the format branch nor the 16-byte
+// branch diverges.  Per frame the arithmetic is yuv_to_bgr_kernel's (the same device functions, the same 16 x 2 block per lane); a BGR
+// entry is a byte copy; an entry of kind FRAME_NONE is a frame that is already in place (a host BGR frame copied straight into the slot).
+enum { FRAME_NONE = 0, FRAME_NV12 = 1, FRAME_I420 = 2, FRAME_BGR = 3 };
+struct FrameEntry {
+    const uint8_t* src;                                 // device address of the frame
+    int kind, fast;                                     // FRAME_*; fast: every address the 16-byte variant forms for THIS frame is aligned
+    int pitch_y, pitch_c;
+    unsigned long long off_c, off_v;
+    int yoff, cy, cvr, cvg, cug, cub;
+};
+static_assert(sizeof(FrameEntry) == VC_FRAME_ENTRY_BYTES, "FrameEntry is copied to the device as plain bytes");
+
+// the 16 x 2 block (row pair rp, column group cg) of one frame: the body of yuv_to_bgr_kernel with the frame's own base addresses
+template <bool NV12, bool FAST>
+__device__ __forceinline__ void frame_block(const uint8_t* __restrict__ sf, uint8_t* __restrict__ df, const YuvGeom& k, int rp, int cg) {
+    const int x0 = cg * 16;
+    const int npx = min(16, k.w - x0);                      // even; 16 on the fast path
+    const uint8_t* y0p = sf + (size_t)(2 * rp) * k.pitch_y + x0;
+    const uint8_t* y1p = y0p + k.pitch_y;
+
+    uint32_t yw[2][4], cw[4];
+    if (FAST) {
+        const uint4 a = *(const uint4*)y0p, b = *(const uint4*)y1p;
+        yw[0][0] = a.x; yw[0][1] = a.y; yw[0][2] = a.z; yw[0][3] = a.w;
+        yw[1][0] = b.x; yw[1][1] = b.y; yw[1][2] = b.z; yw[1][3] = b.w;
+        if (NV12) {
+            const uint4 c = *(const uint4*)(sf + k.off_c + (size_t)rp * k.pitch_c + x0);
+            cw[0] = c.x; cw[1] = c.y; cw[2] = c.z; cw[3] = c.w;
+        } else {
+            const uint2 u = *(const uint2*)(sf + k.off_c + (size_t)rp * k.pitch_c + (x0 >> 1));
+            const uint2 v = *(const uint2*)(sf + k.off_v + (size_t)rp * k.pitch_c + (x0 >> 1));
+            const uint32_t uu[2] = {u.x, u.y}, vv[2] = {v.x, v.y};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t us = uu[j >> 1] >> (16 * (j & 1)), vs = vv[j >> 1] >> (16 * (j & 1));
+                cw[j] = (us & 255) | ((vs & 255) << 8) | ((us & 0xff00) << 8) | ((vs & 0xff00) << 16);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int n = npx - 4 * j;                      // pixels of this group of four that exist
+            yw[0][j] = yuv_bytes4(y0p + 4 * j, n);
+            yw[1][j] = yuv_bytes4(y1p + 4 * j, n);
+            if (NV12) {
+                cw[j] = yuv_bytes4(sf + k.off_c + (size_t)rp * k.pitch_c + x0 + 4 * j, n);
+            } else {
+                const uint32_t us = yuv_bytes4(sf + k.off_c + (size_t)rp * k.pitch_c + (x0 >> 1) + 2 * j, n >> 1);
+                const uint32_t vs = yuv_bytes4(sf + k.off_v + (size_t)rp * k.pitch_c + (x0 >> 1) + 2 * j, n >> 1);
+                cw[j] = (us & 255) | ((vs & 255) << 8) | ((us & 0xff00) << 8) | ((vs & 0xff00) << 16);
+            }
+        }
+    }
+
+    YuvChroma ch[8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        ch[2 * j] = yuv_chroma(cw[j] & 255, (cw[j] >> 8) & 255, k);
+        ch[2 * j + 1] = yuv_chroma((cw[j] >> 16) & 255, cw[j] >> 24, k);
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        uint32_t o[12];
+        yuv_row16(yw[r], ch, k, o);
+        uint8_t* d = df + ((size_t)(2 * rp + r) * k.w + x0) * 3;
+        if (FAST) {
+            uint4* d4 = (uint4*)d;
+            d4[0] = make_uint4(o[0], o[1], o[2], o[3]);
+            d4[1] = make_uint4(o[4], o[5], o[6], o[7]);
+            d4[2] = make_uint4(o[8], o[9], o[10], o[11]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 48; ++i)
+                if (i < npx * 3) d[i] = (uint8_t)(o[i >> 2] >> (8 * (i & 3)));
+        }
+    }
+}
+
+// grid: x = the frame's lanes (row pair, 16-pixel column group) in blocks of 256, y = frame.  dst: frame f at dst + f * h * w * 3.
+__global__ __launch_bounds__(256) void frames_to_bgr_kernel(const FrameEntry* __restrict__ tab, uint8_t* __restrict__ dst, int h, int w, int ncg) {
+    const FrameEntry e = tab[blockIdx.y];                   // workgroup-uniform
+    if (e.kind == FRAME_NONE) return;
+    const size_t frame_bytes = (size_t)h * w * 3;
+    uint8_t* df = dst + (size_t)blockIdx.y * frame_bytes;
+    const int lid = blockIdx.x * 256 + threadIdx.x;
+    if (e.kind == FRAME_BGR) {                              // the frame's lanes stride over its bytes: <= 96 bytes each, as on the YUV side
+        const size_t step = (size_t)gridDim.x * 256;
+        if (e.fast) {
+            const uint4* s4 = (const uint4*)e.src;
+            uint4* d4 = (uint4*)df;
+            for (size_t i = lid; i < frame_bytes / 16; i += step) d4[i] = s4[i];
+        } else {
+            for (size_t i = lid; i < frame_bytes; i += step) df[i] = e.src[i];
+        }
+        return;
+    }
+    if (lid >= (h >> 1) * ncg) return;
+    const int rp = lid / ncg, cg = lid - rp * ncg;
+    YuvGeom k;
+    k.h = h; k.w = w; k.pitch_y = e.pitch_y; k.pitch_c = e.pitch_c; k.off_c = e.off_c; k.off_v = e.off_v;
+    k.yoff = e.yoff; k.cy = e.cy; k.cvr = e.cvr; k.cvg = e.cvg; k.cug = e.cug; k.cub = e.cub;
+    if (e.kind == FRAME_NV12) {
+        if (e.fast) frame_block<true, true>(e.src, df, k, rp, cg);
+        else frame_block<true, false>(e.src, df, k, rp, cg);
+    } else {
+        if (e.fast) frame_block<false, true>(e.src, df, k, rp, cg);
+        else frame_block<false, false>(e.src, df, k, rp, cg);
+    }
+}
+
 }  // namespace
 
 // Validates a descriptor for b frames of h x w and resolves its zeros.  Pure host code: runs before any HIP call.
@@ -204,6 +317,73 @@ int launch_yuv_to_bgr(const YuvGeom& g, const uint8_t* src, uint8_t* dst, int b,
     VC_HIP(hipGetLastError());
     return VC_OK;
 }
+
+namespace {
+
+// The whole validation of a frame list (pure host code, before any HIP call): every refusal names its frame.  geo[f] is resolved for
+// the YUV kinds; raw_off[f] / *raw_bytes: the packing of the YUV_HOST frames into one raw buffer (vc_frames_layout_host).
+int frames_resolve(const vc_frame_src* frames, int b, int h, int w, bool host_only, std::vector<YuvGeom>& geo, int64_t* raw_off, size_t* raw_bytes) {
+    VC_CHECK(b >= 1, VC_ERR_ARG, "bad batch of %d frames", b);
+    VC_CHECK(frames, VC_ERR_ARG, "null frame list");
+    VC_CHECK(h >= 1 && w >= 1, VC_ERR_ARG, "bad frame size %dx%d", h, w);
+    geo.assign((size_t)b, YuvGeom{});
+    size_t cur = 0;
+    for (int f = 0; f < b; ++f) {
+        const vc_frame_src& s = frames[f];
+        VC_CHECK(s.kind == VC_SRC_BGR_HOST || s.kind == VC_SRC_BGR_DEV || s.kind == VC_SRC_YUV_HOST || s.kind == VC_SRC_YUV_DEV, VC_ERR_ARG,
+                 "frame %d: unknown source kind %d (VC_SRC_*)", f, s.kind);
+        VC_CHECK(!host_only || s.kind == VC_SRC_BGR_HOST || s.kind == VC_SRC_YUV_HOST, VC_ERR_ARG, "frame %d: a device source (kind %d) where host frames are expected", f, s.kind);
+        VC_CHECK(s.data, VC_ERR_ARG, "frame %d: null data", f);
+        if (raw_off) raw_off[f] = -1;
+        if (s.kind != VC_SRC_YUV_HOST && s.kind != VC_SRC_YUV_DEV) continue;
+        vc_yuv_desc d = s.desc;
+        d.frame_stride = 0;                                 // one frame: the stride has no meaning here
+        if (yuv_resolve(&d, 1, h, w, geo[f]) != VC_OK) {
+            char msg[400];
+            snprintf(msg, sizeof(msg), "%s", last_error());
+            set_error("frame %d: %s", f, msg);
+            return VC_ERR_ARG;
+        }
+        if (s.kind == VC_SRC_YUV_HOST) {
+            cur = (cur + 15) / 16 * 16;
+            if (raw_off) raw_off[f] = (int64_t)cur;
+            cur += yuv_batch_bytes(geo[f], 1);
+        }
+    }
+    if (raw_bytes) *raw_bytes = cur;
+    return VC_OK;
+}
+
+// src / dst: the DEVICE addresses the kernel will read and write for this frame
+FrameEntry frame_entry(int src_kind, const YuvGeom& g, const uint8_t* src, const uint8_t* dst, int h, int w) {
+    FrameEntry t{};
+    t.src = src;
+    const bool ends = (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0;
+    if (src_kind == VC_SRC_BGR_HOST || src_kind == VC_SRC_BGR_DEV) {
+        t.kind = FRAME_BGR;
+        t.fast = ends && ((size_t)h * w * 3) % 16 == 0;
+        return t;
+    }
+    t.kind = g.nv12 ? FRAME_NV12 : FRAME_I420;
+    // launch_yuv_to_bgr's test with this frame's own addresses in place of the batch's base and stride
+    t.fast = g.w % 16 == 0 && g.pitch_y % 16 == 0 && g.pitch_c % 16 == 0 && g.off_c % 16 == 0 && g.off_v % 16 == 0 && ends;
+    t.pitch_y = g.pitch_y; t.pitch_c = g.pitch_c; t.off_c = g.off_c; t.off_v = g.off_v;
+    t.yoff = g.yoff; t.cy = g.cy; t.cvr = g.cvr; t.cvg = g.cvg; t.cug = g.cug; t.cub = g.cub;
+    return t;
+}
+
+// d_tab: b entries in device memory, dst: [b][h][w][3] in device memory
+int launch_frames_to_bgr(const FrameEntry* d_tab, uint8_t* dst, int b, int h, int w, hipStream_t s) {
+    const int ncg = (w + 15) / 16;
+    const long long lanes = (long long)((h + 1) / 2) * ncg;                    // of one frame
+    const long long blocks = (lanes + 255) / 256;
+    VC_CHECK(b <= 65535 && blocks <= 0x7fffffll, VC_ERR_CAPACITY, "batch too large for one conversion launch");
+    hipLaunchKernelGGL(frames_to_bgr_kernel, dim3((unsigned)blocks, (unsigned)b), dim3(256), 0, s, d_tab, dst, h, w, ncg);
+    VC_HIP(hipGetLastError());
+    return VC_OK;
+}
+
+}  // namespace
 
 }  // namespace vc
 
@@ -283,6 +463,129 @@ int vc_stream_stage_yuv_dev(vc_engine* e, const vc_yuv_desc* d, const void* yuv_
     int slot = 0;
     VC_TRY(ingest_take_slot(e, b, h, w, &slot));
     VC_TRY(launch_yuv_to_bgr(g, (const uint8_t*)yuv_dev, e->d_ingest[slot], b, e->cstream));
+    return ingest_publish(e, slot, frames_dev_out);
+}
+
+int vc_frames_layout_host(const vc_frame_src* frames, int b, int h, int w, int64_t* raw_off, size_t* raw_bytes) {
+    VC_CHECK(raw_off && raw_bytes, VC_ERR_ARG, "null argument");
+    std::vector<YuvGeom> geo;
+    return frames_resolve(frames, b, h, w, false, geo, raw_off, raw_bytes);
+}
+
+// Parity entry point of frames_to_bgr_kernel.  Every frame is uploaded to an address congruent to its host pointer mod 16, so that the
+// caller chooses the 16-byte or the generic path by where it puts the frame; the output sits between two guard blocks as above.
+int vc_frames_to_bgr_host(const vc_frame_src* frames, int b, int h, int w, uint8_t* bgr_out) {
+    VC_CHECK(bgr_out, VC_ERR_ARG, "null argument");
+    std::vector<YuvGeom> geo;
+    VC_TRY(frames_resolve(frames, b, h, w, true, geo, nullptr, nullptr));
+    const size_t frame_out = (size_t)h * w * 3, out_bytes = (size_t)b * frame_out, guard = 256;
+    std::vector<size_t> off((size_t)b), len((size_t)b);
+    size_t in_bytes = 0;
+    for (int f = 0; f < b; ++f) {
+        len[f] = frames[f].kind == VC_SRC_YUV_HOST ? yuv_batch_bytes(geo[f], 1) : frame_out;
+        off[f] = (in_bytes + 15) / 16 * 16 + (uintptr_t)frames[f].data % 16;
+        in_bytes = off[f] + len[f];
+    }
+    vc_engine tmp;
+    uint8_t *ds = nullptr, *dd = nullptr;
+    FrameEntry* dt = nullptr;
+    int st = dev_alloc(&tmp, (void**)&ds, in_bytes);
+    if (st == VC_OK) st = dev_alloc(&tmp, (void**)&dd, out_bytes + 2 * guard);
+    if (st == VC_OK) st = dev_alloc(&tmp, (void**)&dt, (size_t)b * sizeof(FrameEntry));
+    if (st == VC_OK) {
+        std::vector<FrameEntry> tab((size_t)b);
+        bool ok = hipMemset(dd, 0xA5, out_bytes + 2 * guard) == hipSuccess;
+        for (int f = 0; f < b && ok; ++f) {
+            ok = hipMemcpy(ds + off[f], frames[f].data, len[f], hipMemcpyHostToDevice) == hipSuccess;
+            tab[f] = frame_entry(frames[f].kind, geo[f], ds + off[f], dd + guard + (size_t)f * frame_out, h, w);
+        }
+        if (!ok || hipMemcpy(dt, tab.data(), (size_t)b * sizeof(FrameEntry), hipMemcpyHostToDevice) != hipSuccess) {
+            set_error("upload failed");
+            st = VC_ERR_HIP;
+        }
+    }
+    if (st == VC_OK) st = launch_frames_to_bgr(dt, dd + guard, b, h, w, nullptr);
+    if (st == VC_OK) {
+        uint8_t edge[512];
+        if (hipMemcpy(bgr_out, dd + guard, out_bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(edge, dd, guard, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(edge + guard, dd + guard + out_bytes, guard, hipMemcpyDeviceToHost) != hipSuccess) {
+            set_error("frames_to_bgr_kernel failed: %s", hipGetErrorString(hipGetLastError()));
+            st = VC_ERR_HIP;
+        }
+        for (size_t i = 0; i < 2 * guard && st == VC_OK; ++i)
+            if (edge[i] != 0xA5) { set_error("frames_to_bgr_kernel wrote outside its output (guard byte %zu)", i); st = VC_ERR_HIP; }
+    }
+    for (void* q : tmp.allocs) (void)hipFree(q);
+    tmp.allocs.clear();
+    return st;
+}
+
+// The kernel on the caller's own device buffers (measurement), null stream, no wait.  With `frames` the table is built and uploaded
+// (a blocking copy) into table_dev first; without, table_dev is launched as the last such call left it.
+int vc_frames_to_bgr_dev(const vc_frame_src* frames, int b, int h, int w, void* bgr_dev, void* table_dev) {
+    VC_CHECK(bgr_dev && table_dev, VC_ERR_ARG, "null argument");
+    VC_CHECK(b >= 1 && h >= 1 && w >= 1, VC_ERR_ARG, "bad batch of %d frames %dx%d", b, h, w);
+    if (frames) {
+        std::vector<YuvGeom> geo;
+        VC_TRY(frames_resolve(frames, b, h, w, false, geo, nullptr, nullptr));
+        std::vector<FrameEntry> tab((size_t)b);
+        for (int f = 0; f < b; ++f) {
+            VC_CHECK(frames[f].kind == VC_SRC_BGR_DEV || frames[f].kind == VC_SRC_YUV_DEV, VC_ERR_ARG, "frame %d: a host source (kind %d) where device frames are expected", f, frames[f].kind);
+            tab[f] = frame_entry(frames[f].kind, geo[f], (const uint8_t*)frames[f].data, (const uint8_t*)bgr_dev + (size_t)f * h * w * 3, h, w);
+        }
+        VC_HIP(hipMemcpy(table_dev, tab.data(), (size_t)b * sizeof(FrameEntry), hipMemcpyHostToDevice));
+    }
+    return launch_frames_to_bgr((const FrameEntry*)table_dev, (uint8_t*)bgr_dev, b, h, w, nullptr);
+}
+
+// One batch from per-frame sources.  On the copy stream: one copy per host frame (BGR straight into its place in the slot, YUV into
+// the slot's raw buffer at its vc_frames_layout_host offset), one copy of the frame table (per-slot pinned table -> per-slot device
+// table: the slot rules guarantee that the slot's previous batch, and with it the previous copy of the table, is complete), at most one
+// launch, the slot's event.
+int vc_stream_stage_frames(vc_engine* e, const vc_frame_src* frames, int b, int h, int w, void** frames_dev_out) {
+    VC_CHECK(e && frames_dev_out, VC_ERR_ARG, "null argument");
+    std::vector<YuvGeom> geo;
+    std::vector<int64_t> raw_off((size_t)std::max(b, 1));
+    size_t raw_bytes = 0;
+    VC_TRY(frames_resolve(frames, b, h, w, false, geo, raw_off.data(), &raw_bytes));
+    int slot = 0;
+    VC_TRY(ingest_take_slot(e, b, h, w, &slot));
+    if (!e->h_frame_tab[slot]) {
+        VC_TRY(host_alloc(e, &e->h_frame_tab[slot], (size_t)e->cfg.max_batch * sizeof(FrameEntry)));
+        VC_TRY(dev_alloc(e, &e->d_frame_tab[slot], (size_t)e->cfg.max_batch * sizeof(FrameEntry)));
+    }
+    if (raw_bytes > e->yuv_raw_bytes[slot]) {
+        // as in vc_stream_stage_yuv_host: everything the copy stream still has in flight reads the old buffer
+        VC_HIP(hipStreamSynchronize(e->cstream));
+        const size_t tight = (size_t)e->cfg.max_batch * e->cfg.max_frame_h * e->cfg.max_frame_w * 3 / 2;
+        e->yuv_raw_bytes[slot] = 0;
+        VC_TRY(dev_realloc(e, (void**)&e->d_yuv_raw[slot], std::max(raw_bytes, tight)));
+        e->yuv_raw_bytes[slot] = std::max(raw_bytes, tight);
+    }
+    FrameEntry* tab = (FrameEntry*)e->h_frame_tab[slot];
+    const size_t frame_out = (size_t)h * w * 3;
+    bool launch = false;
+    for (int f = 0; f < b; ++f) {
+        const vc_frame_src& s = frames[f];
+        uint8_t* dst = e->d_ingest[slot] + (size_t)f * frame_out;
+        const uint8_t* src = (const uint8_t*)s.data;
+        if (s.kind == VC_SRC_BGR_HOST) {
+            VC_HIP(hipMemcpyAsync(dst, s.data, frame_out, hipMemcpyHostToDevice, e->cstream));
+            tab[f] = FrameEntry{};                          // FRAME_NONE: already in place
+            continue;
+        }
+        if (s.kind == VC_SRC_YUV_HOST) {
+            uint8_t* raw = e->d_yuv_raw[slot] + raw_off[f];
+            VC_HIP(hipMemcpyAsync(raw, s.data, yuv_batch_bytes(geo[f], 1), hipMemcpyHostToDevice, e->cstream));
+            src = raw;
+        }
+        tab[f] = frame_entry(s.kind, geo[f], src, dst, h, w);
+        launch = true;
+    }
+    if (launch) {
+        VC_HIP(hipMemcpyAsync(e->d_frame_tab[slot], tab, (size_t)b * sizeof(FrameEntry), hipMemcpyHostToDevice, e->cstream));
+        VC_TRY(launch_frames_to_bgr((const FrameEntry*)e->d_frame_tab[slot], e->d_ingest[slot], b, h, w, e->cstream));
+    }
     return ingest_publish(e, slot, frames_dev_out);
 }
 

@@ -330,6 +330,16 @@ class Engine:
         L.check(L.lib().vc_stream_stage_yuv_dev(self._h, C.byref(d), C.c_void_p(yuv_dev_ptr), b, h, w, C.byref(out)))
         return out.value
 
+    def stream_stage_frames(self, frames, h, w):
+        """One batch from per-frame sources (`frame_src(...)` each: its own address, kind and, for YUV, descriptor -- the surfaces of
+        several decoders interleaved): host frames are copied, YUV frames converted and device BGR frames copied by ONE kernel launch
+        on the engine's copy stream, into an ingest slot under the rules of stream_stage_host.  All frames share h x w.  Returns the
+        device address of the BGR batch for stream_submit / stream_run*."""
+        out = C.c_void_p()
+        arr = _frame_array(frames)
+        L.check(L.lib().vc_stream_stage_frames(self._h, arr, len(frames), h, w, C.byref(out)))
+        return out.value
+
     # ---------------------------------------------------------------- frame-sharded front end (one stream on several GPUs)
     def stream_embed(self, frames_dev_ptr, b, h, w):
         """Front half of the fused path for the oldest submission: (rows [n, 7] float64 = frame index in the batch, x1, y1, x2, y2,
@@ -525,6 +535,47 @@ def yuv_to_bgr(yuv, b, h, w, fmt="nv12", matrix="bt601", full_range=False, *, de
             raise ValueError(f"yuv holds {src.size} bytes, the descriptor needs {need}")
     L.check(L.lib().vc_yuv_to_bgr_host(C.byref(d), L.ptr(src, C.c_uint8), b, h, w, L.ptr(out, C.c_uint8)))
     return out
+
+
+def frame_src(kind, ptr, desc=None):
+    """vc_frame_src: ONE frame of a batch for `Engine.stream_stage_frames` / `frames_to_bgr`.  kind: "bgr_host", "bgr_dev", "yuv_host"
+    or "yuv_dev"; ptr: integer address of the frame; desc (`yuv_desc(...)`, YUV kinds; None: tight NV12, BT.601 limited): the layout of
+    that one frame (frame_stride is not used).  BGR frames are tight h * w * 3 bytes."""
+    if kind not in L.RENDER_SRC_ID:
+        raise ValueError(f"unknown frame source kind {kind!r}: one of {sorted(L.RENDER_SRC_ID)}")
+    return L.FrameSrc(L.RENDER_SRC_ID[kind], ptr, desc if desc is not None else yuv_desc())
+
+
+def _frame_array(frames):
+    return (L.FrameSrc * max(len(frames), 1))(*frames)
+
+
+def frames_layout(frames, h, w):
+    """vc_frames_layout_host: validates a frame list like `Engine.stream_stage_frames` does (no GPU needed) and returns (raw_off, raw_bytes):
+    the byte offset of every "yuv_host" frame in the staging call's raw buffer (-1 for the other kinds) and the buffer's size."""
+    off, total = np.full(max(len(frames), 1), -2, np.int64), C.c_size_t(0)
+    L.check(L.lib().vc_frames_layout_host(_frame_array(frames), len(frames), h, w, L.ptr(off, C.c_int64), C.byref(total)))
+    return off[:len(frames)], total.value
+
+
+def frames_to_bgr(frames, h, w, out=None):
+    """frames_to_bgr_kernel on host arrays: `frames` = `frame_src("bgr_host" | "yuv_host", address, desc)` each -> (b, h, w, 3) BGR.  A frame
+    whose host address is a multiple of 16 (and whose geometry is) takes the kernel's 16-byte path, any other the generic one.  `out`: a
+    C-contiguous uint8 array of b * h * w * 3 elements to write into instead of a new one."""
+    b = len(frames)
+    if out is None:
+        out = np.zeros((max(b, 0), h, w, 3), np.uint8)
+    assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.size >= b * h * w * 3
+    dst = C.cast(out.ctypes.data, C.POINTER(C.c_uint8))
+    L.check(L.lib().vc_frames_to_bgr_host(_frame_array(frames), b, h, w, dst))
+    return out
+
+
+def frames_to_bgr_dev(frames, b, h, w, bgr_dev_ptr, table_dev_ptr):
+    """frames_to_bgr_kernel on the caller's device buffers (integer addresses), enqueued on the null stream; returns without waiting.
+    frames: `frame_src("bgr_dev" | "yuv_dev", ...)` each; table_dev_ptr: b * FRAME_ENTRY_BYTES bytes of device memory that receive the
+    frame table.  frames=None launches the table of the last call again (the kernel alone, for measurement)."""
+    L.check(L.lib().vc_frames_to_bgr_dev(_frame_array(frames) if frames is not None else None, b, h, w, C.c_void_p(bgr_dev_ptr), C.c_void_p(table_dev_ptr)))
 
 
 def yuv_to_bgr_dev(yuv_dev_ptr, b, h, w, bgr_dev_ptr, desc=None):

@@ -69,7 +69,9 @@ class YuvFrameSource:
     """In-memory video as a decoder delivers it: T frames of 4:2:0 YUV (`fmt` "nv12" or "i420"), `data` = uint8 array whose first axis
     is the frame (or a flat buffer of T whole frames).  Geometry in bytes, 0 = tightly packed (include/vcount_hip.h: vc_yuv_desc):
     `pitch` is the luma pitch; unless given, the chroma pitch follows it (`pitch` for nv12, `pitch // 2` for i420), the planes
-    follow each other without a gap and a frame ends with the last whole row of its last plane.  Only `CountingPipeline.run_stream` takes it: the conversion to BGR runs on the device."""
+    follow each other without a gap and a frame ends with the last whole row of its last plane.  
+    `CountingPipeline.run_stream` takes it, and so does `run_streams` (one per camera, mixed freely with BGR `FrameSource`s and with
+    YUV sources of other formats and pitches); `render` reads it as well.  The conversion to BGR runs on the device."""
 
     def __init__(self, data, h, w, fmt="nv12", matrix="bt601", full_range=False, pitch=0, pitch_c=0, offset_c=0, offset_v=0,
                  frame_stride=0, name="cam_04.mp4", fps=10):
@@ -365,12 +367,20 @@ class CountingPipeline:
                 rnd.collect()
         return sink
 
-    def run_streams(self, sources, cam_names, zone_paths, batch=16):
+    def run_streams(self, sources, cam_names, zone_paths, batch=16, host_frames=False):
         """S videos at once on ONE engine (the reference runs them one after another, each with a new VideoTracker,
         modules/__init__.py:28-36): the frames of the cameras are interleaved round-robin into batches of `batch` frames, the
         detector and the ReID net see one batch, every camera's frames are stepped on that camera's own trackers
         (`vc_stream_run_async_multi`).  Per-camera results are identical to S separate `run_stream` calls; per-camera latency is
-        batch / S frames.  All sources must share one frame size.  Returns [(rows, counts)] in camera order."""
+        batch / S frames.  All sources must share one frame size.  Returns [(rows, counts)] in camera order.
+        With BGR `FrameSource`s only and host_frames=False the interleaved clip is built on the host and uploaded once.  With any
+        `YuvFrameSource`, or host_frames=True, every camera's clip stays where a deployment has it -- its own pinned host tensor
+        (host_frames=True) or its own device tensor -- and each batch is gathered from the cameras' own addresses on the device
+        (`stream_stage_frames`, staged two batches ahead as in `run_stream`): no interleaved copy of the clips exists, cameras may
+        differ in format, colour matrix, range, pitch and length, and a video of any length needs four batches of device memory
+        when its frames stay on the host."""
+        if host_frames or any(isinstance(s, YuvFrameSource) for s in sources):
+            return self._run_streams_frames(sources, cam_names, zone_paths, batch, host_frames)
         import torch
         S = len(sources)
         shapes = {s.frames.shape[1:] for s in sources}
@@ -412,6 +422,71 @@ class CountingPipeline:
                 self.engine.stream_run_async_multi(tids, cams[f0:f0 + b], dev[f0:f0 + b].data_ptr(), b, h, w)
                 if n > 0:
                     record(starts[n - 1], *self.engine.stream_collect()[:2])
+            if starts:
+                record(starts[-1], *self.engine.stream_collect()[:2])
+        return [self._finish(st[1], o, n) for st, o, n in zip(stages, objs, cam_names)]
+
+    def _run_streams_frames(self, sources, cam_names, zone_paths, batch, host_frames):
+        """run_streams over per-camera clips: camera c frame t is read at base_c + t * stride_c with that camera's descriptor."""
+        import torch
+
+        from .engine import frame_src
+        S = len(sources)
+        yuv = [isinstance(s, YuvFrameSource) for s in sources]
+        sizes = [(s.h, s.w) if y else tuple(s.frames.shape[1:3]) for s, y in zip(sources, yuv)]
+        if len(set(sizes)) != 1:
+            raise ValueError(f"run_streams: all cameras must deliver frames of one size, got {sizes}")
+        h, w = sizes[0]
+        # each camera's clip where its decoder would leave it: one tensor per camera, never an interleaved copy
+        clips = [torch.from_numpy(s.data if y else s.frames.reshape(len(s.frames), -1)) for s, y in zip(sources, yuv)]
+        clips = [c.pin_memory() if host_frames else c.to(f"cuda:{self.engine.cfg.device}") for c in clips]
+        base, stride = [c.data_ptr() for c in clips], [c.shape[1] for c in clips]
+        kind = [("yuv" if y else "bgr") + ("_host" if host_frames else "_dev") for y in yuv]
+        desc = [s.desc if y else None for s, y in zip(sources, yuv)]
+        stages = [self._stages(n, s.video_info, z) for n, s, z in zip(cam_names, sources, zone_paths)]
+        tids = np.array([st[0].tracker_ids for st in stages], np.int32)                 # [S][num_classes]
+        order = []                                                                       # (camera, frame) round-robin, exhausted cameras drop out
+        for t in range(max(len(s) for s in sources)):
+            order.extend((c, t) for c in range(S) if t < len(sources[c]))
+        cams = np.array([c for c, _ in order], np.int32)
+        fidx = np.array([t for _, t in order], np.int64)
+        objs = [{"frames": [], "tracks": [], "labels": [], "boxes": []} for _ in range(S)]
+        starts = list(range(0, len(order), batch))
+        ptr = {}
+
+        def record(f0, rows, fb):
+            g = f0 + fb                                                                  # global position of each row's frame
+            for c in range(S):
+                sel = cams[g] == c
+                o = objs[c]
+                o["frames"].extend((fidx[g[sel]] + 1).tolist())
+                o["tracks"].extend(rows[sel, 4].tolist())
+                o["labels"].extend(rows[sel, 5].tolist())
+                o["boxes"].extend(list(rows[sel, :4].copy()))
+
+        def span(n):
+            f0 = starts[n]
+            return f0, min(batch, len(order) - f0)
+
+        def stage(n):
+            f0, b = span(n)
+            ptr[n] = self.engine.stream_stage_frames([frame_src(kind[c], base[c] + t * stride[c], desc[c]) for c, t in order[f0:f0 + b]], h, w)
+
+        with self._video(*[st[0] for st in stages]):
+            for n in range(min(2, len(starts))):            # staging order = batch order (four slots, round-robin)
+                stage(n)
+            if starts:
+                self.engine.stream_submit(ptr[0], span(0)[1], h, w)
+            for n in range(len(starts)):
+                f0, b = span(n)
+                if n + 2 < len(starts):                     # gather batch n+2 under the detector of batch n+1
+                    stage(n + 2)
+                if n + 1 < len(starts):
+                    self.engine.stream_submit(ptr[n + 1], span(n + 1)[1], h, w)
+                self.engine.stream_run_async_multi(tids, cams[f0:f0 + b], ptr[n], b, h, w)
+                if n > 0:
+                    record(starts[n - 1], *self.engine.stream_collect()[:2])
+                ptr.pop(n - 1, None)
             if starts:
                 record(starts[-1], *self.engine.stream_collect()[:2])
         return [self._finish(st[1], o, n) for st, o, n in zip(stages, objs, cam_names)]
