@@ -336,7 +336,7 @@ int vc_render_collect(vc_render* r);
 /* ---- multi-camera ingest: one batch from per-frame sources of mixed formats ------------------------------------------------------
  * A batch that interleaves S cameras has S decoders behind it: every frame has its own address and possibly its own pitch, format,
  * colour matrix and memory space.  The per-frame source is the render path's struct (kind VC_SRC_*, data, desc for the YUV kinds);
- * all frames of a batch share h x w, BGR frames are tight h * w * 3 bytes, a YUV frame is ONE frame laid out as its desc
+ * all frames of a batch share h x w (vc_stream_stage_frames_sized below lifts that), BGR frames are tight h * w * 3 bytes, a YUV frame is ONE frame laid out as its desc
  * (frame_stride is not used).  Per frame the arithmetic is that of yuv_to_bgr_kernel (above); a BGR frame is a byte copy. */
 typedef vc_render_src vc_frame_src;
 /* Fills one of the four ingest slots of vc_stream_stage_host with the b frames as packed BGR (same slot rules, same VC_ERR_STATE /
@@ -361,6 +361,37 @@ int vc_frames_layout_host(const vc_frame_src* frames, int b, int h, int w, int64
  * stream, returns without waiting for it. */
 #define VC_FRAME_ENTRY_BYTES 64
 int vc_frames_to_bgr_dev(const vc_frame_src* frames /* device kinds only, or NULL */, int b, int h, int w, void* bgr_dev, void* table_dev);
+
+/* ---- sized batches: cameras of different frame sizes in one detector batch ----------------------------------------------------------
+ * Under AutoShape a frame's network tensor depends only on its aspect ratio after the stride-32 rounding (Q8): at size 640, 1920x1080,
+ * 1280x720, 640x360, 320x180 and 640x362 all run at 384x640.  A SIZED batch is b frames with their own (h, w) whose own network shapes
+ * -- vc_autoshape_net_size of each frame alone, what the reference gives that camera at batch size 1 -- are all equal: one ingest slot,
+ * one detector pass, one ReID pass, one tracker launch, and every frame gets exactly the result of a batch of its own size.  Frames are
+ * never letterboxed to a batch-wide maximum (AutoShape's rule for a mixed list would change each camera's result).
+ * Layout in device memory: b CELLS of `cell` bytes, cell = the largest h * w * 3 of the batch rounded up to 16; frame f is tight BGR
+ * (row pitch w_f * 3) at f * cell; the rest of a cell is never read and never written.
+ * Refusals, all pure host logic before any HIP call: frames whose network shapes differ are VC_ERR_ARG, the message names the first
+ * frame that differs and both shapes ("frame 3: 480x640 runs at 480x640, frame 0 at 384x640"); YUV frames need an even h and w (BGR
+ * frames may be odd); h_f > max_frame_h, w_f > max_frame_w, b > max_batch or b * cell beyond an ingest slot are VC_ERR_CAPACITY (a slot
+ * holds max_batch frames of the configured maximum in cells).  Opt-in: every other entry point runs a uniform batch as before. */
+typedef struct vc_frame_dims { int h, w; } vc_frame_dims;
+/* The network shape AutoShape gives ONE h x w image at `img_size` (models/common.py v6.0).  Pure host function. */
+int vc_autoshape_net_size(int h, int w, int img_size, int* net_h, int* net_w);
+/* Counterpart of vc_frames_layout_host for a sized batch: all of its validation with every frame's own size, the packing of the
+ * VC_SRC_YUV_HOST frames into the raw buffer (raw_off, raw_bytes as there), the cell size and the shared network shape.  Pure host. */
+int vc_frames_layout_sized_host(const vc_frame_src* frames, const vc_frame_dims* dims, int b, int img_size,
+                                int64_t* raw_off /* b */, size_t* raw_bytes, size_t* cell, int* net_h, int* net_w);
+/* vc_stream_stage_frames for a sized batch: every slot rule and refusal of that call (no slot is taken on a refusal; mixes freely with
+ * the other staging calls); one copy per host frame, one table copy, at most ONE kernel launch, the slot's event.  *frames_dev_out
+ * addresses the cells. */
+int vc_stream_stage_frames_sized(vc_engine* e, const vc_frame_src* frames, const vc_frame_dims* dims, int b, void** frames_dev_out);
+/* vc_stream_submit / vc_stream_run_async_multi for a sized batch (a staged one, or the caller's own device buffer laid out in cells).
+ * The dims handed to submit and to run must equal those of the staged / submitted batch (VC_ERR_ARG otherwise).  All frames of one
+ * camera within a batch have one size (VC_ERR_ARG otherwise): it is the size that camera's track boxes are clamped to.  The detector
+ * runs the unfused stem behind ONE letterbox launch for the batch.  Rows are picked up with vc_stream_collect. */
+int vc_stream_submit_sized(vc_engine* e, const void* frames_dev, const vc_frame_dims* dims, int b);
+int vc_stream_run_async_multi_sized(vc_engine* e, const int* trackers /* n_cam x num_classes */, int n_cam, int num_classes, const int* cam_of_frame /* b */,
+                                    const void* frames_dev, const vc_frame_dims* dims, int b, int cap_rows_per_frame);
 
 /* Host half of vc_allgather_rows: RCCL gathers equal-sized blocks, so every rank contributes `max_rows` rows (its own counts[r] rows
  * followed by padding) and the receive buffer is rank-major [world][max_rows][row_bytes].  This compacts such a padded buffer into
@@ -424,6 +455,23 @@ int vc_yuv_to_bgr_host(const vc_yuv_desc* d, const uint8_t* yuv, int b, int h, i
  * b x h x w x 3.  Each frame is uploaded to a device address congruent to its host pointer mod 16, so where the caller puts a frame
  * decides whether it takes the kernel's 16-byte path or the generic one.  Validation first: bad input is VC_ERR_ARG without a GPU too. */
 int vc_frames_to_bgr_host(const vc_frame_src* frames /* host kinds only */, int b, int h, int w, uint8_t* bgr_out);
+/* The three per-frame-size kernels of a sized batch on host arrays.
+ * vc_frames_to_bgr_sized_host: the sized ingest kernel; frames as for vc_frames_to_bgr_host, `cells` holds b cells (cell size as
+ * vc_frames_layout_sized_host reports it), is uploaded, converted into and read back: bytes of a cell beyond its frame keep the caller's values.
+ * vc_letterbox_frames_host: letterbox_frames_kernel, ONE launch for b frames of their own sizes (frames[f]: h_f x w_f x 3 u8) into
+ * b x net_h x net_w x 3 floats; swap_rb exchanges channels 0 and 2 inside the image.
+ * vc_crop_resize_frames_host: the ReID crop kernel (fp32 instance) with the per-frame table: box i is cut from frame frame_of_box[i]
+ * and clamped to that frame's own size (deep_sort.py:89-95); out k x 50 x 50 x 3, the network input vc_embed_debug_input shows. */
+int vc_frames_to_bgr_sized_host(const vc_frame_src* frames /* host kinds only */, const vc_frame_dims* dims, int b, uint8_t* cells /* b * cell */);
+int vc_letterbox_frames_host(const uint8_t* const* frames, const vc_frame_dims* dims, int b, int net_h, int net_w, int swap_rb, int precision,
+                             float* out_nhwc3);
+int vc_crop_resize_frames_host(const uint8_t* const* bgr, const vc_frame_dims* dims, int b, const int* frame_of_box, const double* boxes_cxcywh, int k,
+                               float* out_nhwc);
+/* The letterbox kernels on the caller's own device buffers (measurement, like vc_frames_to_bgr_dev): frames_dev = b packed h x w x 3 frames,
+ * out_dev = b x net_h x net_w x 4 elements of `precision`.  mode 0: the kernels a uniform batch runs; mode 1: builds the per-frame table of
+ * these uniform frames in table_dev (b * 64 bytes of device memory, a blocking copy) and runs letterbox_frames_kernel; mode 2: that kernel
+ * with the table as the last mode-1 call left it.  Enqueued on the NULL stream, returns without waiting for it. */
+int vc_letterbox_dev(const void* frames_dev, int b, int h, int w, int net_h, int net_w, int swap_rb, int precision, void* out_dev, void* table_dev, int mode);
 /* bgr_to_yuv_kernel (the render path's egress conversion) on host arrays: packed BGR b x h x w x 3 -> b frames laid out as `d` says.
  * Only plane bytes of yuv_out change. */
 int vc_bgr_to_yuv_host(const vc_yuv_desc* d, const uint8_t* bgr, int b, int h, int w, uint8_t* yuv_out);

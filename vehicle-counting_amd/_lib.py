@@ -61,6 +61,13 @@ class RenderSrc(C.Structure):
 
 
 FrameSrc = RenderSrc        # vc_frame_src: the same struct naming ONE frame (vc_stream_stage_frames)
+
+
+class FrameDims(C.Structure):
+    """vc_frame_dims: the size of ONE frame of a sized batch."""
+    _fields_ = [("h", C.c_int), ("w", C.c_int)]
+
+
 FRAME_ENTRY_BYTES = 64       # VC_FRAME_ENTRY_BYTES
 
 
@@ -121,6 +128,15 @@ SIGNATURES = {
     "vc_frames_layout_host": [_P(RenderSrc), _i, _i, _i, _pl, _P(C.c_size_t)],
     "vc_frames_to_bgr_host": [_P(RenderSrc), _i, _i, _i, _pu8],
     "vc_frames_to_bgr_dev": [_P(RenderSrc), _i, _i, _i, _vp, _vp],
+    "vc_autoshape_net_size": [_i, _i, _i, _pi, _pi],
+    "vc_frames_layout_sized_host": [_P(RenderSrc), _P(FrameDims), _i, _i, _pl, _P(C.c_size_t), _P(C.c_size_t), _pi, _pi],
+    "vc_stream_stage_frames_sized": [_vp, _P(RenderSrc), _P(FrameDims), _i, _P(_vp)],
+    "vc_stream_submit_sized": [_vp, _vp, _P(FrameDims), _i],
+    "vc_stream_run_async_multi_sized": [_vp, _pi, _i, _i, _pi, _vp, _P(FrameDims), _i, _i],
+    "vc_frames_to_bgr_sized_host": [_P(RenderSrc), _P(FrameDims), _i, _pu8],
+    "vc_letterbox_frames_host": [_P(_vp), _P(FrameDims), _i, _i, _i, _i, _i, _pf],
+    "vc_crop_resize_frames_host": [_P(_vp), _P(FrameDims), _i, _pi, _pd, _i, _pf],
+    "vc_letterbox_dev": [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i],
     "vc_stream_run_async": [_vp, _pi, _i, _vp, _i, _i, _i, _i],
     "vc_stream_collect": [_vp, _pl, _i, _pi, _pi, _i],
     "vc_stream_run_async_multi": [_vp, _pi, _i, _i, _pi, _vp, _i, _i, _i, _i],

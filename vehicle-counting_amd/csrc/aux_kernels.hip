@@ -154,6 +154,106 @@ int launch_letterbox(const uint8_t* src, void* dst, int B, const LetterboxGeom& 
     return VC_OK;
 }
 
+// ---- sized batches: every frame its own size, one launch (include/vcount_hip.h) ------------------------------------------------------
+// blockIdx.y is the frame, so its table entry -- and with it the resize / copy branch -- is workgroup-uniform; blockIdx.x strides over
+// the frame's items.  One item = four consecutive output pixels of a row: the row's vertical taps are computed once per item and the
+// horizontal taps once per pixel (not per channel), and the item leaves as 16-byte stores (two for bf16, four for fp32).  Per frame the
+// values are those of letterbox_kernel / letterbox_copy_kernel on that frame alone: 11-bit lin_coef taps with the host-formed scales
+// (the kernel's own expression), u8 / 255 exact, RNE to bf16, 114 padding, R / B swapped inside the image only (114 is symmetric).
+template <bool F32>
+__global__ __launch_bounds__(256) void letterbox_frames_kernel(const uint8_t* __restrict__ src, const LetterboxFrame* __restrict__ tab, void* __restrict__ dst,
+                                                               int net_h, int net_w, int swap_rb) {
+    const LetterboxFrame g = tab[blockIdx.y];                              // workgroup-uniform
+    const uint8_t* im = src + g.src_off;
+    const int wq = net_w >> 2;                                             // net_w is a multiple of 32
+    const int items = net_h * wq;
+    const bool resize = !(g.unpad_h == g.src_h && g.unpad_w == g.src_w);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < items; i += gridDim.x * 256) {
+        const int y = i / wq, xq = i - y * wq;
+        const int uy = y - g.top, ux0 = xq * 4 - g.left;
+        const bool row_in = uy >= 0 && uy < g.unpad_h;
+        int pv[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) pv[k] = 114;
+        if (row_in && ux0 + 3 >= 0 && ux0 < g.unpad_w) {
+            if (!resize) {
+                const uint8_t* q0 = im + ((long long)uy * g.src_w + ux0) * 3;          // ux0 may be negative: only in-image pixels are fetched
+                if (ux0 >= 0 && ux0 + 3 < g.unpad_w && ((uintptr_t)q0 & 3) == 0) {
+                    const uint32_t w0 = ((const uint32_t*)q0)[0], w1 = ((const uint32_t*)q0)[1], w2 = ((const uint32_t*)q0)[2];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) { pv[k] = (w0 >> (8 * k)) & 255; pv[4 + k] = (w1 >> (8 * k)) & 255; pv[8 + k] = (w2 >> (8 * k)) & 255; }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int ux = ux0 + k;
+                        if (ux >= 0 && ux < g.unpad_w) {
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) pv[3 * k + c] = q0[3 * k + c];
+                        }
+                    }
+                }
+            } else {
+                int y0, y1, b0, b1;
+                lin_coef(uy, g.src_h, g.sy, y0, y1, b0, b1, false);
+                const uint8_t* r0 = im + (size_t)y0 * g.src_w * 3;
+                const uint8_t* r1 = im + (size_t)y1 * g.src_w * 3;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int ux = ux0 + k;
+                    if (ux >= 0 && ux < g.unpad_w) {
+                        int x0, x1, a0, a1;
+                        lin_coef(ux, g.src_w, g.sx, x0, x1, a0, a1, true);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            const int h0 = r0[x0 * 3 + c] * a0 + r0[x1 * 3 + c] * a1;
+                            const int h1 = r1[x0 * 3 + c] * a0 + r1[x1 * 3 + c] * a1;
+                            const int v = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
+                            pv[3 * k + c] = min(max(v, 0), 255);
+                        }
+                    }
+                }
+            }
+        }
+        float f[4][3];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int p0 = swap_rb ? pv[3 * k + 2] : pv[3 * k], p2 = swap_rb ? pv[3 * k] : pv[3 * k + 2];
+            f[k][0] = div255_exact((float)p0); f[k][1] = div255_exact((float)pv[3 * k + 1]); f[k][2] = div255_exact((float)p2);
+        }
+        const size_t o = ((size_t)blockIdx.y * net_h + y) * net_w + (size_t)xq * 4;
+        if (F32) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) ((float4*)dst)[o + k] = make_float4(f[k][0], f[k][1], f[k][2], 0.f);
+        } else {
+            uint4 t0, t1;
+            t0.x = pack2_bf16(f[0][0], f[0][1]); t0.y = pack2_bf16(f[0][2], 0.f);
+            t0.z = pack2_bf16(f[1][0], f[1][1]); t0.w = pack2_bf16(f[1][2], 0.f);
+            t1.x = pack2_bf16(f[2][0], f[2][1]); t1.y = pack2_bf16(f[2][2], 0.f);
+            t1.z = pack2_bf16(f[3][0], f[3][1]); t1.w = pack2_bf16(f[3][2], 0.f);
+            uint4* d = (uint4*)((uint2*)dst + o);
+            d[0] = t0; d[1] = t1;
+        }
+    }
+}
+
+LetterboxFrame letterbox_frame(long long src_off, const LetterboxGeom& g) {
+    LetterboxFrame t{};
+    t.src_off = src_off; t.src_h = g.src_h; t.src_w = g.src_w; t.unpad_h = g.unpad_h; t.unpad_w = g.unpad_w; t.top = g.top; t.left = g.left;
+    t.sx = 1.0 / ((double)g.unpad_w / (double)g.src_w); t.sy = 1.0 / ((double)g.unpad_h / (double)g.src_h);
+    return t;
+}
+
+int launch_letterbox_frames(const uint8_t* src, const LetterboxFrame* tab, void* dst, int B, int net_h, int net_w, int swap_rb, int prec, hipStream_t s) {
+    VC_CHECK(B >= 1 && B <= 65535 && net_h >= 1 && net_w >= 4 && net_w % 4 == 0, VC_ERR_ARG, "letterbox of %d frames into %dx%d", B, net_h, net_w);
+    const int items = net_h * (net_w / 4);
+    const int gx = std::max(1, std::min((items + 255) / 256, (256 * 8 + B - 1) / B));      // capped like grid_for: about 8 workgroups per CU over the batch
+    const dim3 grid((unsigned)gx, (unsigned)B);
+    if (prec == PREC_F32) hipLaunchKernelGGL(letterbox_frames_kernel<true>, grid, dim3(256), 0, s, src, tab, dst, net_h, net_w, swap_rb);
+    else hipLaunchKernelGGL(letterbox_frames_kernel<false>, grid, dim3(256), 0, s, src, tab, dst, net_h, net_w, swap_rb);
+    VC_HIP(hipGetLastError());
+    return VC_OK;
+}
+
 // ------------------------------------------------------------------------------------------ SPPF pooling (A6)
 // Three chained MaxPool2d(5,1,2) == max over 5x5, 9x9, 13x13 windows of x (padding behaves as -inf).
 template <bool F32>
@@ -614,8 +714,8 @@ __device__ __forceinline__ void lin_coef_f(int d, int src, double scale, int& s0
 }
 
 template <bool F32>
-__global__ __launch_bounds__(256) void crop_resize_kernel(const uint8_t* __restrict__ frames, int H, int W, const int* __restrict__ crops5,
-                                                          int k, void* __restrict__ dst, int cpad) {
+__global__ __launch_bounds__(256) void crop_resize_kernel(const uint8_t* __restrict__ frames, int H, int W0, const int* __restrict__ crops5,
+                                                          int k, void* __restrict__ dst, int cpad, const CropFrame* __restrict__ ftab) {
     constexpr int S = VC_REID_SIZE;
     const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
     const long total = (long)k * S * S;
@@ -625,7 +725,8 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(const uint8_t* __restr
         const int x1 = cr[1], y1 = cr[2], cw = cr[3] - cr[1], chh = cr[4] - cr[2];
         float out[3] = {0.f, 0.f, 0.f};
         if (cw > 0 && chh > 0) {
-            const uint8_t* im = frames + (size_t)cr[0] * H * W * 3;
+            const uint8_t* im = ftab ? frames + ftab[cr[0]].off : frames + (size_t)cr[0] * H * W0 * 3;    // a sized batch: the frame's own cell and pitch
+            const int W = ftab ? ftab[cr[0]].W : W0;
             float v[3];
             if (cw == S && chh == S) {
                 const uint8_t* q = im + ((size_t)(y1 + y) * W + x1 + x) * 3;
@@ -663,8 +764,8 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(const uint8_t* __restr
 // weights of the 50 columns and 50 rows are computed once per crop into LDS (two fp64 divisions each) instead of once per
 // output pixel, u8 / 255 is the two-instruction exact form (div255_exact, vc_common.h), a pixel leaves as one 16-byte store.
 // Bit-identical to crop_resize_kernel<false> (tests/test_gpu_nets.py::test_crop_resize_per_crop_kernel).
-__global__ __launch_bounds__(256) void crop_resize_wg_kernel(const uint8_t* __restrict__ frames, int H, int W, const int* __restrict__ crops5,
-                                                            uint4* __restrict__ dst) {
+__global__ __launch_bounds__(256) void crop_resize_wg_kernel(const uint8_t* __restrict__ frames, int H, int W0, const int* __restrict__ crops5,
+                                                            uint4* __restrict__ dst, const CropFrame* __restrict__ ftab) {
     constexpr int S = VC_REID_SIZE;
     __shared__ int tap[2][S][2];
     __shared__ float wgt[2][S][2];
@@ -685,7 +786,8 @@ __global__ __launch_bounds__(256) void crop_resize_wg_kernel(const uint8_t* __re
     }
     __syncthreads();
     const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-    const uint8_t* im = frames + ((size_t)cr[0] * H + y1) * W * 3 + (size_t)x1 * 3;
+    const int W = ftab ? ftab[cr[0]].W : W0;                           // a sized batch: the frame's own cell and pitch
+    const uint8_t* im = (ftab ? frames + ftab[cr[0]].off + (size_t)y1 * W * 3 : frames + ((size_t)cr[0] * H + y1) * W * 3) + (size_t)x1 * 3;
     const bool same = cw == S && chh == S;
     for (int i = threadIdx.x; i < S * S; i += blockDim.x) {
         const int y = i / S, x = i - y * S;
@@ -713,16 +815,17 @@ __global__ __launch_bounds__(256) void crop_resize_wg_kernel(const uint8_t* __re
     }
 }
 
-int launch_crop_resize(const uint8_t* frames, int H, int W, const int* crops5, int k, void* dst, int cpad, int prec, hipStream_t s, bool per_pixel) {
+int launch_crop_resize(const uint8_t* frames, int H, int W, const int* crops5, int k, void* dst, int cpad, int prec, hipStream_t s, bool per_pixel,
+                       const CropFrame* ftab) {
     if (k <= 0) return VC_OK;
     if (prec != PREC_F32 && cpad == 8 && !per_pixel) {
-        hipLaunchKernelGGL(crop_resize_wg_kernel, dim3(k), dim3(256), 0, s, frames, H, W, crops5, (uint4*)dst);
+        hipLaunchKernelGGL(crop_resize_wg_kernel, dim3(k), dim3(256), 0, s, frames, H, W, crops5, (uint4*)dst, ftab);
         VC_HIP(hipGetLastError());
         return VC_OK;
     }
     const long total = (long)k * VC_REID_SIZE * VC_REID_SIZE;
-    if (prec == PREC_F32) hipLaunchKernelGGL(crop_resize_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, H, W, crops5, k, dst, cpad);
-    else hipLaunchKernelGGL(crop_resize_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, H, W, crops5, k, dst, cpad);
+    if (prec == PREC_F32) hipLaunchKernelGGL(crop_resize_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, H, W, crops5, k, dst, cpad, ftab);
+    else hipLaunchKernelGGL(crop_resize_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, H, W, crops5, k, dst, cpad, ftab);
     VC_HIP(hipGetLastError());
     return VC_OK;
 }

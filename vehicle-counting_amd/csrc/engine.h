@@ -197,6 +197,17 @@ struct vc_engine {
     // frame-table ingest (yuv_ingest.hip: vc_stream_stage_frames): per slot a pinned table of max_batch entries and its device mirror, allocated by the first call
     void* h_frame_tab[4] = {nullptr, nullptr, nullptr, nullptr};
     void* d_frame_tab[4] = {nullptr, nullptr, nullptr, nullptr};
+    // sized batches (vc_stream_stage_frames_sized): per slot the frame entries followed by the cells, pinned + device mirror, and the dims
+    // of the sized batch the slot holds (empty: a uniform batch)
+    void* h_sized_tab[4] = {nullptr, nullptr, nullptr, nullptr};
+    void* d_sized_tab[4] = {nullptr, nullptr, nullptr, nullptr};
+    std::vector<vc_frame_dims> ingest_dims[4];
+    // ... their letterbox table (engine_run.hip: run_detector_dev_sized): two pinned slots like h_geom, one device table (detector stream order)
+    vc::LetterboxFrame* h_lb_tab = nullptr;      // pinned [2][max_batch]
+    vc::LetterboxFrame* d_lb_tab = nullptr;      // [max_batch]
+    // ... and their per-frame crop tables, one per feature / crop buffer
+    vc::CropFrame* h_crop_ftab[3] = {nullptr, nullptr, nullptr};
+    vc::CropFrame* d_crop_ftab[3] = {nullptr, nullptr, nullptr};
     // stream path: three feature / crop buffers -- the batch being tracked (tracker stream), the batch
     // whose ReID is running, and the one after it
     float* d_feat2[3] = {nullptr, nullptr, nullptr};
@@ -212,6 +223,8 @@ struct vc_engine {
     long long boxes_detected = 0, crops_embedded = 0;   // running totals of the stream and blocking paths (vc_stream_crop_stats)
     struct Pending {
         const void* frames; int b, h, w, slot;
+        std::vector<vc_frame_dims> dims; // a sized batch: every frame's own size (h, w above: the largest), frame f at frames + f * cell; empty: a uniform batch
+        size_t cell = 0;
         int stage = 0;                   // 0: detector enqueued, 1: ReID enqueued as well
         bool embed_refused = false;      // a look-ahead attempt to embed this batch failed; the call that consumes it reports why (stream.hip)
         int fslot = 0;                   // feature / crop buffer of this batch
@@ -324,11 +337,15 @@ LetterboxGeom letterbox_geom(int h0, int w0, int nh, int nw, bool swap_rb);
 int yolo_forward(vc_engine* e, int B, int nh, int nw);
 int reid_forward(vc_engine* e, int k, hipStream_t rs, float* feat_out);
 int run_detector_dev(vc_engine* e, const uint8_t* d_frames, int B, int h, int w, bool swap_rb);   // frames same size, on device
+// a sized batch: frame f (dims[f]) at d_frames + f * cell, every frame's own network shape nh x nw; one letterbox launch, the unfused stem
+int run_detector_dev_sized(vc_engine* e, const uint8_t* d_frames, int B, const vc_frame_dims* dims, size_t cell, int nh, int nw, bool swap_rb);
 int run_reid_dev(vc_engine* e, const uint8_t* d_frames, int H, int W, int k);                      // crops in e->d_crops -> e->d_feat
-int run_reid_on(vc_engine* e, const uint8_t* d_frames, int H, int W, int k, const int* d_crops, float* feat_out, hipStream_t rs);
+int run_reid_on(vc_engine* e, const uint8_t* d_frames, int H, int W, int k, const int* d_crops, float* feat_out, hipStream_t rs,
+                const CropFrame* d_ftab = nullptr);     // d_ftab: per-frame {offset, pitch} of a sized batch (device)
 // stream.hip: the slot rules of vc_stream_stage_host (shared with the YUV staging calls): checks, creates the copy stream and the four
 // slots on first use, and hands out the next slot round-robin.  The caller enqueues its work on e->cstream, then calls ingest_publish.
 int ingest_take_slot(vc_engine* e, int b, int h, int w, int* slot);
+size_t ingest_slot_bytes(const vc_engine* e);
 int ingest_publish(vc_engine* e, int slot, void** frames_dev_out);
 // yuv_ingest.hip / yuv_egress.hip: descriptor validation (pure host code) and the two conversions, both enqueued on `s`
 int yuv_resolve(const vc_yuv_desc* d, int b, int h, int w, YuvGeom& g);
@@ -354,8 +371,9 @@ void dsort_nms(const double* tlwh, const double* scores, int n, double max_overl
 // Build + enqueue one tracker batch on the tracker stream (after `wait`, if given, has fired on the GPU).  frame_groups[f] lists
 // (class label, tracker id, prepared detections) of frame f in class order.  Rows land in stage `st`; track_collect waits for them.
 struct FrameClassDets { int label, tracker; Prepared dets; };
+// frame_dims (a sized batch, else nullptr): the tasks of frame f clamp their rows to frame_dims[f] instead of W x H.
 int track_enqueue(vc_engine* e, int st, const std::vector<std::vector<FrameClassDets>>& frames, const float* d_feat, int W, int H,
-                  int rows_cap, hipEvent_t wait);
+                  int rows_cap, hipEvent_t wait, const vc_frame_dims* frame_dims = nullptr);
 // rows6 per frame: out_rows6[f * cap_rows_per_frame * 6 ...], out_m[f]
 int track_collect(vc_engine* e, int st, int64_t* out_rows6, int cap_rows_per_frame, int* out_m);
 int track_idle(vc_engine* e);              // wait until no tracker batch is in flight (stream path included)

@@ -796,4 +796,111 @@ int vc_letterbox_host(const uint8_t* rgb, int h, int w, int net_h, int net_w, in
     return st;
 }
 
+// ---- sized batches: the letterbox and crop kernels with their per-frame tables, on host arrays --------------------------------------
+// frames of their own sizes uploaded into cells (include/vcount_hip.h) -> *cells_out (device, in tmp); *cell_out: the cell size
+static int upload_cells(vc_engine* tmp, const uint8_t* const* frames, const vc_frame_dims* dims, int b, uint8_t** cells_out, size_t* cell_out) {
+    VC_CHECK(frames && dims && b >= 1, VC_ERR_ARG, "bad batch of %d frames", b);
+    size_t cell = 0;
+    for (int f = 0; f < b; ++f) {
+        VC_CHECK(frames[f] && dims[f].h >= 1 && dims[f].w >= 1 && dims[f].h <= (1 << 15) && dims[f].w <= (1 << 15), VC_ERR_ARG, "frame %d: null data or bad size %dx%d", f,
+                 dims[f].h, dims[f].w);
+        cell = std::max(cell, (size_t)dims[f].h * dims[f].w * 3);
+    }
+    cell = (cell + 15) / 16 * 16;
+    VC_TRY(dev_alloc(tmp, (void**)cells_out, (size_t)b * cell));
+    VC_HIP(hipMemset(*cells_out, 0xA5, (size_t)b * cell));             // what a kernel that strays outside a frame would pick up
+    for (int f = 0; f < b; ++f) VC_HIP(hipMemcpy(*cells_out + (size_t)f * cell, frames[f], (size_t)dims[f].h * dims[f].w * 3, hipMemcpyHostToDevice));
+    *cell_out = cell;
+    return VC_OK;
+}
+
+int vc_letterbox_frames_host(const uint8_t* const* frames, const vc_frame_dims* dims, int b, int net_h, int net_w, int swap_rb, int precision, float* out) {
+    VC_CHECK(out, VC_ERR_ARG, "null argument");
+    VC_CHECK(net_h >= 1 && net_w >= 4 && net_w % 4 == 0, VC_ERR_ARG, "network tensor %dx%d (the width must be a multiple of 4)", net_h, net_w);
+    VC_CHECK(precision == VC_PREC_BF16 || precision == VC_PREC_F32, VC_ERR_ARG, "precision must be VC_PREC_BF16 or VC_PREC_F32");
+    vc_engine tmp;
+    uint8_t* dc = nullptr;
+    void *dd = nullptr, *dt = nullptr;
+    size_t cell = 0;
+    const int es = elem_size(precision);
+    const size_t px = (size_t)b * net_h * net_w;
+    int st = upload_cells(&tmp, frames, dims, b, &dc, &cell);
+    if (st == VC_OK) st = dev_alloc(&tmp, &dd, px * 4 * es);
+    if (st == VC_OK) st = dev_alloc(&tmp, &dt, (size_t)b * sizeof(LetterboxFrame));
+    if (st == VC_OK) {
+        std::vector<LetterboxFrame> tab((size_t)b);
+        for (int f = 0; f < b; ++f) tab[f] = letterbox_frame((long long)((size_t)f * cell), letterbox_geom(dims[f].h, dims[f].w, net_h, net_w, swap_rb != 0));
+        if (hipMemcpy(dt, tab.data(), (size_t)b * sizeof(LetterboxFrame), hipMemcpyHostToDevice) != hipSuccess) { set_error("upload failed"); st = VC_ERR_HIP; }
+    }
+    if (st == VC_OK) st = launch_letterbox_frames(dc, (const LetterboxFrame*)dt, dd, b, net_h, net_w, swap_rb ? 1 : 0, precision, nullptr);
+    if (st == VC_OK) {
+        std::vector<uint8_t> buf(px * 4 * es);
+        if (hipMemcpy(buf.data(), dd, buf.size(), hipMemcpyDeviceToHost) != hipSuccess) { set_error("letterbox_frames_kernel failed: %s", hipGetErrorString(hipGetLastError())); st = VC_ERR_HIP; }
+        for (size_t i = 0; i < px && st == VC_OK; ++i)
+            for (int c = 0; c < 3; ++c)
+                out[i * 3 + c] = es == 4 ? ((const float*)buf.data())[i * 4 + c] : bf16_to_f32(((const uint16_t*)buf.data())[i * 4 + c]);
+    }
+    for (void* q : tmp.allocs) hipFree(q);
+    tmp.allocs.clear();
+    return st;
+}
+
+// The letterbox kernels on the caller's own device buffers (measurement; the counterpart of vc_frames_to_bgr_dev): frames_dev = b packed
+// h x w x 3 u8 frames, out_dev = b x net_h x net_w x 4 elements of `precision`.  mode 0: launch_letterbox, the kernels a uniform batch
+// runs.  mode 1: a table of b entries for these uniform frames is built and copied to table_dev (b * 64 bytes, a blocking copy), then
+// letterbox_frames_kernel runs; mode 2: letterbox_frames_kernel with the table as the last mode-1 call left it.  NULL stream, no wait.
+int vc_letterbox_dev(const void* frames_dev, int b, int h, int w, int net_h, int net_w, int swap_rb, int precision, void* out_dev, void* table_dev, int mode) {
+    VC_CHECK(frames_dev && out_dev && (mode == 0 || table_dev), VC_ERR_ARG, "null argument");
+    VC_CHECK(b >= 1 && h >= 1 && w >= 1 && net_h >= 1 && net_w >= 4 && net_w % 4 == 0 && mode >= 0 && mode <= 2, VC_ERR_ARG, "bad argument");
+    VC_CHECK(precision == VC_PREC_BF16 || precision == VC_PREC_F32, VC_ERR_ARG, "precision must be VC_PREC_BF16 or VC_PREC_F32");
+    static_assert(sizeof(LetterboxFrame) <= 64, "the caller reserves 64 bytes per table entry");
+    const LetterboxGeom g = letterbox_geom(h, w, net_h, net_w, swap_rb != 0);
+    if (mode == 0) return launch_letterbox((const uint8_t*)frames_dev, out_dev, b, g, precision, nullptr);
+    if (mode == 1) {
+        std::vector<LetterboxFrame> tab((size_t)b);
+        for (int f = 0; f < b; ++f) tab[f] = letterbox_frame((long long)((size_t)f * h * w * 3), g);
+        VC_HIP(hipMemcpy(table_dev, tab.data(), (size_t)b * sizeof(LetterboxFrame), hipMemcpyHostToDevice));
+    }
+    return launch_letterbox_frames((const uint8_t*)frames_dev, (const LetterboxFrame*)table_dev, out_dev, b, net_h, net_w, swap_rb ? 1 : 0, precision, nullptr);
+}
+
+int vc_crop_resize_frames_host(const uint8_t* const* bgr, const vc_frame_dims* dims, int b, const int* frame_of_box, const double* boxes, int k, float* out) {
+    VC_CHECK(frame_of_box && boxes && out && k >= 1, VC_ERR_ARG, "bad argument");
+    std::vector<int> crops((size_t)k * 5);
+    for (int i = 0; i < k; ++i) {
+        const int f = frame_of_box[i];
+        VC_CHECK(dims && f >= 0 && f < b, VC_ERR_ARG, "box %d: frame %d outside [0, %d)", i, f, b);
+        int c[4];
+        crop_corners(boxes + (size_t)i * 4, dims[f].w, dims[f].h, c);                 // the frame's own W - 1, H - 1
+        VC_CHECK(c[2] > c[0] && c[3] > c[1], VC_ERR_ARG, "box %d gives an empty crop (the reference's cv2.resize raises here)", i);
+        crops[(size_t)i * 5] = f;
+        memcpy(&crops[(size_t)i * 5 + 1], c, sizeof(c));
+    }
+    vc_engine tmp;
+    uint8_t* dc = nullptr;
+    void *dd = nullptr, *dt = nullptr, *dk = nullptr;
+    size_t cell = 0;
+    const size_t px = (size_t)k * VC_REID_SIZE * VC_REID_SIZE;
+    int st = upload_cells(&tmp, bgr, dims, b, &dc, &cell);
+    if (st == VC_OK) st = dev_alloc(&tmp, &dd, px * 4 * sizeof(float));
+    if (st == VC_OK) st = dev_alloc(&tmp, &dt, (size_t)b * sizeof(CropFrame));
+    if (st == VC_OK) st = dev_alloc(&tmp, &dk, crops.size() * sizeof(int));
+    if (st == VC_OK) {
+        std::vector<CropFrame> tab((size_t)b);
+        for (int f = 0; f < b; ++f) tab[f] = CropFrame{(long long)((size_t)f * cell), dims[f].w, 0};
+        if (hipMemcpy(dt, tab.data(), (size_t)b * sizeof(CropFrame), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dk, crops.data(), crops.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { set_error("upload failed"); st = VC_ERR_HIP; }
+    }
+    if (st == VC_OK) st = launch_crop_resize(dc, 0, 0, (const int*)dk, k, dd, 4, VC_PREC_F32, nullptr, false, (const CropFrame*)dt);
+    if (st == VC_OK) {
+        std::vector<float> buf(px * 4);
+        if (hipMemcpy(buf.data(), dd, buf.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { set_error("crop_resize_kernel failed: %s", hipGetErrorString(hipGetLastError())); st = VC_ERR_HIP; }
+        for (size_t i = 0; i < px && st == VC_OK; ++i)
+            for (int c = 0; c < 3; ++c) out[i * 3 + c] = buf[i * 4 + c];
+    }
+    for (void* q : tmp.allocs) hipFree(q);
+    tmp.allocs.clear();
+    return st;
+}
+
 }  // extern "C"

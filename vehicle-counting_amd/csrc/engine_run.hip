@@ -423,6 +423,33 @@ int run_detector_dev(vc_engine* e, const uint8_t* d_frames, int B, int h, int w,
     return st;
 }
 
+// A sized batch (include/vcount_hip.h): the caller has checked that every frame's own network shape is nh x nw.  d_geom per frame, one
+// letterbox_frames_kernel launch into ybuf["in"], then the pass every other entry point runs from the letterboxed tensor (the stem
+// kernels that read u8 frames take ONE geometry per launch: a sized batch always takes the unfused stem).
+int run_detector_dev_sized(vc_engine* e, const uint8_t* d_frames, int B, const vc_frame_dims* dims, size_t cell, int nh, int nw, bool swap_rb) {
+    VC_CHECK(e->finalized && e->cfg.with_detector, VC_ERR_STATE, "detector not finalized");
+    VC_CHECK(B >= 1, VC_ERR_ARG, "a batch needs at least one frame (got %d)", B);
+    VC_CHECK(B <= e->cfg.max_batch, VC_ERR_CAPACITY, "batch %d exceeds max_batch %d", B, e->cfg.max_batch);
+    if (!e->h_lb_tab) {
+        VC_TRY(host_alloc(e, (void**)&e->h_lb_tab, (size_t)2 * e->cfg.max_batch * sizeof(LetterboxFrame)));
+        VC_TRY(dev_alloc(e, (void**)&e->d_lb_tab, (size_t)e->cfg.max_batch * sizeof(LetterboxFrame)));
+    }
+    const unsigned half = e->geom_seq++ & 1;                                          // two pinned slots: two submissions may be in flight
+    float* hg = e->h_geom + (size_t)half * e->cfg.max_batch * 5;
+    LetterboxFrame* ht = e->h_lb_tab + (size_t)half * e->cfg.max_batch;
+    for (int b = 0; b < B; ++b) {
+        scale_geom_host(ScaleGeom{nh, nw, dims[b].h, dims[b].w}, hg + (size_t)b * 5);
+        ht[b] = letterbox_frame((long long)((size_t)b * cell), letterbox_geom(dims[b].h, dims[b].w, nh, nw, swap_rb));
+    }
+    VC_HIP(hipMemcpyAsync(e->d_geom, hg, (size_t)B * 5 * sizeof(float), hipMemcpyHostToDevice, e->dstream));
+    VC_HIP(hipMemcpyAsync(e->d_lb_tab, ht, (size_t)B * sizeof(LetterboxFrame), hipMemcpyHostToDevice, e->dstream));
+    e->stem_src = nullptr;
+    e->in_stale = false;
+    { ProfScope ps(e, VC_PROF_DETECT_AUX, 0, 0, e->dstream);
+      VC_TRY(launch_letterbox_frames(d_frames, e->d_lb_tab, e->ybuf["in"].ptr, B, nh, nw, swap_rb ? 1 : 0, e->aux_prec, e->dstream)); }
+    return yolo_forward(e, B, nh, nw);
+}
+
 #define VC_REID_CHUNK 6400
 #define VC_REID_PLAN_CACHE_MAX_K 256       // crop counts whose op plans are kept (k0 is 0 for these: one chunk)
 static int reid_forward_chunk(vc_engine* e, int k0, int k, hipStream_t rs, float* feat_out) {
@@ -447,12 +474,12 @@ int reid_forward(vc_engine* e, int k, hipStream_t rs, float* feat_out) {
     return VC_OK;
 }
 
-int run_reid_on(vc_engine* e, const uint8_t* d_frames, int H, int W, int k, const int* d_crops, float* feat_out, hipStream_t rs) {
+int run_reid_on(vc_engine* e, const uint8_t* d_frames, int H, int W, int k, const int* d_crops, float* feat_out, hipStream_t rs, const CropFrame* d_ftab) {
     VC_CHECK(e->finalized && e->cfg.with_reid, VC_ERR_STATE, "ReID net not finalized");
     VC_CHECK(k <= e->cfg.max_crops, VC_ERR_CAPACITY, "%d crops exceed max_crops %d", k, e->cfg.max_crops);
     if (k <= 0) return VC_OK;
     { ProfScope ps(e, VC_PROF_REID_AUX, 0, 0, rs);
-      VC_TRY(launch_crop_resize(d_frames, H, W, d_crops, k, e->rbuf["in"].ptr, reid_cpad(e->aux_prec), e->aux_prec, rs, e->opt.crop_per_pixel != 0)); }
+      VC_TRY(launch_crop_resize(d_frames, H, W, d_crops, k, e->rbuf["in"].ptr, reid_cpad(e->aux_prec), e->aux_prec, rs, e->opt.crop_per_pixel != 0, d_ftab)); }
     return reid_forward(e, k, rs, feat_out);
 }
 

@@ -23,6 +23,16 @@ struct LetterboxGeom {
 };
 // src: B x src_h x src_w x 3 u8.  dst: B x net_h x net_w x 4 (prec), channel 3 = 0, values /255.
 int launch_letterbox(const uint8_t* src, void* dst, int B, const LetterboxGeom& g, int prec, hipStream_t s);
+// A batch whose frames have their own sizes (sized batches, include/vcount_hip.h): one entry per frame, precomputed on the host.
+// sx / sy: letterbox_kernel's scales, formed with its own expression 1.0 / ((double)unpad / (double)src).
+struct LetterboxFrame {
+    long long src_off;    // byte offset of the frame (tight h x w x 3 u8) from the batch's base
+    int src_h, src_w, unpad_h, unpad_w, top, left;
+    double sx, sy;
+};
+LetterboxFrame letterbox_frame(long long src_off, const LetterboxGeom& g);
+// tab: B entries in device memory.  dst as launch_letterbox; per frame the values are those of launch_letterbox on that frame alone.
+int launch_letterbox_frames(const uint8_t* src, const LetterboxFrame* tab, void* dst, int B, int net_h, int net_w, int swap_rb, int prec, hipStream_t s);
 // SPPF: x = view slice [0,C); writes maxpool5, maxpool5∘2, maxpool5∘3 into slices [C,2C), [2C,3C), [3C,4C) of the same buffer.
 int launch_sppf_pool(const View& cat, int C, int prec, int form, hipStream_t s);   // form 1: register form where it applies, 0: the LDS-plane forms
 int launch_upsample2x(const View& src, const View& dst, int prec, hipStream_t s);
@@ -69,8 +79,11 @@ int launch_nms(int B, int max_cand, int max_det, float iou, const float* geom_de
 // ---- ReID side -------------------------------------------------------------------------------------
 // frames: F x H x W x 3 u8 BGR.  crop[i] = (frame, x1, y1, x2, y2) end-exclusive int corners.
 // dst: k x 50 x 50 x cpad (prec), channels >= 3 zero.  ((v/255 bilinear) - mean) / std, BGR order kept (quirk Q3).
+// ftab (device, one entry per frame; nullptr = the uniform addressing above): frame f starts at frames + ftab[f].off and has row pitch ftab[f].W pixels.
+struct CropFrame { long long off; int W, pad; };
 int launch_crop_resize(const uint8_t* frames, int H, int W, const int* crops5, int k, void* dst, int cpad, int prec,
-                       hipStream_t s, bool per_pixel = false);     // per_pixel: the per-pixel instance of the bf16 path (parity tests)
+                       hipStream_t s, bool per_pixel = false,      // per_pixel: the per-pixel instance of the bf16 path (parity tests)
+                       const CropFrame* ftab = nullptr);
 // x_nchw: k x 3 x 50 x 50 f32 already-normalised tensor -> same NHWC/cpad layout (vc_embed_tensor)
 int launch_nchw_to_nhwc_pad(const float* x, int k, int C, int H, int W, void* dst, int cpad, int prec, hipStream_t s);
 int launch_maxpool3s2(const View& src, const View& dst, int prec, hipStream_t s);
@@ -97,7 +110,8 @@ struct CostJob {
 };
 // One tracker step = (tracker, frame): Tracker.predict() + Tracker.update(detections) on the prepared (confidence-filtered,
 // DeepSORT-NMS'ed, deep_sort.py:31-41) detections [det_off, det_off + det_n) of the batch's detection arrays.
-struct TrackTask { int tracker, det_off, det_n, frame, label, pad0, pad1, pad2; };
+// frame_w / frame_h: the size this task's boxes are clamped to (a camera of a sized batch); 0 = TrackBatchArgs.frame_w / frame_h.
+struct TrackTask { int tracker, det_off, det_n, frame, label, frame_w, frame_h, pad2; };
 // workgroup b of the batch kernel owns one tracker and runs its tasks [task_begin, task_end) in order; the tracker's detections of
 // the batch are the contiguous range [det_begin, det_begin + det_n) of the detection arrays (frames ascending)
 struct TrackWgPlan { int tracker, task_begin, task_end, det_begin, det_n, pad0, pad1, pad2; };

@@ -62,12 +62,15 @@ void marshal(const float* det6, int n, FrameDets& out) {
 
 namespace vc {
 
+// an ingest slot holds max_batch frames of the configured maximum, also as the 16-byte-aligned cells of a sized batch
+size_t ingest_slot_bytes(const vc_engine* e) { return (size_t)e->cfg.max_batch * ((size_t)e->cfg.max_frame_h * e->cfg.max_frame_w * 3 + 16); }
+
 int ingest_take_slot(vc_engine* e, int b, int h, int w, int* slot_out) {
     VC_CHECK(e->finalized && e->cfg.with_detector, VC_ERR_STATE, "engine not finalized");
     VC_CHECK(b >= 1 && b <= e->cfg.max_batch && h >= 1 && w >= 1 && h <= e->cfg.max_frame_h && w <= e->cfg.max_frame_w, VC_ERR_CAPACITY,
              "batch of %d frames %dx%d exceeds max_batch / max_frame_h / max_frame_w", b, h, w);
     VC_HIP(hipSetDevice(e->cfg.device));
-    const size_t slot_bytes = (size_t)e->cfg.max_batch * e->cfg.max_frame_h * e->cfg.max_frame_w * 3;
+    const size_t slot_bytes = ingest_slot_bytes(e);
     if (!e->cstream) {
         VC_HIP(hipStreamCreateWithFlags(&e->cstream, hipStreamNonBlocking));
         for (int i = 0; i < 4; ++i) {
@@ -83,6 +86,7 @@ int ingest_take_slot(vc_engine* e, int b, int h, int w, int* slot_out) {
     for (const auto& job : e->jobs)                      // its crops may still be being cut on the ReID stream
         VC_CHECK(job.frames != e->d_ingest[slot], VC_ERR_STATE, "the staging slot's previous batch has not been collected: at most four host batches may be alive");
     ++e->ingest_seq;
+    e->ingest_dims[slot].clear();                        // a uniform batch until vc_stream_stage_frames_sized says otherwise
     *slot_out = slot;
     return VC_OK;
 }
@@ -111,10 +115,18 @@ int vc_stream_inject(vc_engine* e, const float* det6, const int* count, int b, i
 
 // Enqueue the detector (letterbox .. NMS, results to pinned memory) for a batch on the detector stream and return
 // immediately.  At most two submissions may be outstanding; vc_stream_run consumes them in order.
-int vc_stream_submit(vc_engine* e, const void* frames_dev, int b, int h, int w) {
-    VC_CHECK(e && frames_dev, VC_ERR_ARG, "null argument");
+// dims == nullptr: a uniform batch of h x w frames.  Otherwise a sized batch whose dims have been validated (sized_layout below): frame f
+// at frames_dev + f * cell, every frame's own network shape nh x nw, h x w the largest frame.
+static int submit_batch(vc_engine* e, const void* frames_dev, int b, int h, int w, const vc_frame_dims* dims, size_t cell, int nh, int nw) {
     VC_CHECK(e->finalized && e->cfg.with_detector, VC_ERR_STATE, "engine not finalized");
     VC_CHECK(e->pending.size() < 2, VC_ERR_STATE, "two submissions are already in flight: call vc_stream_run first");
+    for (int i = 0; i < 4; ++i)                          // a staged batch is submitted as what it was staged as
+        if (e->d_ingest[i] && frames_dev == e->d_ingest[i] && e->ingest_staged[i]) {
+            const std::vector<vc_frame_dims>& sd = e->ingest_dims[i];
+            VC_CHECK(dims || sd.empty(), VC_ERR_ARG, "the batch was staged by vc_stream_stage_frames_sized: submit it with vc_stream_submit_sized");
+            VC_CHECK(!dims || ((int)sd.size() == b && memcmp(sd.data(), dims, (size_t)b * sizeof(vc_frame_dims)) == 0), VC_ERR_ARG,
+                     "the frame sizes differ from those the batch was staged with");
+        }
     VC_HIP(hipSetDevice(e->cfg.device));
     for (int i = 0; i < 4; ++i)                          // a batch staged by vc_stream_stage_host: the detector starts behind its copy
         if (e->d_ingest[i] && frames_dev == e->d_ingest[i] && e->ingest_staged[i]) {
@@ -123,15 +135,49 @@ int vc_stream_submit(vc_engine* e, const void* frames_dev, int b, int h, int w) 
         }
     const int slot = (int)(e->submit_seq++ & 1);
     const int md = e->cfg.max_det;
-    VC_TRY(run_detector_dev(e, (const uint8_t*)frames_dev, b, h, w, /*swap_rb=*/true));
+    if (dims) VC_TRY(run_detector_dev_sized(e, (const uint8_t*)frames_dev, b, dims, cell, nh, nw, /*swap_rb=*/true));
+    else VC_TRY(run_detector_dev(e, (const uint8_t*)frames_dev, b, h, w, /*swap_rb=*/true));
     VC_HIP(hipMemcpyAsync(e->h_det2[slot], e->post.det, (size_t)b * md * 6 * sizeof(float), hipMemcpyDeviceToHost, e->dstream));
     VC_HIP(hipMemcpyAsync(e->h_det_count2[slot], e->post.det_count, b * sizeof(int), hipMemcpyDeviceToHost, e->dstream));
     VC_HIP(hipEventRecord(e->ev_det[slot], e->dstream));
     vc_engine::Pending pd{};
     pd.frames = frames_dev; pd.b = b; pd.h = h; pd.w = w; pd.slot = slot;
+    if (dims) { pd.dims.assign(dims, dims + b); pd.cell = cell; }
     if (e->inject_b > 0) { pd.inj_det = e->inject_det; pd.inj_cnt = e->inject_count; pd.inj_b = e->inject_b; pd.inj_n = e->inject_n; }   // this batch's own rectangles
     e->pending.push_back(std::move(pd));
     return VC_OK;
+}
+
+int vc_stream_submit(vc_engine* e, const void* frames_dev, int b, int h, int w) {
+    VC_CHECK(e && frames_dev, VC_ERR_ARG, "null argument");
+    return submit_batch(e, frames_dev, b, h, w, nullptr, 0, 0, 0);
+}
+
+// The rules of a sized batch for a caller that hands in device frames (pure host logic): equal network shapes, the cell, the capacities.
+static int sized_layout(vc_engine* e, const vc_frame_dims* dims, int b, size_t& cell, int& nh, int& nw, int& max_h, int& max_w) {
+    VC_CHECK(b >= 1 && dims, VC_ERR_ARG, "bad sized batch of %d frames", b);
+    cell = 0; max_h = max_w = 0;
+    for (int f = 0; f < b; ++f) {
+        const int h = dims[f].h, w = dims[f].w;
+        VC_CHECK(h >= 1 && w >= 1 && h <= (1 << 15) && w <= (1 << 15), VC_ERR_ARG, "frame %d: bad frame size %dx%d", f, h, w);
+        int fh, fw;
+        autoshape_net_size(&h, &w, 1, e->cfg.img_size, fh, fw);
+        if (f == 0) { nh = fh; nw = fw; }
+        VC_CHECK(fh == nh && fw == nw, VC_ERR_ARG, "frame %d: %dx%d runs at %dx%d, frame 0 at %dx%d", f, h, w, fh, fw, nh, nw);
+        cell = std::max(cell, (size_t)h * w * 3);
+        max_h = std::max(max_h, h); max_w = std::max(max_w, w);
+    }
+    cell = (cell + 15) / 16 * 16;
+    VC_CHECK(b <= e->cfg.max_batch && max_h <= e->cfg.max_frame_h && max_w <= e->cfg.max_frame_w, VC_ERR_CAPACITY,
+             "batch of %d frames up to %dx%d exceeds max_batch / max_frame_h / max_frame_w", b, max_h, max_w);
+    return VC_OK;
+}
+
+int vc_stream_submit_sized(vc_engine* e, const void* frames_dev, const vc_frame_dims* dims, int b) {
+    VC_CHECK(e && frames_dev && dims, VC_ERR_ARG, "null argument");
+    size_t cell; int nh = 0, nw = 0, mh, mw;
+    VC_TRY(sized_layout(e, dims, b, cell, nh, nw, mh, mw));
+    return submit_batch(e, frames_dev, b, mh, mw, dims, cell, nh, nw);
 }
 
 // Ingest from host memory (the reference decodes on the host and hands numpy frames over, modules/datasets.py:47-61):
@@ -164,13 +210,14 @@ namespace {
 // The crop of every box of the batch, in (frame, box) order (deep_sort.py:78-95), with the checks that refuse a batch: more boxes than
 // max_crops, an empty crop.  Both count ALL boxes, whatever is embedded afterwards.  pd.row0[f] = first row of frame f in that list.
 int all_crops(vc_engine* e, vc_engine::Pending& pd, std::vector<int>& crops) {
-    const int b = pd.b, h = pd.h, w = pd.w;
+    const int b = pd.b;
     crops.clear();
     pd.row0.assign(b, 0);
     int k = 0;
     for (int f = 0; f < b; ++f) {
         pd.row0[f] = k;
         FrameDets& d = pd.fd[f];
+        const int h = pd.dims.empty() ? pd.h : pd.dims[f].h, w = pd.dims.empty() ? pd.w : pd.dims[f].w;    // the frame's own size
         VC_CHECK(k + (int)d.conf.size() <= e->cfg.max_crops, VC_ERR_CAPACITY,
                  "the batch has more boxes than max_crops (%d): raise vc_engine_config.max_crops", e->cfg.max_crops);
         for (size_t i = 0; i < d.conf.size(); ++i) {
@@ -194,9 +241,20 @@ int all_crops(vc_engine* e, vc_engine::Pending& pd, std::vector<int>& crops) {
 int enqueue_reid(vc_engine* e, vc_engine::Pending& pd, const int* crops, int k) {
     int* hc = e->h_crops2[pd.fslot];
     if (k > 0) {
+        const CropFrame* ftab = nullptr;
+        if (!pd.dims.empty()) {                              // a sized batch: the crop kernels reach frame f through its cell and its own pitch
+            if (!e->h_crop_ftab[pd.fslot]) {
+                VC_TRY(host_alloc(e, (void**)&e->h_crop_ftab[pd.fslot], (size_t)e->cfg.max_batch * sizeof(CropFrame)));
+                VC_TRY(dev_alloc(e, (void**)&e->d_crop_ftab[pd.fslot], (size_t)e->cfg.max_batch * sizeof(CropFrame)));
+            }
+            CropFrame* hf = e->h_crop_ftab[pd.fslot];
+            for (int f = 0; f < pd.b; ++f) hf[f] = CropFrame{(long long)((size_t)f * pd.cell), pd.dims[f].w, 0};
+            VC_HIP(hipMemcpyAsync(e->d_crop_ftab[pd.fslot], hf, (size_t)pd.b * sizeof(CropFrame), hipMemcpyHostToDevice, e->rstream));
+            ftab = e->d_crop_ftab[pd.fslot];
+        }
         memcpy(hc, crops, (size_t)k * 5 * sizeof(int));
         VC_HIP(hipMemcpyAsync(e->d_crops2[pd.fslot], hc, (size_t)k * 5 * sizeof(int), hipMemcpyHostToDevice, e->rstream));
-        VC_TRY(run_reid_on(e, (const uint8_t*)pd.frames, pd.h, pd.w, k, e->d_crops2[pd.fslot], e->d_feat2[pd.fslot], e->rstream));
+        VC_TRY(run_reid_on(e, (const uint8_t*)pd.frames, pd.h, pd.w, k, e->d_crops2[pd.fslot], e->d_feat2[pd.fslot], e->rstream, ftab));
     }
     VC_HIP(hipEventRecord(e->ev_reid[pd.fslot], e->rstream));
     e->crops_embedded += k;
@@ -391,18 +449,25 @@ static int enqueue_batch_tracking(vc_engine* e, vc_engine::Pending& pd, const in
         }
     }
     g_tm.lap(1);
-    VC_TRY(track_enqueue(e, stage, frames, e->d_feat2[pd.fslot], pd.w, pd.h, b * cap_rows_per_frame, e->ev_reid[pd.fslot]));
+    VC_TRY(track_enqueue(e, stage, frames, e->d_feat2[pd.fslot], pd.w, pd.h, b * cap_rows_per_frame, e->ev_reid[pd.fslot], pd.dims.empty() ? nullptr : pd.dims.data()));
     g_tm.lap(2);
     return VC_OK;
 }
 
 // Pop the oldest submission once its detector has finished and its ReID is enqueued.
-static int take_front(vc_engine* e, const void* frames_dev, int b, int h, int w, vc_engine::Pending& out) {
-    if (e->pending.empty()) VC_TRY(vc_stream_submit(e, frames_dev, b, h, w));
+static int take_front(vc_engine* e, const void* frames_dev, int b, int h, int w, vc_engine::Pending& out, const vc_frame_dims* dims = nullptr) {
+    if (e->pending.empty()) VC_TRY(dims ? vc_stream_submit_sized(e, frames_dev, dims, b) : vc_stream_submit(e, frames_dev, b, h, w));
     {
         const vc_engine::Pending& fr = e->pending.front();
-        VC_CHECK(fr.frames == frames_dev && fr.b == b && fr.h == h && fr.w == w, VC_ERR_STATE,
-                 "vc_stream_run must consume submissions in the order they were made");
+        if (dims) {                                          // a sized run: the front must be that sized batch, frame size by frame size
+            VC_CHECK(fr.frames == frames_dev && fr.b == b, VC_ERR_STATE, "vc_stream_run must consume submissions in the order they were made");
+            VC_CHECK((int)fr.dims.size() == b && memcmp(fr.dims.data(), dims, (size_t)b * sizeof(vc_frame_dims)) == 0, VC_ERR_ARG,
+                     "the frame sizes differ from those the batch was submitted with");
+        } else {
+            VC_CHECK(fr.frames == frames_dev && fr.b == b && fr.h == h && fr.w == w, VC_ERR_STATE,
+                     "vc_stream_run must consume submissions in the order they were made");
+            VC_CHECK(fr.dims.empty(), VC_ERR_ARG, "the batch was submitted by vc_stream_submit_sized: run it with vc_stream_run_async_multi_sized");
+        }
     }
     g_tm.start();
     if (e->pending.front().stage == 0) {
@@ -433,8 +498,8 @@ int vc_stream_run_async(vc_engine* e, const int* trackers, int num_classes, cons
     return vc_stream_run_async_multi(e, trackers, 1, num_classes, nullptr, frames_dev, b, h, w, cap_rows_per_frame);
 }
 
-int vc_stream_run_async_multi(vc_engine* e, const int* trackers, int n_cam, int num_classes, const int* cam_of_frame, const void* frames_dev, int b, int h,
-                              int w, int cap_rows_per_frame) {
+static int run_async_batch(vc_engine* e, const int* trackers, int n_cam, int num_classes, const int* cam_of_frame, const void* frames_dev, int b, int h,
+                           int w, int cap_rows_per_frame, const vc_frame_dims* dims) {
     VC_CHECK(e && trackers && frames_dev && cap_rows_per_frame > 0 && n_cam >= 1 && (n_cam == 1 || cam_of_frame), VC_ERR_ARG, "bad argument");
     VC_CHECK(e->finalized && e->cfg.with_detector && e->cfg.with_reid, VC_ERR_STATE, "engine not finalized");
     VC_HIP(hipSetDevice(e->cfg.device));
@@ -453,7 +518,7 @@ int vc_stream_run_async_multi(vc_engine* e, const int* trackers, int n_cam, int 
         e->stream_flt = flt;
     }
     vc_engine::Pending pd;
-    VC_TRY(take_front(e, frames_dev, b, h, w, pd));
+    VC_TRY(take_front(e, frames_dev, b, h, w, pd, dims));
     vc_engine::AsyncJob job;
     job.stage = (int)(e->tstage_seq++ % 3); job.b = b; job.cap = cap_rows_per_frame; job.frames = frames_dev;
     VC_TRY(enqueue_batch_tracking(e, pd, trackers, num_classes, cam_of_frame, n_cam, job.stage, cap_rows_per_frame, job.ndet));
@@ -461,6 +526,29 @@ int vc_stream_run_async_multi(vc_engine* e, const int* trackers, int n_cam, int 
     g_tm.report();
     try_issue_next(e);
     return VC_OK;
+}
+
+int vc_stream_run_async_multi(vc_engine* e, const int* trackers, int n_cam, int num_classes, const int* cam_of_frame, const void* frames_dev, int b, int h,
+                              int w, int cap_rows_per_frame) {
+    return run_async_batch(e, trackers, n_cam, num_classes, cam_of_frame, frames_dev, b, h, w, cap_rows_per_frame, nullptr);
+}
+
+// The same for a sized batch.  A camera's track boxes are clamped to ITS frame (track_core.h: emit_rows), so within the batch all frames
+// of one camera have one size; refused before the submission is consumed.
+int vc_stream_run_async_multi_sized(vc_engine* e, const int* trackers, int n_cam, int num_classes, const int* cam_of_frame, const void* frames_dev,
+                                    const vc_frame_dims* dims, int b, int cap_rows_per_frame) {
+    VC_CHECK(e && dims && b >= 1 && n_cam >= 1 && (n_cam == 1 || cam_of_frame), VC_ERR_ARG, "bad argument");
+    std::vector<int> first((size_t)n_cam, -1);
+    for (int f = 0; f < b; ++f) {
+        const int cam = cam_of_frame ? cam_of_frame[f] : 0;
+        VC_CHECK(cam >= 0 && cam < n_cam, VC_ERR_ARG, "frame %d: camera index %d outside [0, %d)", f, cam, n_cam);
+        if (first[cam] < 0) first[cam] = f;
+        VC_CHECK(dims[f].h == dims[first[cam]].h && dims[f].w == dims[first[cam]].w, VC_ERR_ARG, "frame %d: camera %d delivers %dx%d here and %dx%d in frame %d", f, cam,
+                 dims[f].h, dims[f].w, dims[first[cam]].h, dims[first[cam]].w, first[cam]);
+    }
+    int mh = 0, mw = 0;
+    for (int f = 0; f < b; ++f) { mh = std::max(mh, dims[f].h); mw = std::max(mw, dims[f].w); }
+    return run_async_batch(e, trackers, n_cam, num_classes, cam_of_frame, frames_dev, b, mh, mw, cap_rows_per_frame, dims);
 }
 
 // Results of the oldest asynchronous batch (blocks until its tracker kernel has finished).  While waiting, the ReID of the

@@ -654,7 +654,7 @@ __global__ __launch_bounds__(NW * 64) void track_batch_kernel(const TrackBatchAr
                 if (lane == 0) { report_error(a, hdr, TERR_ROWS, plan.tracker, task); a.task_row_n[task] = 0; a.task_row_off[task] = 0; }
             } else {
                 auto mean_of = [&](int t) -> const double* { return use_st ? sh.st_mean[t] : tp.mean + (size_t)w.slot[t] * 8; };
-                emit_rows(L, w, mean_of, T, a.frame_w, a.frame_h, tk.label, [&](int pos, const long long* row) {
+                emit_rows(L, w, mean_of, T, tk.frame_w ? tk.frame_w : a.frame_w, tk.frame_h ? tk.frame_h : a.frame_h, tk.label, [&](int pos, const long long* row) {
                     long long* o = a.rows + (size_t)(base + pos) * 6;
 #pragma unroll
                     for (int c = 0; c < 6; ++c) o[c] = row[c];

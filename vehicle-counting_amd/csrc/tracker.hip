@@ -164,7 +164,7 @@ static OutLayout out_layout(int n_tasks, int rows_cap) {
 }
 
 int track_enqueue(vc_engine* e, int st, const std::vector<std::vector<FrameClassDets>>& frames, const float* d_feat, int W, int H,
-                  int rows_cap, hipEvent_t wait) {
+                  int rows_cap, hipEvent_t wait, const vc_frame_dims* frame_dims) {
     TrackStage& s = e->tstage[st];
     VC_CHECK(!s.busy, VC_ERR_STATE, "tracker staging slot %d is still in flight", st);
     // tasks in (frame, class) order -- the order rows are handed back in
@@ -246,7 +246,7 @@ int track_enqueue(vc_engine* e, int st, const std::vector<std::vector<FrameClass
     TrackTask* ht = (TrackTask*)(s.h_in + o_tasks);
     for (int k = 0; k < n_tasks; ++k) {
         const TrackTaskHost& t = s.tasks[order[k]];
-        ht[k] = TrackTask{t.tracker, t.det_off, t.det_n, t.frame, t.label, 0, 0, 0};
+        ht[k] = TrackTask{t.tracker, t.det_off, t.det_n, t.frame, t.label, frame_dims ? frame_dims[t.frame].w : 0, frame_dims ? frame_dims[t.frame].h : 0, 0};
     }
     memcpy(s.h_in + o_plans, plans.data(), (size_t)n_wg * sizeof(TrackWgPlan));
     {

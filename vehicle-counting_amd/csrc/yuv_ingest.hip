@@ -225,12 +225,9 @@ __device__ __forceinline__ void frame_block(const uint8_t* __restrict__ sf, uint
     }
 }
 
-// grid: x = the frame's lanes (row pair, 16-pixel column group) in blocks of 256, y = frame.  dst: frame f at dst + f * h * w * 3.
-__global__ __launch_bounds__(256) void frames_to_bgr_kernel(const FrameEntry* __restrict__ tab, uint8_t* __restrict__ dst, int h, int w, int ncg) {
-    const FrameEntry e = tab[blockIdx.y];                   // workgroup-uniform
-    if (e.kind == FRAME_NONE) return;
+// one frame of a table-driven batch: this lane's share of entry e (workgroup-uniform), converted or copied into the frame at df
+__device__ __forceinline__ void frame_convert(const FrameEntry& e, uint8_t* __restrict__ df, int h, int w, int ncg) {
     const size_t frame_bytes = (size_t)h * w * 3;
-    uint8_t* df = dst + (size_t)blockIdx.y * frame_bytes;
     const int lid = blockIdx.x * 256 + threadIdx.x;
     if (e.kind == FRAME_BGR) {                              // the frame's lanes stride over its bytes: <= 96 bytes each, as on the YUV side
         const size_t step = (size_t)gridDim.x * 256;
@@ -255,6 +252,28 @@ __global__ __launch_bounds__(256) void frames_to_bgr_kernel(const FrameEntry* __
         if (e.fast) frame_block<false, true>(e.src, df, k, rp, cg);
         else frame_block<false, false>(e.src, df, k, rp, cg);
     }
+}
+
+// grid: x = the frame's lanes (row pair, 16-pixel column group) in blocks of 256, y = frame.  dst: frame f at dst + f * h * w * 3.
+__global__ __launch_bounds__(256) void frames_to_bgr_kernel(const FrameEntry* __restrict__ tab, uint8_t* __restrict__ dst, int h, int w, int ncg) {
+    const FrameEntry e = tab[blockIdx.y];                   // workgroup-uniform
+    if (e.kind == FRAME_NONE) return;
+    frame_convert(e, dst + (size_t)blockIdx.y * ((size_t)h * w * 3), h, w, ncg);
+}
+
+// Sized batches (include/vcount_hip.h): a second table beside the first gives every frame its own size and its cell in dst.  The grid's
+// x extent covers the largest frame; workgroups past a smaller frame's own lanes exit.
+struct FrameCell {
+    unsigned long long dst_off;                             // f * cell
+    int h, w;
+};
+static_assert(sizeof(FrameCell) == 16, "FrameCell is copied to the device as plain bytes");
+
+__global__ __launch_bounds__(256) void frames_to_bgr_sized_kernel(const FrameEntry* __restrict__ tab, const FrameCell* __restrict__ cells, uint8_t* __restrict__ dst) {
+    const FrameEntry e = tab[blockIdx.y];                   // workgroup-uniform
+    if (e.kind == FRAME_NONE) return;
+    const FrameCell c = cells[blockIdx.y];
+    frame_convert(e, dst + c.dst_off, c.h, c.w, (c.w + 15) >> 4);
 }
 
 }  // namespace
@@ -379,6 +398,66 @@ int launch_frames_to_bgr(const FrameEntry* d_tab, uint8_t* dst, int b, int h, in
     const long long blocks = (lanes + 255) / 256;
     VC_CHECK(b <= 65535 && blocks <= 0x7fffffll, VC_ERR_CAPACITY, "batch too large for one conversion launch");
     hipLaunchKernelGGL(frames_to_bgr_kernel, dim3((unsigned)blocks, (unsigned)b), dim3(256), 0, s, d_tab, dst, h, w, ncg);
+    VC_HIP(hipGetLastError());
+    return VC_OK;
+}
+
+
+// The validation of a sized frame list (pure host code, before any HIP call): frames_resolve with every frame's own size, plus the rule
+// that makes the batch one detector pass -- every frame's own network shape is that of frame 0.
+struct SizedLayout { size_t cell = 0; int net_h = 0, net_w = 0, max_h = 0, max_w = 0; };
+int frames_resolve_sized(const vc_frame_src* frames, const vc_frame_dims* dims, int b, int img_size, bool host_only, std::vector<YuvGeom>& geo, int64_t* raw_off,
+                         size_t* raw_bytes, SizedLayout& lay) {
+    VC_CHECK(b >= 1, VC_ERR_ARG, "bad batch of %d frames", b);
+    VC_CHECK(frames && dims, VC_ERR_ARG, "null frame list");
+    VC_CHECK(img_size >= 1, VC_ERR_ARG, "bad img_size %d", img_size);
+    geo.assign((size_t)b, YuvGeom{});
+    lay = SizedLayout{};
+    size_t cur = 0;
+    int nh0 = 0, nw0 = 0;
+    for (int f = 0; f < b; ++f) {
+        const vc_frame_src& s = frames[f];
+        const int h = dims[f].h, w = dims[f].w;
+        VC_CHECK(h >= 1 && w >= 1 && h <= (1 << 15) && w <= (1 << 15), VC_ERR_ARG, "frame %d: bad frame size %dx%d", f, h, w);
+        VC_CHECK(s.kind == VC_SRC_BGR_HOST || s.kind == VC_SRC_BGR_DEV || s.kind == VC_SRC_YUV_HOST || s.kind == VC_SRC_YUV_DEV, VC_ERR_ARG,
+                 "frame %d: unknown source kind %d (VC_SRC_*)", f, s.kind);
+        VC_CHECK(!host_only || s.kind == VC_SRC_BGR_HOST || s.kind == VC_SRC_YUV_HOST, VC_ERR_ARG, "frame %d: a device source (kind %d) where host frames are expected", f, s.kind);
+        VC_CHECK(s.data, VC_ERR_ARG, "frame %d: null data", f);
+        int nh, nw;
+        autoshape_net_size(&h, &w, 1, img_size, nh, nw);
+        if (f == 0) { nh0 = nh; nw0 = nw; }
+        VC_CHECK(nh == nh0 && nw == nw0, VC_ERR_ARG, "frame %d: %dx%d runs at %dx%d, frame 0 at %dx%d", f, h, w, nh, nw, nh0, nw0);
+        if (raw_off) raw_off[f] = -1;
+        lay.cell = std::max(lay.cell, (size_t)h * w * 3);
+        lay.max_h = std::max(lay.max_h, h); lay.max_w = std::max(lay.max_w, w);
+        if (s.kind != VC_SRC_YUV_HOST && s.kind != VC_SRC_YUV_DEV) continue;
+        vc_yuv_desc d = s.desc;
+        d.frame_stride = 0;                                 // one frame: the stride has no meaning here
+        if (yuv_resolve(&d, 1, h, w, geo[f]) != VC_OK) {
+            char msg[400];
+            snprintf(msg, sizeof(msg), "%s", last_error());
+            set_error("frame %d: %s", f, msg);
+            return VC_ERR_ARG;
+        }
+        if (s.kind == VC_SRC_YUV_HOST) {
+            cur = (cur + 15) / 16 * 16;
+            if (raw_off) raw_off[f] = (int64_t)cur;
+            cur += yuv_batch_bytes(geo[f], 1);
+        }
+    }
+    lay.cell = (lay.cell + 15) / 16 * 16;
+    lay.net_h = nh0; lay.net_w = nw0;
+    if (raw_bytes) *raw_bytes = cur;
+    return VC_OK;
+}
+
+// d_tab: b entries, d_cells: b cells, both in device memory; dst: b cells of device memory
+int launch_frames_to_bgr_sized(const FrameEntry* d_tab, const FrameCell* d_cells, uint8_t* dst, int b, const vc_frame_dims* dims, hipStream_t s) {
+    long long lanes = 1;                                                       // of the largest frame
+    for (int f = 0; f < b; ++f) lanes = std::max(lanes, (long long)((dims[f].h + 1) / 2) * ((dims[f].w + 15) / 16));
+    const long long blocks = (lanes + 255) / 256;
+    VC_CHECK(b <= 65535 && blocks <= 0x7fffffll, VC_ERR_CAPACITY, "batch too large for one conversion launch");
+    hipLaunchKernelGGL(frames_to_bgr_sized_kernel, dim3((unsigned)blocks, (unsigned)b), dim3(256), 0, s, d_tab, d_cells, dst);
     VC_HIP(hipGetLastError());
     return VC_OK;
 }
@@ -586,6 +665,135 @@ int vc_stream_stage_frames(vc_engine* e, const vc_frame_src* frames, int b, int 
         VC_HIP(hipMemcpyAsync(e->d_frame_tab[slot], tab, (size_t)b * sizeof(FrameEntry), hipMemcpyHostToDevice, e->cstream));
         VC_TRY(launch_frames_to_bgr((const FrameEntry*)e->d_frame_tab[slot], e->d_ingest[slot], b, h, w, e->cstream));
     }
+    return ingest_publish(e, slot, frames_dev_out);
+}
+
+// ---- sized batches -------------------------------------------------------------------------------------------------------------------
+int vc_autoshape_net_size(int h, int w, int img_size, int* net_h, int* net_w) {
+    VC_CHECK(net_h && net_w, VC_ERR_ARG, "null argument");
+    VC_CHECK(h >= 1 && w >= 1 && img_size >= 1, VC_ERR_ARG, "bad image %dx%d at size %d", h, w, img_size);
+    autoshape_net_size(&h, &w, 1, img_size, *net_h, *net_w);
+    return VC_OK;
+}
+
+int vc_frames_layout_sized_host(const vc_frame_src* frames, const vc_frame_dims* dims, int b, int img_size, int64_t* raw_off, size_t* raw_bytes, size_t* cell,
+                                int* net_h, int* net_w) {
+    VC_CHECK(raw_off && raw_bytes && cell && net_h && net_w, VC_ERR_ARG, "null argument");
+    std::vector<YuvGeom> geo;
+    SizedLayout lay;
+    VC_TRY(frames_resolve_sized(frames, dims, b, img_size, false, geo, raw_off, raw_bytes, lay));
+    *cell = lay.cell; *net_h = lay.net_h; *net_w = lay.net_w;
+    return VC_OK;
+}
+
+// Parity entry point of frames_to_bgr_sized_kernel.  The caller's cells are uploaded between two guard blocks, converted into and read
+// back: what the kernel leaves alone inside a cell comes back as the caller filled it.  Frames are uploaded to addresses congruent to
+// their host pointers mod 16, as in vc_frames_to_bgr_host.  Network shapes are not compared here (img_size 1 gives every frame 32 x 32).
+int vc_frames_to_bgr_sized_host(const vc_frame_src* frames, const vc_frame_dims* dims, int b, uint8_t* cells) {
+    VC_CHECK(cells, VC_ERR_ARG, "null argument");
+    std::vector<YuvGeom> geo;
+    SizedLayout lay;
+    VC_TRY(frames_resolve_sized(frames, dims, b, 1, true, geo, nullptr, nullptr, lay));
+    const size_t out_bytes = (size_t)b * lay.cell, guard = 256;
+    std::vector<size_t> off((size_t)b), len((size_t)b);
+    size_t in_bytes = 0;
+    for (int f = 0; f < b; ++f) {
+        len[f] = frames[f].kind == VC_SRC_YUV_HOST ? yuv_batch_bytes(geo[f], 1) : (size_t)dims[f].h * dims[f].w * 3;
+        off[f] = (in_bytes + 15) / 16 * 16 + (uintptr_t)frames[f].data % 16;
+        in_bytes = off[f] + len[f];
+    }
+    vc_engine tmp;
+    uint8_t *ds = nullptr, *dd = nullptr, *dt = nullptr;
+    const size_t tab_bytes = (size_t)b * (sizeof(FrameEntry) + sizeof(FrameCell));
+    int st = dev_alloc(&tmp, (void**)&ds, in_bytes);
+    if (st == VC_OK) st = dev_alloc(&tmp, (void**)&dd, out_bytes + 2 * guard);
+    if (st == VC_OK) st = dev_alloc(&tmp, (void**)&dt, tab_bytes);
+    if (st == VC_OK) {
+        std::vector<uint8_t> tabs(tab_bytes);
+        FrameEntry* tab = (FrameEntry*)tabs.data();
+        FrameCell* cl = (FrameCell*)(tabs.data() + (size_t)b * sizeof(FrameEntry));
+        bool ok = hipMemset(dd, 0xA5, out_bytes + 2 * guard) == hipSuccess && hipMemcpy(dd + guard, cells, out_bytes, hipMemcpyHostToDevice) == hipSuccess;
+        for (int f = 0; f < b && ok; ++f) {
+            ok = hipMemcpy(ds + off[f], frames[f].data, len[f], hipMemcpyHostToDevice) == hipSuccess;
+            tab[f] = frame_entry(frames[f].kind, geo[f], ds + off[f], dd + guard + (size_t)f * lay.cell, dims[f].h, dims[f].w);
+            cl[f] = FrameCell{(unsigned long long)f * lay.cell, dims[f].h, dims[f].w};
+        }
+        if (!ok || hipMemcpy(dt, tabs.data(), tab_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            set_error("upload failed");
+            st = VC_ERR_HIP;
+        }
+    }
+    if (st == VC_OK) st = launch_frames_to_bgr_sized((const FrameEntry*)dt, (const FrameCell*)(dt + (size_t)b * sizeof(FrameEntry)), dd + guard, b, dims, nullptr);
+    if (st == VC_OK) {
+        uint8_t edge[512];
+        if (hipMemcpy(cells, dd + guard, out_bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(edge, dd, guard, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(edge + guard, dd + guard + out_bytes, guard, hipMemcpyDeviceToHost) != hipSuccess) {
+            set_error("frames_to_bgr_sized_kernel failed: %s", hipGetErrorString(hipGetLastError()));
+            st = VC_ERR_HIP;
+        }
+        for (size_t i = 0; i < 2 * guard && st == VC_OK; ++i)
+            if (edge[i] != 0xA5) { set_error("frames_to_bgr_sized_kernel wrote outside its output (guard byte %zu)", i); st = VC_ERR_HIP; }
+    }
+    for (void* q : tmp.allocs) (void)hipFree(q);
+    tmp.allocs.clear();
+    return st;
+}
+
+// vc_stream_stage_frames with every frame's own size: frame f lands in cell f of the slot.  The per-slot tables hold the frame entries
+// followed by the cells, so one copy still carries both; a slot remembers the dims of its sized batch for vc_stream_submit_sized.
+int vc_stream_stage_frames_sized(vc_engine* e, const vc_frame_src* frames, const vc_frame_dims* dims, int b, void** frames_dev_out) {
+    VC_CHECK(e && frames_dev_out, VC_ERR_ARG, "null argument");
+    std::vector<YuvGeom> geo;
+    std::vector<int64_t> raw_off((size_t)std::max(b, 1));
+    size_t raw_bytes = 0;
+    SizedLayout lay;
+    VC_TRY(frames_resolve_sized(frames, dims, b, e->cfg.img_size, false, geo, raw_off.data(), &raw_bytes, lay));
+    VC_CHECK(e->finalized && e->cfg.with_detector, VC_ERR_STATE, "engine not finalized");
+    VC_CHECK(b <= e->cfg.max_batch && lay.max_h <= e->cfg.max_frame_h && lay.max_w <= e->cfg.max_frame_w && (size_t)b * lay.cell <= ingest_slot_bytes(e), VC_ERR_CAPACITY,
+             "batch of %d frames up to %dx%d (%zu-byte cells) exceeds max_batch / max_frame_h / max_frame_w", b, lay.max_h, lay.max_w, lay.cell);
+    int slot = 0;
+    VC_TRY(ingest_take_slot(e, b, lay.max_h, lay.max_w, &slot));
+    const size_t entry_bytes = sizeof(FrameEntry) + sizeof(FrameCell);
+    if (!e->h_sized_tab[slot]) {
+        VC_TRY(host_alloc(e, &e->h_sized_tab[slot], (size_t)e->cfg.max_batch * entry_bytes));
+        VC_TRY(dev_alloc(e, &e->d_sized_tab[slot], (size_t)e->cfg.max_batch * entry_bytes));
+    }
+    if (raw_bytes > e->yuv_raw_bytes[slot]) {
+        // as in vc_stream_stage_yuv_host: everything the copy stream still has in flight reads the old buffer
+        VC_HIP(hipStreamSynchronize(e->cstream));
+        const size_t tight = (size_t)e->cfg.max_batch * e->cfg.max_frame_h * e->cfg.max_frame_w * 3 / 2;
+        e->yuv_raw_bytes[slot] = 0;
+        VC_TRY(dev_realloc(e, (void**)&e->d_yuv_raw[slot], std::max(raw_bytes, tight)));
+        e->yuv_raw_bytes[slot] = std::max(raw_bytes, tight);
+    }
+    FrameEntry* tab = (FrameEntry*)e->h_sized_tab[slot];
+    FrameCell* cl = (FrameCell*)((uint8_t*)e->h_sized_tab[slot] + (size_t)b * sizeof(FrameEntry));
+    bool launch = false;
+    for (int f = 0; f < b; ++f) {
+        const vc_frame_src& s = frames[f];
+        const int h = dims[f].h, w = dims[f].w;
+        uint8_t* dst = e->d_ingest[slot] + (size_t)f * lay.cell;
+        const uint8_t* src = (const uint8_t*)s.data;
+        cl[f] = FrameCell{(unsigned long long)f * lay.cell, h, w};
+        if (s.kind == VC_SRC_BGR_HOST) {
+            VC_HIP(hipMemcpyAsync(dst, s.data, (size_t)h * w * 3, hipMemcpyHostToDevice, e->cstream));
+            tab[f] = FrameEntry{};                          // FRAME_NONE: already in place
+            continue;
+        }
+        if (s.kind == VC_SRC_YUV_HOST) {
+            uint8_t* raw = e->d_yuv_raw[slot] + raw_off[f];
+            VC_HIP(hipMemcpyAsync(raw, s.data, yuv_batch_bytes(geo[f], 1), hipMemcpyHostToDevice, e->cstream));
+            src = raw;
+        }
+        tab[f] = frame_entry(s.kind, geo[f], src, dst, h, w);
+        launch = true;
+    }
+    if (launch) {
+        uint8_t* dt = (uint8_t*)e->d_sized_tab[slot];
+        VC_HIP(hipMemcpyAsync(dt, tab, (size_t)b * entry_bytes, hipMemcpyHostToDevice, e->cstream));
+        VC_TRY(launch_frames_to_bgr_sized((const FrameEntry*)dt, (const FrameCell*)(dt + (size_t)b * sizeof(FrameEntry)), e->d_ingest[slot], b, dims, e->cstream));
+    }
+    e->ingest_dims[slot].assign(dims, dims + b);
     return ingest_publish(e, slot, frames_dev_out);
 }
 

@@ -340,6 +340,32 @@ class Engine:
         L.check(L.lib().vc_stream_stage_frames(self._h, arr, len(frames), h, w, C.byref(out)))
         return out.value
 
+    # ---------------------------------------------------------------- sized batches: cameras of different frame sizes in one batch
+    def stream_stage_frames_sized(self, frames, dims):
+        """`stream_stage_frames` for a sized batch: frame f has its own size dims[f] = (h, w); all frames must run at one network
+        shape (`autoshape_net_size` of each alone).  Frame f lands as tight BGR in cell f of an ingest slot (`frames_layout_sized`
+        gives the cell size).  Returns the device address of the cells for stream_submit_sized / stream_run_async_multi_sized."""
+        out = C.c_void_p()
+        L.check(L.lib().vc_stream_stage_frames_sized(self._h, _frame_array(frames), _dims_array(dims), len(frames), C.byref(out)))
+        return out.value
+
+    def stream_submit_sized(self, frames_dev_ptr, dims):
+        """Enqueue the detector for a sized batch (a staged one or the caller's own device buffer laid out in cells)."""
+        L.check(L.lib().vc_stream_submit_sized(self._h, C.c_void_p(frames_dev_ptr), _dims_array(dims), len(dims)))
+
+    def stream_run_async_multi_sized(self, tracker_ids, cam_of_frame, frames_dev_ptr, dims, cap_rows=512):
+        """`stream_run_async_multi` for a sized batch; within the batch all frames of one camera have one size (the size that
+        camera's track boxes are clamped to).  Rows are collected with `stream_collect`."""
+        tr = np.ascontiguousarray(tracker_ids, dtype=np.int32)
+        assert tr.ndim == 2, "tracker_ids must be [n_cam][num_classes]"
+        b = len(dims)
+        cams = np.ascontiguousarray(cam_of_frame, dtype=np.int32).reshape(-1)
+        assert len(cams) == b
+        L.check(L.lib().vc_stream_run_async_multi_sized(self._h, L.ptr(tr, C.c_int), tr.shape[0], tr.shape[1], L.ptr(cams, C.c_int),
+                                                        C.c_void_p(frames_dev_ptr), _dims_array(dims), b, cap_rows))
+        self._async_shapes = getattr(self, "_async_shapes", [])
+        self._async_shapes.append((b, cap_rows))
+
     # ---------------------------------------------------------------- frame-sharded front end (one stream on several GPUs)
     def stream_embed(self, frames_dev_ptr, b, h, w):
         """Front half of the fused path for the oldest submission: (rows [n, 7] float64 = frame index in the batch, x1, y1, x2, y2,
@@ -568,6 +594,67 @@ def frames_to_bgr(frames, h, w, out=None):
     assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.size >= b * h * w * 3
     dst = C.cast(out.ctypes.data, C.POINTER(C.c_uint8))
     L.check(L.lib().vc_frames_to_bgr_host(_frame_array(frames), b, h, w, dst))
+    return out
+
+
+def _dims_array(dims):
+    return (L.FrameDims * max(len(dims), 1))(*[L.FrameDims(int(h), int(w)) for h, w in dims])
+
+
+def autoshape_net_size(h, w, img_size=640):
+    """vc_autoshape_net_size: the (net_h, net_w) AutoShape gives ONE h x w image at `img_size` -- frames of a sized batch must agree on it."""
+    nh, nw = C.c_int(), C.c_int()
+    L.check(L.lib().vc_autoshape_net_size(int(h), int(w), int(img_size), C.byref(nh), C.byref(nw)))
+    return nh.value, nw.value
+
+
+def frames_layout_sized(frames, dims, img_size=640):
+    """vc_frames_layout_sized_host: validates a sized frame list like `Engine.stream_stage_frames_sized` does (no GPU needed) and returns
+    (raw_off, raw_bytes, cell, (net_h, net_w))."""
+    b = len(frames)
+    off, total, cell, nh, nw = np.full(max(b, 1), -2, np.int64), C.c_size_t(0), C.c_size_t(0), C.c_int(), C.c_int()
+    L.check(L.lib().vc_frames_layout_sized_host(_frame_array(frames), _dims_array(dims), b, int(img_size), L.ptr(off, C.c_int64), C.byref(total),
+                                                C.byref(cell), C.byref(nh), C.byref(nw)))
+    return off[:b], total.value, cell.value, (nh.value, nw.value)
+
+
+def frames_to_bgr_sized(frames, dims, cells):
+    """The sized ingest kernel on host arrays: `cells` (uint8, b * cell bytes, C-contiguous) is converted into IN PLACE -- frame f tight at
+    f * cell, every other byte as the caller left it."""
+    assert cells.dtype == np.uint8 and cells.flags["C_CONTIGUOUS"]
+    L.check(L.lib().vc_frames_to_bgr_sized_host(_frame_array(frames), _dims_array(dims), len(frames), C.cast(cells.ctypes.data, C.POINTER(C.c_uint8))))
+    return cells
+
+
+def letterbox_frames(frames, net_h, net_w, swap_rb=False, precision="f32"):
+    """letterbox_frames_kernel on host arrays: ONE launch for frames (h_f, w_f, 3) uint8 of different sizes -> (b, net_h, net_w, 3) float32."""
+    ims = [np.ascontiguousarray(im, dtype=np.uint8) for im in frames]
+    ptrs = (C.c_void_p * len(ims))(*[im.ctypes.data for im in ims])
+    out = np.zeros((len(ims), net_h, net_w, 3), np.float32)
+    L.check(L.lib().vc_letterbox_frames_host(ptrs, _dims_array([im.shape[:2] for im in ims]), len(ims), net_h, net_w, 1 if swap_rb else 0,
+                                             L.PREC_BF16 if precision == "bf16" else L.PREC_F32, L.ptr(out, C.c_float)))
+    return out
+
+
+def letterbox_dev(frames_dev_ptr, b, h, w, net_h, net_w, out_dev_ptr, *, swap_rb=True, precision="bf16", table_dev_ptr=None, mode=0):
+    """The letterbox kernels on the caller's device buffers (integer addresses), enqueued on the null stream; returns without waiting.
+    mode 0: the kernels a uniform batch runs; 1: build the per-frame table in table_dev_ptr (b * 64 bytes) and run letterbox_frames_kernel;
+    2: that kernel with the table as mode 1 left it (the kernel alone, for measurement)."""
+    L.check(L.lib().vc_letterbox_dev(C.c_void_p(frames_dev_ptr), b, h, w, net_h, net_w, 1 if swap_rb else 0, L.PREC_BF16 if precision == "bf16" else L.PREC_F32,
+                                     C.c_void_p(out_dev_ptr), C.c_void_p(table_dev_ptr) if table_dev_ptr else None, mode))
+
+
+def crop_resize_frames(frames, frame_of_box, boxes_cxcywh):
+    """The ReID crop kernel with the per-frame table on host arrays: box i is cut from frames[frame_of_box[i]] (BGR uint8, own size) ->
+    (k, 50, 50, 3) float32, the network input `Engine.embed_input` shows for that frame alone."""
+    ims = [np.ascontiguousarray(im, dtype=np.uint8) for im in frames]
+    ptrs = (C.c_void_p * len(ims))(*[im.ctypes.data for im in ims])
+    fob = np.ascontiguousarray(frame_of_box, dtype=np.int32).reshape(-1)
+    boxes = L.f64(boxes_cxcywh).reshape(-1, 4)
+    assert len(fob) == len(boxes)
+    out = np.zeros((len(boxes), 50, 50, 3), np.float32)
+    L.check(L.lib().vc_crop_resize_frames_host(ptrs, _dims_array([im.shape[:2] for im in ims]), len(ims), L.ptr(fob, C.c_int), L.ptr(boxes, C.c_double),
+                                               len(boxes), L.ptr(out, C.c_float)))
     return out
 
 

@@ -367,7 +367,7 @@ class CountingPipeline:
                 rnd.collect()
         return sink
 
-    def run_streams(self, sources, cam_names, zone_paths, batch=16, host_frames=False):
+    def run_streams(self, sources, cam_names, zone_paths, batch=16, host_frames=False, mixed_sizes=False):
         """S videos at once on ONE engine (the reference runs them one after another, each with a new VideoTracker,
         modules/__init__.py:28-36): the frames of the cameras are interleaved round-robin into batches of `batch` frames, the
         detector and the ReID net see one batch, every camera's frames are stepped on that camera's own trackers
@@ -378,9 +378,13 @@ class CountingPipeline:
         (host_frames=True) or its own device tensor -- and each batch is gathered from the cameras' own addresses on the device
         (`stream_stage_frames`, staged two batches ahead as in `run_stream`): no interleaved copy of the clips exists, cameras may
         differ in format, colour matrix, range, pitch and length, and a video of any length needs four batches of device memory
-        when its frames stay on the host."""
-        if host_frames or any(isinstance(s, YuvFrameSource) for s in sources):
-            return self._run_streams_frames(sources, cam_names, zone_paths, batch, host_frames)
+        when its frames stay on the host.
+        mixed_sizes=True: the cameras may also differ in frame size, as long as every camera's own AutoShape network shape
+        (`engine.autoshape_net_size`) is the same -- at size 640, 1920x1080, 1280x720, 640x360 and 320x180 all run at 384x640.  Each
+        batch is a sized batch (`stream_stage_frames_sized`): one detector pass, and every camera still gets the result of running
+        alone.  Cameras whose network shapes differ are refused; run each group of equal shapes in a call of its own."""
+        if mixed_sizes or host_frames or any(isinstance(s, YuvFrameSource) for s in sources):
+            return self._run_streams_frames(sources, cam_names, zone_paths, batch, host_frames, mixed_sizes)
         import torch
         S = len(sources)
         shapes = {s.frames.shape[1:] for s in sources}
@@ -426,7 +430,7 @@ class CountingPipeline:
                 record(starts[-1], *self.engine.stream_collect()[:2])
         return [self._finish(st[1], o, n) for st, o, n in zip(stages, objs, cam_names)]
 
-    def _run_streams_frames(self, sources, cam_names, zone_paths, batch, host_frames):
+    def _run_streams_frames(self, sources, cam_names, zone_paths, batch, host_frames, mixed_sizes=False):
         """run_streams over per-camera clips: camera c frame t is read at base_c + t * stride_c with that camera's descriptor."""
         import torch
 
@@ -434,7 +438,13 @@ class CountingPipeline:
         S = len(sources)
         yuv = [isinstance(s, YuvFrameSource) for s in sources]
         sizes = [(s.h, s.w) if y else tuple(s.frames.shape[1:3]) for s, y in zip(sources, yuv)]
-        if len(set(sizes)) != 1:
+        if mixed_sizes:
+            from .engine import autoshape_net_size
+            shapes = [autoshape_net_size(h, w, self.engine.cfg.img_size) for h, w in sizes]
+            if len(set(shapes)) != 1:
+                per_cam = ", ".join(f"{n}: {h}x{w} runs at {nh}x{nw}" for n, (h, w), (nh, nw) in zip(cam_names, sizes, shapes))
+                raise ValueError(f"run_streams(mixed_sizes=True): the cameras' network shapes differ ({per_cam}); run each group of equal shapes in its own call")
+        elif len(set(sizes)) != 1:
             raise ValueError(f"run_streams: all cameras must deliver frames of one size, got {sizes}")
         h, w = sizes[0]
         # each camera's clip where its decoder would leave it: one tensor per camera, never an interleaved copy
@@ -470,20 +480,34 @@ class CountingPipeline:
 
         def stage(n):
             f0, b = span(n)
-            ptr[n] = self.engine.stream_stage_frames([frame_src(kind[c], base[c] + t * stride[c], desc[c]) for c, t in order[f0:f0 + b]], h, w)
+            srcs = [frame_src(kind[c], base[c] + t * stride[c], desc[c]) for c, t in order[f0:f0 + b]]
+            ptr[n] = self.engine.stream_stage_frames_sized(srcs, dims(n)) if mixed_sizes else self.engine.stream_stage_frames(srcs, h, w)
+
+        def dims(n):
+            f0, b = span(n)
+            return [sizes[c] for c, _ in order[f0:f0 + b]]
+
+        def submit(n):
+            if mixed_sizes:
+                self.engine.stream_submit_sized(ptr[n], dims(n))
+            else:
+                self.engine.stream_submit(ptr[n], span(n)[1], h, w)
 
         with self._video(*[st[0] for st in stages]):
             for n in range(min(2, len(starts))):            # staging order = batch order (four slots, round-robin)
                 stage(n)
             if starts:
-                self.engine.stream_submit(ptr[0], span(0)[1], h, w)
+                submit(0)
             for n in range(len(starts)):
                 f0, b = span(n)
                 if n + 2 < len(starts):                     # gather batch n+2 under the detector of batch n+1
                     stage(n + 2)
                 if n + 1 < len(starts):
-                    self.engine.stream_submit(ptr[n + 1], span(n + 1)[1], h, w)
-                self.engine.stream_run_async_multi(tids, cams[f0:f0 + b], ptr[n], b, h, w)
+                    submit(n + 1)
+                if mixed_sizes:
+                    self.engine.stream_run_async_multi_sized(tids, cams[f0:f0 + b], ptr[n], dims(n))
+                else:
+                    self.engine.stream_run_async_multi(tids, cams[f0:f0 + b], ptr[n], b, h, w)
                 if n > 0:
                     record(starts[n - 1], *self.engine.stream_collect()[:2])
                 ptr.pop(n - 1, None)
