@@ -6,7 +6,8 @@
      alone (vc_letterbox_host), fp32 and bf16, with and without the R / B swap, and in fp32 against the oracle;
   3. the crop kernel with the per-frame table against vc_embed + vc_embed_debug_input on each frame alone;
   4. staging: cells read back as the reference frames, the slot rules and refusals of vc_stream_stage_frames, dims that differ between
-     stage / submit / run, and a sized batch of uniform frames tracks like vc_stream_stage_frames + vc_stream_run_async_multi;
+     stage / submit / run, a sized batch of uniform frames tracks like vc_stream_stage_frames + vc_stream_run_async_multi, and uniform
+     and sized batches that take turns in every slot (one table pair per slot serves both) stage the reference frames;
   5. run_streams(mixed_sizes=True) over four cameras of four sizes equals, per camera, run_stream of that camera alone."""
 import json
 import os
@@ -350,6 +351,99 @@ def test_sized_staging_follows_the_slot_rules(staged):
             np.testing.assert_array_equal(n0, n1, err_msg=name)
             np.testing.assert_array_equal(f0, f1, err_msg=name)
             np.testing.assert_array_equal(r0, r1, err_msg=name)
+
+
+def test_uniform_and_sized_batches_share_the_slot_tables(staged):
+    """Every ingest slot has ONE pinned / device table pair that serves both kinds of staged batch.  Twelve batches in the kinds
+    u s s u  s u u s  u s s u (u: stream_stage_frames, s: stream_stage_frames_sized) go through stage i + 2, submit i + 1, run i,
+    collect i - 1: with four slots, whatever the slot phase at entry, every slot holds u -> s -> u or s -> u -> s.  After each collect
+    the slot's bytes are the reference frames (uniform tight, sized in their cells), and all rows equal those of the same twelve
+    batches submitted as plain device batches of the reference frames (no staging, no table)."""
+    import torch
+    eng = staged.eng
+    pattern = "ussusuusussu"
+    nb = len(pattern)
+    slots = [[pattern[i] for i in range(nb) if i % 4 == ph] for ph in range(4)]
+    assert all(sl in (["u", "s", "u"], ["s", "u", "s"]) for sl in slots)
+    keep, sized_frames, dims, sized_want = four_sizes(staged.clip)
+    cell = cell_bytes(dims)
+    uni = [(H, W)] * B
+    fb = H * W * 3
+    nv12 = bgr_to_yuv420(staged.clip, "nv12")
+    host_nv12 = torch.from_numpy(nv12).pin_memory()
+    ref_clip = staged.clip.copy()
+    ref_clip[0::2] = yuv_ref.yuv_to_bgr(nv12, len(nv12), H, W, "nv12")[0::2]          # even frames arrive as NV12, odd ones as BGR
+    # the uniform batches walk through the clip in order (and once more): B is even, so the parity of j is that of the clip index
+    clip_idx = lambda i: [(pattern[:i].count("u") * B + j) % (B * NB) for j in range(B)]
+
+    def uniform_frames(i):
+        return [E.frame_src("yuv_host", host_nv12[k].data_ptr(), E.yuv_desc("nv12")) if k % 2 == 0 else E.frame_src("bgr_dev", staged.dev_bgr.data_ptr() + k * fb)
+                for k in clip_idx(i)]
+
+    # the reference batches in device memory: uniform ones tight, the sized one in its cells
+    ref_uniform = {i: torch.from_numpy(ref_clip[clip_idx(i)]).cuda() for i in range(nb) if pattern[i] == "u"}
+    cells = np.zeros((B, cell), np.uint8)
+    for f, (h, w) in enumerate(dims):
+        cells[f, : h * w * 3] = sized_want[f].reshape(-1)
+    ref_sized = torch.from_numpy(cells).cuda()
+    many = np.array([[eng.tracker_create(max_dist=0.2, min_confidence=0.25, nms_max_overlap=0.5, max_iou_distance=0.6, max_age=30, n_init=3, nn_budget=60)
+                      for _ in range(NC)] for _ in range(4)], np.int32)
+    own_cam, one_cam = np.arange(B, dtype=np.int32), np.zeros(B, np.int32)
+
+    def run(staging):
+        eng.stream_reset()
+        for t in many.reshape(-1):
+            eng.tracker_reset(int(t))
+        ptrs, got = {}, []
+
+        def stage(i):
+            if not staging:
+                ptrs[i] = (ref_sized if pattern[i] == "s" else ref_uniform[i]).data_ptr()
+            elif pattern[i] == "s":
+                ptrs[i] = eng.stream_stage_frames_sized(sized_frames, dims)
+            else:
+                ptrs[i] = eng.stream_stage_frames(uniform_frames(i), H, W)
+
+        submit = lambda i: eng.stream_submit_sized(ptrs[i], dims) if pattern[i] == "s" else eng.stream_submit(ptrs[i], B, H, W)
+
+        def collect(i):
+            got.append(eng.stream_collect())
+            if not staging:
+                return
+            torch.cuda.synchronize()                                                    # the slot is restaged by stage(i + 4) at the earliest
+            if pattern[i] == "s":
+                slot = read_bytes(ptrs[i], B * cell).reshape(B, cell)
+                for f, (h, w) in enumerate(dims):
+                    np.testing.assert_array_equal(slot[f, : h * w * 3].reshape(h, w, 3), sized_want[f], err_msg=f"batch {i} (sized) frame {f}")
+            else:
+                np.testing.assert_array_equal(read_bytes(ptrs[i], B * fb).reshape(B, H, W, 3), ref_clip[clip_idx(i)], err_msg=f"batch {i} (uniform)")
+
+        stage(0); stage(1)
+        submit(0)
+        for i in range(nb):
+            if i + 2 < nb:
+                stage(i + 2)
+            if i + 1 < nb:
+                submit(i + 1)
+            if pattern[i] == "s":
+                eng.stream_run_async_multi_sized(many, own_cam, ptrs[i], dims)
+            else:
+                eng.stream_run_async_multi(many, one_cam, ptrs[i], B, H, W)
+            if i > 0:
+                collect(i - 1)
+        collect(nb - 1)
+        return got
+
+    plain, mixed = run(False), run(True)
+    assert sum(len(r[0]) for i, r in enumerate(plain) if pattern[i] == "u") > 0          # not empty against empty
+    for i, ((r0, f0, n0), (r1, f1, n1)) in enumerate(zip(plain, mixed)):
+        np.testing.assert_array_equal(n0, n1, err_msg=f"batch {i} ({pattern[i]})")
+        np.testing.assert_array_equal(f0, f1, err_msg=f"batch {i} ({pattern[i]})")
+        np.testing.assert_array_equal(r0, r1, err_msg=f"batch {i} ({pattern[i]})")
+    eng.stream_reset()
+    for t in many.reshape(-1):
+        eng.tracker_destroy(int(t))
+    del keep
 
 
 # ---- 5. run_streams ----------------------------------------------------------------------------------------------------------------

@@ -194,13 +194,11 @@ struct vc_engine {
     // YUV ingest (yuv_ingest.hip): raw 4:2:0 bytes of vc_stream_stage_yuv_host, one buffer per ingest slot, allocated by its first call
     uint8_t* d_yuv_raw[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t yuv_raw_bytes[4] = {0, 0, 0, 0};
-    // frame-table ingest (yuv_ingest.hip: vc_stream_stage_frames): per slot a pinned table of max_batch entries and its device mirror, allocated by the first call
+    // frame-table ingest (yuv_ingest.hip: vc_stream_stage_frames[_sized]): per slot a pinned table and its device mirror, allocated by the
+    // first call -- max_batch frame entries followed, for a sized batch, by its cells; and the dims of the sized batch the slot holds
+    // (empty: a uniform batch)
     void* h_frame_tab[4] = {nullptr, nullptr, nullptr, nullptr};
     void* d_frame_tab[4] = {nullptr, nullptr, nullptr, nullptr};
-    // sized batches (vc_stream_stage_frames_sized): per slot the frame entries followed by the cells, pinned + device mirror, and the dims
-    // of the sized batch the slot holds (empty: a uniform batch)
-    void* h_sized_tab[4] = {nullptr, nullptr, nullptr, nullptr};
-    void* d_sized_tab[4] = {nullptr, nullptr, nullptr, nullptr};
     std::vector<vc_frame_dims> ingest_dims[4];
     // ... their letterbox table (engine_run.hip: run_detector_dev_sized): two pinned slots like h_geom, one device table (detector stream order)
     vc::LetterboxFrame* h_lb_tab = nullptr;      // pinned [2][max_batch]
@@ -225,6 +223,7 @@ struct vc_engine {
         const void* frames; int b, h, w, slot;
         std::vector<vc_frame_dims> dims; // a sized batch: every frame's own size (h, w above: the largest), frame f at frames + f * cell; empty: a uniform batch
         size_t cell = 0;
+        vc_frame_dims frame_dims(int f) const { return dims.empty() ? vc_frame_dims{h, w} : dims[f]; }   // the size of frame f
         int stage = 0;                   // 0: detector enqueued, 1: ReID enqueued as well
         bool embed_refused = false;      // a look-ahead attempt to embed this batch failed; the call that consumes it reports why (stream.hip)
         int fslot = 0;                   // feature / crop buffer of this batch
@@ -313,7 +312,29 @@ struct vc_engine {
 
 namespace vc {
 // engine.hip
-int dev_alloc(vc_engine* e, void** p, size_t bytes);
+int dev_alloc(std::vector<void*>& allocs, void** p, size_t bytes);   // the one allocation routine: hipMalloc, recorded in `allocs`
+inline int dev_alloc(vc_engine* e, void** p, size_t bytes) { return dev_alloc(e->allocs, p, bytes); }
+// Device scratch memory of the stateless host-array entry points (vc_*_host): freed when the owner goes out of scope, so every early
+// VC_TRY / VC_HIP / VC_CHECK return releases it.
+struct DevScratch {
+    std::vector<void*> allocs;
+    DevScratch() = default;
+    DevScratch(const DevScratch&) = delete;
+    DevScratch& operator=(const DevScratch&) = delete;
+    ~DevScratch() { for (void* q : allocs) (void)hipFree(q); }
+    template <class T> int alloc(T** p, size_t bytes) { return dev_alloc(allocs, (void**)p, bytes); }
+};
+// The device output of a parity entry point between two guard blocks that read_back checks: a kernel that wrote outside its output is
+// reported instead of returning a plausible result.
+struct GuardedOut {
+    static constexpr size_t kGuard = 256;
+    uint8_t* base = nullptr;
+    size_t bytes = 0;
+    // out_bytes + 2 guard blocks, all 0xA5; with `preload` the output starts as the caller's array
+    int alloc(DevScratch& mem, size_t out_bytes, const uint8_t* preload = nullptr);
+    uint8_t* out() const { return base + kGuard; }
+    int read_back(uint8_t* host_out, const char* kernel) const;      // waits for the null stream; `kernel` names the culprit
+};
 int dev_realloc(vc_engine* e, void** p, size_t bytes);            // frees *p (if it belongs to the engine) and allocates anew
 int host_alloc(vc_engine* e, void** p, size_t bytes);
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
@@ -349,6 +370,10 @@ size_t ingest_slot_bytes(const vc_engine* e);
 int ingest_publish(vc_engine* e, int slot, void** frames_dev_out);
 // yuv_ingest.hip / yuv_egress.hip: descriptor validation (pure host code) and the two conversions, both enqueued on `s`
 int yuv_resolve(const vc_yuv_desc* d, int b, int h, int w, YuvGeom& g);
+// The rules of a sized batch (pure host code): every size in 1 .. 1 << 15, every frame's own network shape at img_size that of frame 0;
+// the cell (the largest frame, rounded up to 16 bytes) and the largest height and width.  Capacities are the caller's to check.
+struct SizedDims { size_t cell = 0; int net_h = 0, net_w = 0, max_h = 0, max_w = 0; };
+int sized_dims_resolve(const vc_frame_dims* dims, int b, int img_size, SizedDims& out);
 size_t yuv_batch_bytes(const YuvGeom& g, int b);
 int launch_yuv_to_bgr(const YuvGeom& g, const uint8_t* src, uint8_t* dst, int b, hipStream_t s);
 int launch_bgr_to_yuv(const YuvGeom& g, const uint8_t* src_bgr, uint8_t* dst_yuv, int b, hipStream_t s);

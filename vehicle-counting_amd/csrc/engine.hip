@@ -19,10 +19,27 @@ void set_error(const char* fmt, ...) {
 }
 const char* last_error() { return g_err; }
 
-int dev_alloc(vc_engine* e, void** p, size_t bytes) {
+int dev_alloc(std::vector<void*>& allocs, void** p, size_t bytes) {
     if (bytes == 0) bytes = 16;
     VC_HIP(hipMalloc(p, bytes));
-    e->allocs.push_back(*p);
+    allocs.push_back(*p);
+    return VC_OK;
+}
+int GuardedOut::alloc(DevScratch& mem, size_t out_bytes, const uint8_t* preload) {
+    bytes = out_bytes;
+    VC_TRY(mem.alloc(&base, bytes + 2 * kGuard));
+    VC_HIP(hipMemset(base, 0xA5, bytes + 2 * kGuard));
+    if (preload) VC_HIP(hipMemcpy(out(), preload, bytes, hipMemcpyHostToDevice));
+    return VC_OK;
+}
+int GuardedOut::read_back(uint8_t* host_out, const char* kernel) const {
+    uint8_t edge[2 * kGuard];
+    if (hipMemcpy(host_out, out(), bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(edge, base, kGuard, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(edge + kGuard, out() + bytes, kGuard, hipMemcpyDeviceToHost) != hipSuccess) {
+        set_error("%s failed: %s", kernel, hipGetErrorString(hipGetLastError()));
+        return VC_ERR_HIP;
+    }
+    for (size_t i = 0; i < 2 * kGuard; ++i) VC_CHECK(edge[i] == 0xA5, VC_ERR_HIP, "%s wrote outside its output (guard byte %zu)", kernel, i);
     return VC_OK;
 }
 // Replace *p (an allocation of this engine, or null) by a fresh block of `bytes`; the old block is freed.  The caller makes sure no
@@ -61,7 +78,7 @@ ProfScope::~ProfScope() {
 }
 
 // ------------------------------------------------------------------------------------------------ weights
-static int pack_and_upload(vc_engine* e, ConvParam& p, int prec, float act_scale = 1.0f) {
+static int pack_and_upload(std::vector<void*>& allocs, ConvParam& p, int prec, float act_scale = 1.0f) {
     VC_CHECK(p.set, VC_ERR_STATE, "parameter '%s' was never set", p.name.c_str());
     p.prec = prec;
     const int ch = prec == PREC_F32 ? 4 : prec == PREC_FP8 ? 16 : 8;
@@ -90,8 +107,8 @@ static int pack_and_upload(vc_engine* e, ConvParam& p, int prec, float act_scale
     std::vector<float> bias(p.cout_pad, 0.f);
     for (int n = 0; n < p.O; ++n) bias[n] = p.b[n];
     const size_t nel = packed.size();
-    VC_TRY(dev_alloc(e, &p.d_w, nel * elem_size(prec)));
-    VC_TRY(dev_alloc(e, (void**)&p.d_b, bias.size() * sizeof(float)));
+    VC_TRY(dev_alloc(allocs, &p.d_w, nel * elem_size(prec)));
+    VC_TRY(dev_alloc(allocs, (void**)&p.d_b, bias.size() * sizeof(float)));
     if (prec == PREC_F32) {
         VC_HIP(hipMemcpy(p.d_w, packed.data(), nel * 4, hipMemcpyHostToDevice));
     } else if (prec == PREC_FP8) {
@@ -108,7 +125,7 @@ static int pack_and_upload(vc_engine* e, ConvParam& p, int prec, float act_scale
         }
         for (size_t i = (size_t)p.O * p.Kp; i < nel; ++i) h[i] = 0;
         VC_HIP(hipMemcpy(p.d_w, h.data(), nel, hipMemcpyHostToDevice));
-        VC_TRY(dev_alloc(e, (void**)&p.d_scale, sc.size() * sizeof(float)));
+        VC_TRY(dev_alloc(allocs, (void**)&p.d_scale, sc.size() * sizeof(float)));
         VC_HIP(hipMemcpy(p.d_scale, sc.data(), sc.size() * 4, hipMemcpyHostToDevice));
     } else {
         std::vector<uint16_t> h(nel);
@@ -345,10 +362,10 @@ int vc_engine_finalize(vc_engine* e) {
             ConvParam& cp = e->yolo.params[i];
             // fp8 mode: every detector conv but the 3-channel stem (Cin must be a multiple of 16 for 16-byte K chunks)
             const bool fp8 = e->prec == PREC_FP8 && cp.I % 16 == 0;
-            VC_TRY(pack_and_upload(e, cp, fp8 ? (int)PREC_FP8 : e->aux_prec, e->act_scale));
+            VC_TRY(pack_and_upload(e->allocs, cp, fp8 ? (int)PREC_FP8 : e->aux_prec, e->act_scale));
         }
     }
-    for (auto& p : e->reid.params) VC_TRY(pack_and_upload(e, p, e->aux_prec));
+    for (auto& p : e->reid.params) VC_TRY(pack_and_upload(e->allocs, p, e->aux_prec));
     e->d_frames_bytes = (size_t)e->cfg.max_batch * e->cfg.max_frame_h * e->cfg.max_frame_w * 3;     // staging for host frames
     VC_TRY(dev_alloc(e, (void**)&e->d_frames, e->d_frames_bytes));
     if (e->cfg.with_detector) VC_TRY(yolo_alloc(e));
@@ -670,12 +687,12 @@ int vc_profile_conv_busy(vc_engine* e, double* union_ms, double* span_ms) {
 int vc_conv2d_host(const vc_conv_desc* d, const float* x, const float* w, const float* bias, const float* res, float* y) {
     VC_CHECK(d && x && w && bias && y, VC_ERR_ARG, "null argument");
     const int prec = d->precision, es = elem_size(prec), ch = prec == PREC_F32 ? 4 : prec == PREC_FP8 ? 16 : 8;
-    vc_engine tmp;                           // only used as an allocation list
+    DevScratch mem;
     ConvParam p;
     p.name = "host"; p.O = d->cout; p.I = d->cin; p.kh = d->kh; p.kw = d->kw; p.set = true;
     p.w.assign(w, w + (size_t)d->cout * d->cin * d->kh * d->kw);
     p.b.assign(bias, bias + d->cout);
-    int st = pack_and_upload(&tmp, p, prec);
+    VC_TRY(pack_and_upload(mem.allocs, p, prec));
     const int cin_eff = p.cin_eff;
     const int Ho = (d->h + 2 * d->pad - d->kh) / d->stride + 1, Wo = (d->w + 2 * d->pad - d->kw) / d->stride + 1;
     const size_t npix_in = (size_t)d->b * d->h * d->w, npix_out = (size_t)d->b * Ho * Wo;
@@ -689,14 +706,15 @@ int vc_conv2d_host(const vc_conv_desc* d, const float* x, const float* w, const 
                 else if (es == 2) ((uint16_t*)buf.data())[i * Cs + c] = f32_to_bf16(src[i * C + c]);
                 else buf[i * Cs + c] = f32_to_e4m3(src[i * C + c]);                 // activation scale 1
             }
-        VC_TRY(dev_alloc(&tmp, dst, buf.size()));
+        VC_TRY(mem.alloc(dst, buf.size()));
         VC_HIP(hipMemcpy(*dst, buf.data(), buf.size(), hipMemcpyHostToDevice));
         return VC_OK;
     };
-    if (st == VC_OK) st = upload(x, npix_in, d->cin, cin_eff, &dx);
-    if (st == VC_OK && res) st = upload(res, npix_out, d->cout, cout_s, &dr);
-    if (st == VC_OK) st = dev_alloc(&tmp, &dy, npix_out * cout_s * es);
-    if (st == VC_OK) {
+    VC_TRY(upload(x, npix_in, d->cin, cin_eff, &dx));
+    if (res) VC_TRY(upload(res, npix_out, d->cout, cout_s, &dr));
+    VC_TRY(mem.alloc(&dy, npix_out * cout_s * es));
+    int st = VC_OK;
+    {
         ConvP c{};
         c.in = dx; c.w = p.d_w; c.bias = p.d_b; c.res = dr; c.out = dy;
         c.B = d->b; c.H = d->h; c.W = d->w; c.Cin = cin_eff; c.in_cs = cin_eff; c.in_co = 0;
@@ -768,46 +786,37 @@ int vc_conv2d_host(const vc_conv_desc* d, const float* x, const float* w, const 
             for (int c = 0; c < d->cout; ++c)
                 y[i * d->cout + c] = es == 4 ? ((const float*)buf.data())[i * cout_s + c] : es == 2 ? bf16_to_f32(((const uint16_t*)buf.data())[i * cout_s + c]) : e4m3_to_f32(buf[i * cout_s + c]);
     }
-    for (void* q : tmp.allocs) hipFree(q);
-    tmp.allocs.clear();
     return st;
 }
 
 int vc_letterbox_host(const uint8_t* rgb, int h, int w, int net_h, int net_w, int precision, float* out) {
     VC_CHECK(rgb && out, VC_ERR_ARG, "null argument");
-    vc_engine tmp;
-    tmp.prec = precision;
+    DevScratch mem;
     const LetterboxGeom g = letterbox_geom(h, w, net_h, net_w, false);
     void *ds = nullptr, *dd = nullptr;
     const int es = elem_size(precision);
-    int st = dev_alloc(&tmp, &ds, (size_t)h * w * 3);
-    if (st == VC_OK) st = dev_alloc(&tmp, &dd, (size_t)net_h * net_w * 4 * es);
-    if (st == VC_OK && hipMemcpy(ds, rgb, (size_t)h * w * 3, hipMemcpyHostToDevice) != hipSuccess) { set_error("upload failed"); st = VC_ERR_HIP; }
-    if (st == VC_OK) st = launch_letterbox((const uint8_t*)ds, dd, 1, g, precision, nullptr);
-    if (st == VC_OK) {
-        std::vector<uint8_t> buf((size_t)net_h * net_w * 4 * es);
-        if (hipMemcpy(buf.data(), dd, buf.size(), hipMemcpyDeviceToHost) != hipSuccess) { set_error("letterbox failed: %s", hipGetErrorString(hipGetLastError())); st = VC_ERR_HIP; }
-        for (size_t i = 0; i < (size_t)net_h * net_w && st == VC_OK; ++i)
-            for (int c = 0; c < 3; ++c)
-                out[i * 3 + c] = es == 4 ? ((const float*)buf.data())[i * 4 + c] : bf16_to_f32(((const uint16_t*)buf.data())[i * 4 + c]);
-    }
-    for (void* q : tmp.allocs) hipFree(q);
-    tmp.allocs.clear();
-    return st;
+    VC_TRY(mem.alloc(&ds, (size_t)h * w * 3));
+    VC_TRY(mem.alloc(&dd, (size_t)net_h * net_w * 4 * es));
+    VC_HIP(hipMemcpy(ds, rgb, (size_t)h * w * 3, hipMemcpyHostToDevice));
+    VC_TRY(launch_letterbox((const uint8_t*)ds, dd, 1, g, precision, nullptr));
+    std::vector<uint8_t> buf((size_t)net_h * net_w * 4 * es);
+    VC_CHECK(hipMemcpy(buf.data(), dd, buf.size(), hipMemcpyDeviceToHost) == hipSuccess, VC_ERR_HIP, "letterbox failed: %s", hipGetErrorString(hipGetLastError()));
+    for (size_t i = 0; i < (size_t)net_h * net_w; ++i)
+        for (int c = 0; c < 3; ++c)
+            out[i * 3 + c] = es == 4 ? ((const float*)buf.data())[i * 4 + c] : bf16_to_f32(((const uint16_t*)buf.data())[i * 4 + c]);
+    return VC_OK;
 }
 
 // ---- sized batches: the letterbox and crop kernels with their per-frame tables, on host arrays --------------------------------------
-// frames of their own sizes uploaded into cells (include/vcount_hip.h) -> *cells_out (device, in tmp); *cell_out: the cell size
-static int upload_cells(vc_engine* tmp, const uint8_t* const* frames, const vc_frame_dims* dims, int b, uint8_t** cells_out, size_t* cell_out) {
-    VC_CHECK(frames && dims && b >= 1, VC_ERR_ARG, "bad batch of %d frames", b);
-    size_t cell = 0;
-    for (int f = 0; f < b; ++f) {
-        VC_CHECK(frames[f] && dims[f].h >= 1 && dims[f].w >= 1 && dims[f].h <= (1 << 15) && dims[f].w <= (1 << 15), VC_ERR_ARG, "frame %d: null data or bad size %dx%d", f,
-                 dims[f].h, dims[f].w);
-        cell = std::max(cell, (size_t)dims[f].h * dims[f].w * 3);
-    }
-    cell = (cell + 15) / 16 * 16;
-    VC_TRY(dev_alloc(tmp, (void**)cells_out, (size_t)b * cell));
+// frames of their own sizes uploaded into cells (include/vcount_hip.h) -> *cells_out (device, in mem); *cell_out: the cell size.
+// Network shapes are not compared here (img_size 1 gives every frame 32 x 32).
+static int upload_cells(DevScratch& mem, const uint8_t* const* frames, const vc_frame_dims* dims, int b, uint8_t** cells_out, size_t* cell_out) {
+    VC_CHECK(frames, VC_ERR_ARG, "null frame list");
+    SizedDims sd;
+    VC_TRY(sized_dims_resolve(dims, b, 1, sd));
+    for (int f = 0; f < b; ++f) VC_CHECK(frames[f], VC_ERR_ARG, "frame %d: null data", f);
+    const size_t cell = sd.cell;
+    VC_TRY(mem.alloc(cells_out, (size_t)b * cell));
     VC_HIP(hipMemset(*cells_out, 0xA5, (size_t)b * cell));             // what a kernel that strays outside a frame would pick up
     for (int f = 0; f < b; ++f) VC_HIP(hipMemcpy(*cells_out + (size_t)f * cell, frames[f], (size_t)dims[f].h * dims[f].w * 3, hipMemcpyHostToDevice));
     *cell_out = cell;
@@ -818,31 +827,25 @@ int vc_letterbox_frames_host(const uint8_t* const* frames, const vc_frame_dims* 
     VC_CHECK(out, VC_ERR_ARG, "null argument");
     VC_CHECK(net_h >= 1 && net_w >= 4 && net_w % 4 == 0, VC_ERR_ARG, "network tensor %dx%d (the width must be a multiple of 4)", net_h, net_w);
     VC_CHECK(precision == VC_PREC_BF16 || precision == VC_PREC_F32, VC_ERR_ARG, "precision must be VC_PREC_BF16 or VC_PREC_F32");
-    vc_engine tmp;
+    DevScratch mem;
     uint8_t* dc = nullptr;
     void *dd = nullptr, *dt = nullptr;
     size_t cell = 0;
     const int es = elem_size(precision);
+    VC_TRY(upload_cells(mem, frames, dims, b, &dc, &cell));
     const size_t px = (size_t)b * net_h * net_w;
-    int st = upload_cells(&tmp, frames, dims, b, &dc, &cell);
-    if (st == VC_OK) st = dev_alloc(&tmp, &dd, px * 4 * es);
-    if (st == VC_OK) st = dev_alloc(&tmp, &dt, (size_t)b * sizeof(LetterboxFrame));
-    if (st == VC_OK) {
-        std::vector<LetterboxFrame> tab((size_t)b);
-        for (int f = 0; f < b; ++f) tab[f] = letterbox_frame((long long)((size_t)f * cell), letterbox_geom(dims[f].h, dims[f].w, net_h, net_w, swap_rb != 0));
-        if (hipMemcpy(dt, tab.data(), (size_t)b * sizeof(LetterboxFrame), hipMemcpyHostToDevice) != hipSuccess) { set_error("upload failed"); st = VC_ERR_HIP; }
-    }
-    if (st == VC_OK) st = launch_letterbox_frames(dc, (const LetterboxFrame*)dt, dd, b, net_h, net_w, swap_rb ? 1 : 0, precision, nullptr);
-    if (st == VC_OK) {
-        std::vector<uint8_t> buf(px * 4 * es);
-        if (hipMemcpy(buf.data(), dd, buf.size(), hipMemcpyDeviceToHost) != hipSuccess) { set_error("letterbox_frames_kernel failed: %s", hipGetErrorString(hipGetLastError())); st = VC_ERR_HIP; }
-        for (size_t i = 0; i < px && st == VC_OK; ++i)
-            for (int c = 0; c < 3; ++c)
-                out[i * 3 + c] = es == 4 ? ((const float*)buf.data())[i * 4 + c] : bf16_to_f32(((const uint16_t*)buf.data())[i * 4 + c]);
-    }
-    for (void* q : tmp.allocs) hipFree(q);
-    tmp.allocs.clear();
-    return st;
+    VC_TRY(mem.alloc(&dd, px * 4 * es));
+    VC_TRY(mem.alloc(&dt, (size_t)b * sizeof(LetterboxFrame)));
+    std::vector<LetterboxFrame> tab((size_t)b);
+    for (int f = 0; f < b; ++f) tab[f] = letterbox_frame((long long)((size_t)f * cell), letterbox_geom(dims[f].h, dims[f].w, net_h, net_w, swap_rb != 0));
+    VC_HIP(hipMemcpy(dt, tab.data(), (size_t)b * sizeof(LetterboxFrame), hipMemcpyHostToDevice));
+    VC_TRY(launch_letterbox_frames(dc, (const LetterboxFrame*)dt, dd, b, net_h, net_w, swap_rb ? 1 : 0, precision, nullptr));
+    std::vector<uint8_t> buf(px * 4 * es);
+    VC_CHECK(hipMemcpy(buf.data(), dd, buf.size(), hipMemcpyDeviceToHost) == hipSuccess, VC_ERR_HIP, "letterbox_frames_kernel failed: %s", hipGetErrorString(hipGetLastError()));
+    for (size_t i = 0; i < px; ++i)
+        for (int c = 0; c < 3; ++c)
+            out[i * 3 + c] = es == 4 ? ((const float*)buf.data())[i * 4 + c] : bf16_to_f32(((const uint16_t*)buf.data())[i * 4 + c]);
+    return VC_OK;
 }
 
 // The letterbox kernels on the caller's own device buffers (measurement; the counterpart of vc_frames_to_bgr_dev): frames_dev = b packed
@@ -876,31 +879,25 @@ int vc_crop_resize_frames_host(const uint8_t* const* bgr, const vc_frame_dims* d
         crops[(size_t)i * 5] = f;
         memcpy(&crops[(size_t)i * 5 + 1], c, sizeof(c));
     }
-    vc_engine tmp;
+    DevScratch mem;
     uint8_t* dc = nullptr;
     void *dd = nullptr, *dt = nullptr, *dk = nullptr;
     size_t cell = 0;
     const size_t px = (size_t)k * VC_REID_SIZE * VC_REID_SIZE;
-    int st = upload_cells(&tmp, bgr, dims, b, &dc, &cell);
-    if (st == VC_OK) st = dev_alloc(&tmp, &dd, px * 4 * sizeof(float));
-    if (st == VC_OK) st = dev_alloc(&tmp, &dt, (size_t)b * sizeof(CropFrame));
-    if (st == VC_OK) st = dev_alloc(&tmp, &dk, crops.size() * sizeof(int));
-    if (st == VC_OK) {
-        std::vector<CropFrame> tab((size_t)b);
-        for (int f = 0; f < b; ++f) tab[f] = CropFrame{(long long)((size_t)f * cell), dims[f].w, 0};
-        if (hipMemcpy(dt, tab.data(), (size_t)b * sizeof(CropFrame), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(dk, crops.data(), crops.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { set_error("upload failed"); st = VC_ERR_HIP; }
-    }
-    if (st == VC_OK) st = launch_crop_resize(dc, 0, 0, (const int*)dk, k, dd, 4, VC_PREC_F32, nullptr, false, (const CropFrame*)dt);
-    if (st == VC_OK) {
-        std::vector<float> buf(px * 4);
-        if (hipMemcpy(buf.data(), dd, buf.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { set_error("crop_resize_kernel failed: %s", hipGetErrorString(hipGetLastError())); st = VC_ERR_HIP; }
-        for (size_t i = 0; i < px && st == VC_OK; ++i)
-            for (int c = 0; c < 3; ++c) out[i * 3 + c] = buf[i * 4 + c];
-    }
-    for (void* q : tmp.allocs) hipFree(q);
-    tmp.allocs.clear();
-    return st;
+    VC_TRY(upload_cells(mem, bgr, dims, b, &dc, &cell));
+    VC_TRY(mem.alloc(&dd, px * 4 * sizeof(float)));
+    VC_TRY(mem.alloc(&dt, (size_t)b * sizeof(CropFrame)));
+    VC_TRY(mem.alloc(&dk, crops.size() * sizeof(int)));
+    std::vector<CropFrame> tab((size_t)b);
+    for (int f = 0; f < b; ++f) tab[f] = CropFrame{(long long)((size_t)f * cell), dims[f].w, 0};
+    VC_HIP(hipMemcpy(dt, tab.data(), (size_t)b * sizeof(CropFrame), hipMemcpyHostToDevice));
+    VC_HIP(hipMemcpy(dk, crops.data(), crops.size() * sizeof(int), hipMemcpyHostToDevice));
+    VC_TRY(launch_crop_resize(dc, 0, 0, (const int*)dk, k, dd, 4, VC_PREC_F32, nullptr, false, (const CropFrame*)dt));
+    std::vector<float> buf(px * 4);
+    VC_CHECK(hipMemcpy(buf.data(), dd, buf.size() * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess, VC_ERR_HIP, "crop_resize_kernel failed: %s", hipGetErrorString(hipGetLastError()));
+    for (size_t i = 0; i < px; ++i)
+        for (int c = 0; c < 3; ++c) out[i * 3 + c] = buf[i * 4 + c];
+    return VC_OK;
 }
 
 }  // extern "C"

@@ -115,24 +115,25 @@ int vc_stream_inject(vc_engine* e, const float* det6, const int* count, int b, i
 
 // Enqueue the detector (letterbox .. NMS, results to pinned memory) for a batch on the detector stream and return
 // immediately.  At most two submissions may be outstanding; vc_stream_run consumes them in order.
-// dims == nullptr: a uniform batch of h x w frames.  Otherwise a sized batch whose dims have been validated (sized_layout below): frame f
+// dims == nullptr: a uniform batch of h x w frames.  Otherwise a sized batch whose dims have been validated (sized_dims_resolve): frame f
 // at frames_dev + f * cell, every frame's own network shape nh x nw, h x w the largest frame.
 static int submit_batch(vc_engine* e, const void* frames_dev, int b, int h, int w, const vc_frame_dims* dims, size_t cell, int nh, int nw) {
     VC_CHECK(e->finalized && e->cfg.with_detector, VC_ERR_STATE, "engine not finalized");
     VC_CHECK(e->pending.size() < 2, VC_ERR_STATE, "two submissions are already in flight: call vc_stream_run first");
-    for (int i = 0; i < 4; ++i)                          // a staged batch is submitted as what it was staged as
-        if (e->d_ingest[i] && frames_dev == e->d_ingest[i] && e->ingest_staged[i]) {
-            const std::vector<vc_frame_dims>& sd = e->ingest_dims[i];
-            VC_CHECK(dims || sd.empty(), VC_ERR_ARG, "the batch was staged by vc_stream_stage_frames_sized: submit it with vc_stream_submit_sized");
-            VC_CHECK(!dims || ((int)sd.size() == b && memcmp(sd.data(), dims, (size_t)b * sizeof(vc_frame_dims)) == 0), VC_ERR_ARG,
-                     "the frame sizes differ from those the batch was staged with");
-        }
+    int staged = -1;                                     // the ingest slot frames_dev was staged into, if it was
+    for (int i = 0; i < 4; ++i)
+        if (e->d_ingest[i] && frames_dev == e->d_ingest[i] && e->ingest_staged[i]) staged = i;
+    if (staged >= 0) {                                   // a staged batch is submitted as what it was staged as
+        const std::vector<vc_frame_dims>& sd = e->ingest_dims[staged];
+        VC_CHECK(dims || sd.empty(), VC_ERR_ARG, "the batch was staged by vc_stream_stage_frames_sized: submit it with vc_stream_submit_sized");
+        VC_CHECK(!dims || ((int)sd.size() == b && memcmp(sd.data(), dims, (size_t)b * sizeof(vc_frame_dims)) == 0), VC_ERR_ARG,
+                 "the frame sizes differ from those the batch was staged with");
+    }
     VC_HIP(hipSetDevice(e->cfg.device));
-    for (int i = 0; i < 4; ++i)                          // a batch staged by vc_stream_stage_host: the detector starts behind its copy
-        if (e->d_ingest[i] && frames_dev == e->d_ingest[i] && e->ingest_staged[i]) {
-            VC_HIP(hipStreamWaitEvent(e->dstream, e->ev_ingest[i], 0));
-            e->ingest_staged[i] = false;
-        }
+    if (staged >= 0) {                                   // the detector starts behind the slot's copy
+        VC_HIP(hipStreamWaitEvent(e->dstream, e->ev_ingest[staged], 0));
+        e->ingest_staged[staged] = false;
+    }
     const int slot = (int)(e->submit_seq++ & 1);
     const int md = e->cfg.max_det;
     if (dims) VC_TRY(run_detector_dev_sized(e, (const uint8_t*)frames_dev, b, dims, cell, nh, nw, /*swap_rb=*/true));
@@ -153,31 +154,13 @@ int vc_stream_submit(vc_engine* e, const void* frames_dev, int b, int h, int w) 
     return submit_batch(e, frames_dev, b, h, w, nullptr, 0, 0, 0);
 }
 
-// The rules of a sized batch for a caller that hands in device frames (pure host logic): equal network shapes, the cell, the capacities.
-static int sized_layout(vc_engine* e, const vc_frame_dims* dims, int b, size_t& cell, int& nh, int& nw, int& max_h, int& max_w) {
-    VC_CHECK(b >= 1 && dims, VC_ERR_ARG, "bad sized batch of %d frames", b);
-    cell = 0; max_h = max_w = 0;
-    for (int f = 0; f < b; ++f) {
-        const int h = dims[f].h, w = dims[f].w;
-        VC_CHECK(h >= 1 && w >= 1 && h <= (1 << 15) && w <= (1 << 15), VC_ERR_ARG, "frame %d: bad frame size %dx%d", f, h, w);
-        int fh, fw;
-        autoshape_net_size(&h, &w, 1, e->cfg.img_size, fh, fw);
-        if (f == 0) { nh = fh; nw = fw; }
-        VC_CHECK(fh == nh && fw == nw, VC_ERR_ARG, "frame %d: %dx%d runs at %dx%d, frame 0 at %dx%d", f, h, w, fh, fw, nh, nw);
-        cell = std::max(cell, (size_t)h * w * 3);
-        max_h = std::max(max_h, h); max_w = std::max(max_w, w);
-    }
-    cell = (cell + 15) / 16 * 16;
-    VC_CHECK(b <= e->cfg.max_batch && max_h <= e->cfg.max_frame_h && max_w <= e->cfg.max_frame_w, VC_ERR_CAPACITY,
-             "batch of %d frames up to %dx%d exceeds max_batch / max_frame_h / max_frame_w", b, max_h, max_w);
-    return VC_OK;
-}
-
 int vc_stream_submit_sized(vc_engine* e, const void* frames_dev, const vc_frame_dims* dims, int b) {
     VC_CHECK(e && frames_dev && dims, VC_ERR_ARG, "null argument");
-    size_t cell; int nh = 0, nw = 0, mh, mw;
-    VC_TRY(sized_layout(e, dims, b, cell, nh, nw, mh, mw));
-    return submit_batch(e, frames_dev, b, mh, mw, dims, cell, nh, nw);
+    SizedDims sd;
+    VC_TRY(sized_dims_resolve(dims, b, e->cfg.img_size, sd));
+    VC_CHECK(b <= e->cfg.max_batch && sd.max_h <= e->cfg.max_frame_h && sd.max_w <= e->cfg.max_frame_w, VC_ERR_CAPACITY,
+             "batch of %d frames up to %dx%d exceeds max_batch / max_frame_h / max_frame_w", b, sd.max_h, sd.max_w);
+    return submit_batch(e, frames_dev, b, sd.max_h, sd.max_w, dims, sd.cell, sd.net_h, sd.net_w);
 }
 
 // Ingest from host memory (the reference decodes on the host and hands numpy frames over, modules/datasets.py:47-61):
@@ -217,7 +200,7 @@ int all_crops(vc_engine* e, vc_engine::Pending& pd, std::vector<int>& crops) {
     for (int f = 0; f < b; ++f) {
         pd.row0[f] = k;
         FrameDets& d = pd.fd[f];
-        const int h = pd.dims.empty() ? pd.h : pd.dims[f].h, w = pd.dims.empty() ? pd.w : pd.dims[f].w;    // the frame's own size
+        const int h = pd.frame_dims(f).h, w = pd.frame_dims(f).w;
         VC_CHECK(k + (int)d.conf.size() <= e->cfg.max_crops, VC_ERR_CAPACITY,
                  "the batch has more boxes than max_crops (%d): raise vc_engine_config.max_crops", e->cfg.max_crops);
         for (size_t i = 0; i < d.conf.size(); ++i) {
@@ -546,9 +529,9 @@ int vc_stream_run_async_multi_sized(vc_engine* e, const int* trackers, int n_cam
         VC_CHECK(dims[f].h == dims[first[cam]].h && dims[f].w == dims[first[cam]].w, VC_ERR_ARG, "frame %d: camera %d delivers %dx%d here and %dx%d in frame %d", f, cam,
                  dims[f].h, dims[f].w, dims[first[cam]].h, dims[first[cam]].w, first[cam]);
     }
-    int mh = 0, mw = 0;
-    for (int f = 0; f < b; ++f) { mh = std::max(mh, dims[f].h); mw = std::max(mw, dims[f].w); }
-    return run_async_batch(e, trackers, n_cam, num_classes, cam_of_frame, frames_dev, b, mh, mw, cap_rows_per_frame, dims);
+    SizedDims sd;                                            // for the largest frame: what the submission was filed under
+    VC_TRY(sized_dims_resolve(dims, b, e->cfg.img_size, sd));
+    return run_async_batch(e, trackers, n_cam, num_classes, cam_of_frame, frames_dev, b, sd.max_h, sd.max_w, cap_rows_per_frame, dims);
 }
 
 // Results of the oldest asynchronous batch (blocks until its tracker kernel has finished).  While waiting, the ReID of the
@@ -742,38 +725,31 @@ int vc_nms_host(const float* boxes4, const float* conf, const int* cls, int n, f
                 int* out_n) {
     VC_CHECK(boxes4 && conf && cls && out6 && out_n && n >= 0, VC_ERR_ARG, "bad argument");
     VC_CHECK(max_cand % 64 == 0 && max_cand >= 64 && max_cand <= 8192 && n <= max_cand, VC_ERR_ARG, "max_cand must be a multiple of 64 in [64,8192] and >= n");
-    vc_engine tmp;
+    DevScratch mem;
     DetectPostBuffers pb{};
     float* geom = nullptr;
-    int st = VC_OK;
     const size_t mc = max_cand;
-    auto A = [&](void** p, size_t bytes) { if (st == VC_OK) st = dev_alloc(&tmp, p, bytes); };
-    A((void**)&pb.cand_box, mc * 16); A((void**)&pb.cand_conf, mc * 4); A((void**)&pb.cand_cls, mc * 4); A((void**)&pb.cand_idx, mc * 4);
-    A((void**)&pb.cand_count, 4); A((void**)&pb.sort_box, mc * 16); A((void**)&pb.sort_conf, mc * 4); A((void**)&pb.sort_cls, mc * 4);
-    A((void**)&pb.mask, mc * (mc / 64) * 8); A((void**)&pb.det, (size_t)max_det * 24); A((void**)&pb.det_count, 4); A((void**)&pb.overflow, 4);
-    A((void**)&geom, 20);
-    if (st == VC_OK && hipMemset(pb.overflow, 0, 4) != hipSuccess) { set_error("memset failed"); st = VC_ERR_HIP; }
-    if (st == VC_OK) {
-        std::vector<int> idx(n);
-        std::iota(idx.begin(), idx.end(), 0);
-        const float g[5] = {1.f, 0.f, 0.f, 1e30f, 1e30f};
-        bool ok = hipMemcpy(pb.cand_box, boxes4, (size_t)n * 16, hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMemcpy(pb.cand_conf, conf, (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMemcpy(pb.cand_cls, cls, (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMemcpy(pb.cand_idx, idx.data(), (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMemcpy(pb.cand_count, &n, 4, hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMemcpy(geom, g, 20, hipMemcpyHostToDevice) == hipSuccess;
-        if (!ok) { set_error("upload failed"); st = VC_ERR_HIP; }
-    }
-    if (st == VC_OK) st = launch_nms(1, max_cand, max_det, iou, geom, pb, nullptr);
-    if (st == VC_OK && hipDeviceSynchronize() != hipSuccess) { set_error("nms kernels failed: %s", hipGetErrorString(hipGetLastError())); st = VC_ERR_HIP; }
-    if (st == VC_OK) {
-        if (hipMemcpy(out_n, pb.det_count, 4, hipMemcpyDeviceToHost) != hipSuccess || *out_n < 0 ||
-            hipMemcpy(out6, pb.det, (size_t)std::min(*out_n, max_det) * 24, hipMemcpyDeviceToHost) != hipSuccess) { set_error("download failed"); st = VC_ERR_HIP; }
-    }
-    for (void* q : tmp.allocs) (void)hipFree(q);
-    tmp.allocs.clear();
-    return st;
+    const std::pair<void**, size_t> bufs[] = {
+        {(void**)&pb.cand_box, mc * 16}, {(void**)&pb.cand_conf, mc * 4}, {(void**)&pb.cand_cls, mc * 4}, {(void**)&pb.cand_idx, mc * 4}, {(void**)&pb.cand_count, 4},
+        {(void**)&pb.sort_box, mc * 16}, {(void**)&pb.sort_conf, mc * 4}, {(void**)&pb.sort_cls, mc * 4}, {(void**)&pb.mask, mc * (mc / 64) * 8},
+        {(void**)&pb.det, (size_t)max_det * 24}, {(void**)&pb.det_count, 4}, {(void**)&pb.overflow, 4}, {(void**)&geom, 20}};
+    for (const auto& bf : bufs) VC_TRY(mem.alloc(bf.first, bf.second));
+    VC_HIP(hipMemset(pb.overflow, 0, 4));
+    std::vector<int> idx(n);
+    std::iota(idx.begin(), idx.end(), 0);
+    const float g[5] = {1.f, 0.f, 0.f, 1e30f, 1e30f};
+    VC_HIP(hipMemcpy(pb.cand_box, boxes4, (size_t)n * 16, hipMemcpyHostToDevice));
+    VC_HIP(hipMemcpy(pb.cand_conf, conf, (size_t)n * 4, hipMemcpyHostToDevice));
+    VC_HIP(hipMemcpy(pb.cand_cls, cls, (size_t)n * 4, hipMemcpyHostToDevice));
+    VC_HIP(hipMemcpy(pb.cand_idx, idx.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    VC_HIP(hipMemcpy(pb.cand_count, &n, 4, hipMemcpyHostToDevice));
+    VC_HIP(hipMemcpy(geom, g, 20, hipMemcpyHostToDevice));
+    VC_TRY(launch_nms(1, max_cand, max_det, iou, geom, pb, nullptr));
+    VC_CHECK(hipDeviceSynchronize() == hipSuccess, VC_ERR_HIP, "nms kernels failed: %s", hipGetErrorString(hipGetLastError()));
+    VC_CHECK(hipMemcpy(out_n, pb.det_count, 4, hipMemcpyDeviceToHost) == hipSuccess && *out_n >= 0 &&
+                 hipMemcpy(out6, pb.det, (size_t)std::min(*out_n, max_det) * 24, hipMemcpyDeviceToHost) == hipSuccess,
+             VC_ERR_HIP, "download failed");
+    return VC_OK;
 }
 
 }  // extern "C"

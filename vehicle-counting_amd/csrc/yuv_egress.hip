@@ -177,30 +177,15 @@ int vc_bgr_to_yuv_host(const vc_yuv_desc* d, const uint8_t* bgr, int b, int h, i
     VC_CHECK(bgr && yuv_out, VC_ERR_ARG, "null argument");
     YuvGeom g;
     VC_TRY(yuv_resolve(d, b, h, w, g));
-    const size_t in_bytes = (size_t)b * h * w * 3, out_bytes = yuv_batch_bytes(g, b), guard = 256;
-    vc_engine tmp;
-    uint8_t *ds = nullptr, *dd = nullptr;
-    int st = dev_alloc(&tmp, (void**)&ds, in_bytes);
-    if (st == VC_OK) st = dev_alloc(&tmp, (void**)&dd, out_bytes + 2 * guard);
-    if (st == VC_OK && (hipMemcpy(ds, bgr, in_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemset(dd, 0xA5, out_bytes + 2 * guard) != hipSuccess ||
-                        hipMemcpy(dd + guard, yuv_out, out_bytes, hipMemcpyHostToDevice) != hipSuccess)) {
-        set_error("upload failed");
-        st = VC_ERR_HIP;
-    }
-    if (st == VC_OK) st = launch_bgr_to_yuv(g, ds, dd + guard, b, nullptr);
-    if (st == VC_OK) {
-        uint8_t edge[512];
-        if (hipMemcpy(yuv_out, dd + guard, out_bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(edge, dd, guard, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(edge + guard, dd + guard + out_bytes, guard, hipMemcpyDeviceToHost) != hipSuccess) {
-            set_error("bgr_to_yuv_kernel failed: %s", hipGetErrorString(hipGetLastError()));
-            st = VC_ERR_HIP;
-        }
-        for (size_t i = 0; i < 2 * guard && st == VC_OK; ++i)
-            if (edge[i] != 0xA5) { set_error("bgr_to_yuv_kernel wrote outside its output (guard byte %zu)", i); st = VC_ERR_HIP; }
-    }
-    for (void* q : tmp.allocs) (void)hipFree(q);
-    tmp.allocs.clear();
-    return st;
+    const size_t in_bytes = (size_t)b * h * w * 3;
+    DevScratch mem;
+    uint8_t* ds = nullptr;
+    GuardedOut dd;
+    VC_TRY(mem.alloc(&ds, in_bytes));
+    VC_TRY(dd.alloc(mem, yuv_batch_bytes(g, b), yuv_out));
+    VC_HIP(hipMemcpy(ds, bgr, in_bytes, hipMemcpyHostToDevice));
+    VC_TRY(launch_bgr_to_yuv(g, ds, dd.out(), b, nullptr));
+    return dd.read_back(yuv_out, "bgr_to_yuv_kernel");
 }
 
 int vc_bgr_to_yuv_dev(const vc_yuv_desc* d, const void* bgr_dev, int b, int h, int w, void* yuv_dev) {

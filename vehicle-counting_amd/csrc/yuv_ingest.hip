@@ -71,95 +71,7 @@ __device__ __forceinline__ uint32_t yuv_bytes4(const uint8_t* p, int n) {      /
     return v;
 }
 
-// grid: one lane per (frame, row pair, 16-pixel column group), flattened in that order so that a wavefront walks along a row pair
-template <bool NV12, bool FAST>
-__global__ __launch_bounds__(256) void yuv_to_bgr_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, YuvGeom k, int ncg, long long total) {
-    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= total) return;
-    const int hp = k.h >> 1;
-    const long long rowpair = gid / ncg;
-    const int cg = (int)(gid - rowpair * ncg);
-    const int f = (int)(rowpair / hp), rp = (int)(rowpair - (long long)f * hp);
-    const int x0 = cg * 16;
-    const int npx = min(16, k.w - x0);                      // even; 16 on the fast path
-    const uint8_t* sf = src + (size_t)f * k.frame_stride;
-    const uint8_t* y0p = sf + (size_t)(2 * rp) * k.pitch_y + x0;
-    const uint8_t* y1p = y0p + k.pitch_y;
-
-    uint32_t yw[2][4], cw[4];
-    if (FAST) {
-        const uint4 a = *(const uint4*)y0p, b = *(const uint4*)y1p;
-        yw[0][0] = a.x; yw[0][1] = a.y; yw[0][2] = a.z; yw[0][3] = a.w;
-        yw[1][0] = b.x; yw[1][1] = b.y; yw[1][2] = b.z; yw[1][3] = b.w;
-        if (NV12) {
-            const uint4 c = *(const uint4*)(sf + k.off_c + (size_t)rp * k.pitch_c + x0);
-            cw[0] = c.x; cw[1] = c.y; cw[2] = c.z; cw[3] = c.w;
-        } else {
-            const uint2 u = *(const uint2*)(sf + k.off_c + (size_t)rp * k.pitch_c + (x0 >> 1));
-            const uint2 v = *(const uint2*)(sf + k.off_v + (size_t)rp * k.pitch_c + (x0 >> 1));
-            const uint32_t uu[2] = {u.x, u.y}, vv[2] = {v.x, v.y};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t us = uu[j >> 1] >> (16 * (j & 1)), vs = vv[j >> 1] >> (16 * (j & 1));
-                cw[j] = (us & 255) | ((vs & 255) << 8) | ((us & 0xff00) << 8) | ((vs & 0xff00) << 16);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = npx - 4 * j;                      // pixels of this group of four that exist
-            yw[0][j] = yuv_bytes4(y0p + 4 * j, n);
-            yw[1][j] = yuv_bytes4(y1p + 4 * j, n);
-            if (NV12) {
-                cw[j] = yuv_bytes4(sf + k.off_c + (size_t)rp * k.pitch_c + x0 + 4 * j, n);
-            } else {
-                const uint32_t us = yuv_bytes4(sf + k.off_c + (size_t)rp * k.pitch_c + (x0 >> 1) + 2 * j, n >> 1);
-                const uint32_t vs = yuv_bytes4(sf + k.off_v + (size_t)rp * k.pitch_c + (x0 >> 1) + 2 * j, n >> 1);
-                cw[j] = (us & 255) | ((vs & 255) << 8) | ((us & 0xff00) << 8) | ((vs & 0xff00) << 16);
-            }
-        }
-    }
-
-    YuvChroma ch[8];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        ch[2 * j] = yuv_chroma(cw[j] & 255, (cw[j] >> 8) & 255, k);
-        ch[2 * j + 1] = yuv_chroma((cw[j] >> 16) & 255, cw[j] >> 24, k);
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        uint32_t o[12];
-        yuv_row16(yw[r], ch, k, o);
-        uint8_t* d = dst + (((size_t)f * k.h + 2 * rp + r) * k.w + x0) * 3;
-        if (FAST) {
-            uint4* d4 = (uint4*)d;
-            d4[0] = make_uint4(o[0], o[1], o[2], o[3]);
-            d4[1] = make_uint4(o[4], o[5], o[6], o[7]);
-            d4[2] = make_uint4(o[8], o[9], o[10], o[11]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 48; ++i)
-                if (i < npx * 3) d[i] = (uint8_t)(o[i >> 2] >> (8 * (i & 3)));
-        }
-    }
-}
-
-// ---- frame table: one batch whose frames each come from their own place (S decoders' surface pools: own addresses, own pitch, format,
-// colour matrix, memory space).  One launch per batch, driven by a table in device memory with one entry per frame (256 frames do not
-// fit kernel arguments).  blockIdx.y is the frame, so the entry is workgroup-uniform and neither the format branch nor the 16-byte
-// branch diverges.  Per frame the arithmetic is yuv_to_bgr_kernel's (the same device functions, the same 16 x 2 block per lane); a BGR
-// entry is a byte copy; an entry of kind FRAME_NONE is a frame that is already in place (a host BGR frame copied straight into the slot).
-enum { FRAME_NONE = 0, FRAME_NV12 = 1, FRAME_I420 = 2, FRAME_BGR = 3 };
-struct FrameEntry {
-    const uint8_t* src;                                 // device address of the frame
-    int kind, fast;                                     // FRAME_*; fast: every address the 16-byte variant forms for THIS frame is aligned
-    int pitch_y, pitch_c;
-    unsigned long long off_c, off_v;
-    int yoff, cy, cvr, cvg, cug, cub;
-};
-static_assert(sizeof(FrameEntry) == VC_FRAME_ENTRY_BYTES, "FrameEntry is copied to the device as plain bytes");
-
-// the 16 x 2 block (row pair rp, column group cg) of one frame: the body of yuv_to_bgr_kernel with the frame's own base addresses
+// the 16 x 2 block (row pair rp, column group cg) of the frame that starts at sf, converted into the h x w x 3 frame at df
 template <bool NV12, bool FAST>
 __device__ __forceinline__ void frame_block(const uint8_t* __restrict__ sf, uint8_t* __restrict__ df, const YuvGeom& k, int rp, int cg) {
     const int x0 = cg * 16;
@@ -224,6 +136,33 @@ __device__ __forceinline__ void frame_block(const uint8_t* __restrict__ sf, uint
         }
     }
 }
+
+// grid: one lane per (frame, row pair, 16-pixel column group), flattened in that order so that a wavefront walks along a row pair
+template <bool NV12, bool FAST>
+__global__ __launch_bounds__(256) void yuv_to_bgr_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, YuvGeom k, int ncg, long long total) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= total) return;
+    const int hp = k.h >> 1;
+    const long long rowpair = gid / ncg;
+    const int cg = (int)(gid - rowpair * ncg);
+    const int f = (int)(rowpair / hp), rp = (int)(rowpair - (long long)f * hp);
+    frame_block<NV12, FAST>(src + (size_t)f * k.frame_stride, dst + (size_t)f * k.h * k.w * 3, k, rp, cg);
+}
+
+// ---- frame table: one batch whose frames each come from their own place (S decoders' surface pools: own addresses, own pitch, format,
+// colour matrix, memory space).  One launch per batch, driven by a table in device memory with one entry per frame (256 frames do not
+// fit kernel arguments).  blockIdx.y is the frame, so the entry is workgroup-uniform and neither the format branch nor the 16-byte
+// branch diverges.  Per frame the conversion is yuv_to_bgr_kernel's (frame_block, the same 16 x 2 block per lane); a BGR
+// entry is a byte copy; an entry of kind FRAME_NONE is a frame that is already in place (a host BGR frame copied straight into the slot).
+enum { FRAME_NONE = 0, FRAME_NV12 = 1, FRAME_I420 = 2, FRAME_BGR = 3 };
+struct FrameEntry {
+    const uint8_t* src;                                 // device address of the frame
+    int kind, fast;                                     // FRAME_*; fast: every address the 16-byte variant forms for THIS frame is aligned
+    int pitch_y, pitch_c;
+    unsigned long long off_c, off_v;
+    int yoff, cy, cvr, cvg, cug, cub;
+};
+static_assert(sizeof(FrameEntry) == VC_FRAME_ENTRY_BYTES, "FrameEntry is copied to the device as plain bytes");
 
 // one frame of a table-driven batch: this lane's share of entry e (workgroup-uniform), converted or copied into the frame at df
 __device__ __forceinline__ void frame_convert(const FrameEntry& e, uint8_t* __restrict__ df, int h, int w, int ncg) {
@@ -315,6 +254,25 @@ int yuv_resolve(const vc_yuv_desc* d, int b, int h, int w, YuvGeom& g) {
     return VC_OK;
 }
 
+int sized_dims_resolve(const vc_frame_dims* dims, int b, int img_size, SizedDims& out) {
+    VC_CHECK(b >= 1, VC_ERR_ARG, "bad batch of %d frames", b);
+    VC_CHECK(dims, VC_ERR_ARG, "null frame list");
+    VC_CHECK(img_size >= 1, VC_ERR_ARG, "bad img_size %d", img_size);
+    out = SizedDims{};
+    for (int f = 0; f < b; ++f) {
+        const int h = dims[f].h, w = dims[f].w;
+        VC_CHECK(h >= 1 && w >= 1 && h <= (1 << 15) && w <= (1 << 15), VC_ERR_ARG, "frame %d: bad frame size %dx%d", f, h, w);
+        int nh, nw;
+        autoshape_net_size(&h, &w, 1, img_size, nh, nw);
+        if (f == 0) { out.net_h = nh; out.net_w = nw; }
+        VC_CHECK(nh == out.net_h && nw == out.net_w, VC_ERR_ARG, "frame %d: %dx%d runs at %dx%d, frame 0 at %dx%d", f, h, w, nh, nw, out.net_h, out.net_w);
+        out.cell = std::max(out.cell, (size_t)h * w * 3);
+        out.max_h = std::max(out.max_h, h); out.max_w = std::max(out.max_w, w);
+    }
+    out.cell = (out.cell + 15) / 16 * 16;
+    return VC_OK;
+}
+
 size_t yuv_batch_bytes(const YuvGeom& g, int b) { return (size_t)(b - 1) * g.frame_stride + g.frame_end; }
 
 // src: b frames laid out as g says, dst: [b][h][w][3], both device memory.  The 16-byte variant needs every address it forms aligned.
@@ -339,36 +297,53 @@ int launch_yuv_to_bgr(const YuvGeom& g, const uint8_t* src, uint8_t* dst, int b,
 
 namespace {
 
-// The whole validation of a frame list (pure host code, before any HIP call): every refusal names its frame.  geo[f] is resolved for
-// the YUV kinds; raw_off[f] / *raw_bytes: the packing of the YUV_HOST frames into one raw buffer (vc_frames_layout_host).
+// One frame of a frame list (pure host code): its refusals name it.  g is resolved for the YUV kinds, for the frame's own h x w; a
+// YUV_HOST frame takes the next 16-byte-aligned place in the raw buffer (*cur: the bytes packed so far; raw_off[f], -1 for the rest).
+int frame_resolve(const vc_frame_src& s, int f, int h, int w, bool host_only, YuvGeom& g, int64_t* raw_off, size_t* cur) {
+    VC_CHECK(s.kind == VC_SRC_BGR_HOST || s.kind == VC_SRC_BGR_DEV || s.kind == VC_SRC_YUV_HOST || s.kind == VC_SRC_YUV_DEV, VC_ERR_ARG,
+             "frame %d: unknown source kind %d (VC_SRC_*)", f, s.kind);
+    VC_CHECK(!host_only || s.kind == VC_SRC_BGR_HOST || s.kind == VC_SRC_YUV_HOST, VC_ERR_ARG, "frame %d: a device source (kind %d) where host frames are expected", f, s.kind);
+    VC_CHECK(s.data, VC_ERR_ARG, "frame %d: null data", f);
+    if (raw_off) raw_off[f] = -1;
+    if (s.kind != VC_SRC_YUV_HOST && s.kind != VC_SRC_YUV_DEV) return VC_OK;
+    vc_yuv_desc d = s.desc;
+    d.frame_stride = 0;                                     // one frame: the stride has no meaning here
+    if (yuv_resolve(&d, 1, h, w, g) != VC_OK) {
+        char msg[400];
+        snprintf(msg, sizeof(msg), "%s", last_error());
+        set_error("frame %d: %s", f, msg);
+        return VC_ERR_ARG;
+    }
+    if (s.kind == VC_SRC_YUV_HOST) {
+        *cur = (*cur + 15) / 16 * 16;
+        if (raw_off) raw_off[f] = (int64_t)*cur;
+        *cur += yuv_batch_bytes(g, 1);
+    }
+    return VC_OK;
+}
+
+// The whole validation of a frame list of h x w frames (before any HIP call).  raw_off[f] / *raw_bytes: the packing of the YUV_HOST
+// frames into one raw buffer (vc_frames_layout_host).
 int frames_resolve(const vc_frame_src* frames, int b, int h, int w, bool host_only, std::vector<YuvGeom>& geo, int64_t* raw_off, size_t* raw_bytes) {
     VC_CHECK(b >= 1, VC_ERR_ARG, "bad batch of %d frames", b);
     VC_CHECK(frames, VC_ERR_ARG, "null frame list");
     VC_CHECK(h >= 1 && w >= 1, VC_ERR_ARG, "bad frame size %dx%d", h, w);
     geo.assign((size_t)b, YuvGeom{});
     size_t cur = 0;
-    for (int f = 0; f < b; ++f) {
-        const vc_frame_src& s = frames[f];
-        VC_CHECK(s.kind == VC_SRC_BGR_HOST || s.kind == VC_SRC_BGR_DEV || s.kind == VC_SRC_YUV_HOST || s.kind == VC_SRC_YUV_DEV, VC_ERR_ARG,
-                 "frame %d: unknown source kind %d (VC_SRC_*)", f, s.kind);
-        VC_CHECK(!host_only || s.kind == VC_SRC_BGR_HOST || s.kind == VC_SRC_YUV_HOST, VC_ERR_ARG, "frame %d: a device source (kind %d) where host frames are expected", f, s.kind);
-        VC_CHECK(s.data, VC_ERR_ARG, "frame %d: null data", f);
-        if (raw_off) raw_off[f] = -1;
-        if (s.kind != VC_SRC_YUV_HOST && s.kind != VC_SRC_YUV_DEV) continue;
-        vc_yuv_desc d = s.desc;
-        d.frame_stride = 0;                                 // one frame: the stride has no meaning here
-        if (yuv_resolve(&d, 1, h, w, geo[f]) != VC_OK) {
-            char msg[400];
-            snprintf(msg, sizeof(msg), "%s", last_error());
-            set_error("frame %d: %s", f, msg);
-            return VC_ERR_ARG;
-        }
-        if (s.kind == VC_SRC_YUV_HOST) {
-            cur = (cur + 15) / 16 * 16;
-            if (raw_off) raw_off[f] = (int64_t)cur;
-            cur += yuv_batch_bytes(geo[f], 1);
-        }
-    }
+    for (int f = 0; f < b; ++f) VC_TRY(frame_resolve(frames[f], f, h, w, host_only, geo[f], raw_off, &cur));
+    if (raw_bytes) *raw_bytes = cur;
+    return VC_OK;
+}
+
+// The same for a sized frame list: the rules of its dims first, then every frame with its own size.
+int frames_resolve_sized(const vc_frame_src* frames, const vc_frame_dims* dims, int b, int img_size, bool host_only, std::vector<YuvGeom>& geo, int64_t* raw_off,
+                         size_t* raw_bytes, SizedDims& sd) {
+    VC_CHECK(b >= 1, VC_ERR_ARG, "bad batch of %d frames", b);
+    VC_CHECK(frames, VC_ERR_ARG, "null frame list");
+    VC_TRY(sized_dims_resolve(dims, b, img_size, sd));
+    geo.assign((size_t)b, YuvGeom{});
+    size_t cur = 0;
+    for (int f = 0; f < b; ++f) VC_TRY(frame_resolve(frames[f], f, dims[f].h, dims[f].w, host_only, geo[f], raw_off, &cur));
     if (raw_bytes) *raw_bytes = cur;
     return VC_OK;
 }
@@ -402,55 +377,6 @@ int launch_frames_to_bgr(const FrameEntry* d_tab, uint8_t* dst, int b, int h, in
     return VC_OK;
 }
 
-
-// The validation of a sized frame list (pure host code, before any HIP call): frames_resolve with every frame's own size, plus the rule
-// that makes the batch one detector pass -- every frame's own network shape is that of frame 0.
-struct SizedLayout { size_t cell = 0; int net_h = 0, net_w = 0, max_h = 0, max_w = 0; };
-int frames_resolve_sized(const vc_frame_src* frames, const vc_frame_dims* dims, int b, int img_size, bool host_only, std::vector<YuvGeom>& geo, int64_t* raw_off,
-                         size_t* raw_bytes, SizedLayout& lay) {
-    VC_CHECK(b >= 1, VC_ERR_ARG, "bad batch of %d frames", b);
-    VC_CHECK(frames && dims, VC_ERR_ARG, "null frame list");
-    VC_CHECK(img_size >= 1, VC_ERR_ARG, "bad img_size %d", img_size);
-    geo.assign((size_t)b, YuvGeom{});
-    lay = SizedLayout{};
-    size_t cur = 0;
-    int nh0 = 0, nw0 = 0;
-    for (int f = 0; f < b; ++f) {
-        const vc_frame_src& s = frames[f];
-        const int h = dims[f].h, w = dims[f].w;
-        VC_CHECK(h >= 1 && w >= 1 && h <= (1 << 15) && w <= (1 << 15), VC_ERR_ARG, "frame %d: bad frame size %dx%d", f, h, w);
-        VC_CHECK(s.kind == VC_SRC_BGR_HOST || s.kind == VC_SRC_BGR_DEV || s.kind == VC_SRC_YUV_HOST || s.kind == VC_SRC_YUV_DEV, VC_ERR_ARG,
-                 "frame %d: unknown source kind %d (VC_SRC_*)", f, s.kind);
-        VC_CHECK(!host_only || s.kind == VC_SRC_BGR_HOST || s.kind == VC_SRC_YUV_HOST, VC_ERR_ARG, "frame %d: a device source (kind %d) where host frames are expected", f, s.kind);
-        VC_CHECK(s.data, VC_ERR_ARG, "frame %d: null data", f);
-        int nh, nw;
-        autoshape_net_size(&h, &w, 1, img_size, nh, nw);
-        if (f == 0) { nh0 = nh; nw0 = nw; }
-        VC_CHECK(nh == nh0 && nw == nw0, VC_ERR_ARG, "frame %d: %dx%d runs at %dx%d, frame 0 at %dx%d", f, h, w, nh, nw, nh0, nw0);
-        if (raw_off) raw_off[f] = -1;
-        lay.cell = std::max(lay.cell, (size_t)h * w * 3);
-        lay.max_h = std::max(lay.max_h, h); lay.max_w = std::max(lay.max_w, w);
-        if (s.kind != VC_SRC_YUV_HOST && s.kind != VC_SRC_YUV_DEV) continue;
-        vc_yuv_desc d = s.desc;
-        d.frame_stride = 0;                                 // one frame: the stride has no meaning here
-        if (yuv_resolve(&d, 1, h, w, geo[f]) != VC_OK) {
-            char msg[400];
-            snprintf(msg, sizeof(msg), "%s", last_error());
-            set_error("frame %d: %s", f, msg);
-            return VC_ERR_ARG;
-        }
-        if (s.kind == VC_SRC_YUV_HOST) {
-            cur = (cur + 15) / 16 * 16;
-            if (raw_off) raw_off[f] = (int64_t)cur;
-            cur += yuv_batch_bytes(geo[f], 1);
-        }
-    }
-    lay.cell = (lay.cell + 15) / 16 * 16;
-    lay.net_h = nh0; lay.net_w = nw0;
-    if (raw_bytes) *raw_bytes = cur;
-    return VC_OK;
-}
-
 // d_tab: b entries, d_cells: b cells, both in device memory; dst: b cells of device memory
 int launch_frames_to_bgr_sized(const FrameEntry* d_tab, const FrameCell* d_cells, uint8_t* dst, int b, const vc_frame_dims* dims, hipStream_t s) {
     long long lanes = 1;                                                       // of the largest frame
@@ -460,6 +386,102 @@ int launch_frames_to_bgr_sized(const FrameEntry* d_tab, const FrameCell* d_cells
     hipLaunchKernelGGL(frames_to_bgr_sized_kernel, dim3((unsigned)blocks, (unsigned)b), dim3(256), 0, s, d_tab, d_cells, dst);
     VC_HIP(hipGetLastError());
     return VC_OK;
+}
+
+// A frame list's table: b entries, followed for a sized batch (dims != nullptr) by its b cells -- one block, so one copy carries both.
+size_t frame_table_bytes(int b, bool sized) { return (size_t)b * (sizeof(FrameEntry) + (sized ? sizeof(FrameCell) : 0)); }
+
+// fills entry f (and, for a sized batch, cell f) of the host table: the frame at DEVICE address src goes to dst + f * stride
+void frame_table_set(void* tab, int b, int f, const vc_frame_src& s, const YuvGeom& g, const uint8_t* src, uint8_t* dst, size_t stride, int h, int w, bool sized) {
+    ((FrameEntry*)tab)[f] = src ? frame_entry(s.kind, g, src, dst + (size_t)f * stride, h, w) : FrameEntry{};      // no src: FRAME_NONE, already in place
+    if (sized) ((FrameCell*)((FrameEntry*)tab + b))[f] = FrameCell{(unsigned long long)f * stride, h, w};
+}
+
+// the launch for a table in device memory; dims == nullptr: a uniform batch of h x w frames, dst [b][h][w][3]
+int launch_frame_table(const void* d_tab, uint8_t* dst, int b, int h, int w, const vc_frame_dims* dims, hipStream_t s) {
+    const FrameEntry* ent = (const FrameEntry*)d_tab;
+    return dims ? launch_frames_to_bgr_sized(ent, (const FrameCell*)(ent + b), dst, b, dims, s) : launch_frames_to_bgr(ent, dst, b, h, w, s);
+}
+
+// Parity of the two table kernels on a validated list of host frames.  Every frame is uploaded to an address congruent to its host
+// pointer mod 16, so that the caller chooses the 16-byte or the generic path by where it puts the frame.  dims == nullptr: b frames of
+// h x w into out [b][h][w][3] (stride = h * w * 3).  Otherwise the caller's cells (stride = the cell) are uploaded, converted into and
+// read back: what the kernel leaves alone inside a cell comes back as the caller filled it.
+int frames_to_bgr_parity(const vc_frame_src* frames, int b, int h, int w, const vc_frame_dims* dims, size_t stride, const std::vector<YuvGeom>& geo, uint8_t* out,
+                         const char* kernel) {
+    std::vector<size_t> off((size_t)b), len((size_t)b);
+    size_t in_bytes = 0;
+    for (int f = 0; f < b; ++f) {
+        const int fh = dims ? dims[f].h : h, fw = dims ? dims[f].w : w;
+        len[f] = frames[f].kind == VC_SRC_YUV_HOST ? yuv_batch_bytes(geo[f], 1) : (size_t)fh * fw * 3;
+        off[f] = (in_bytes + 15) / 16 * 16 + (uintptr_t)frames[f].data % 16;
+        in_bytes = off[f] + len[f];
+    }
+    DevScratch mem;
+    uint8_t *ds = nullptr, *dt = nullptr;
+    GuardedOut dd;
+    VC_TRY(mem.alloc(&ds, in_bytes));
+    VC_TRY(dd.alloc(mem, (size_t)b * stride, dims ? out : nullptr));
+    VC_TRY(mem.alloc(&dt, frame_table_bytes(b, dims != nullptr)));
+    std::vector<uint8_t> tab(frame_table_bytes(b, dims != nullptr));
+    for (int f = 0; f < b; ++f) {
+        VC_HIP(hipMemcpy(ds + off[f], frames[f].data, len[f], hipMemcpyHostToDevice));
+        frame_table_set(tab.data(), b, f, frames[f], geo[f], ds + off[f], dd.out(), stride, dims ? dims[f].h : h, dims ? dims[f].w : w, dims != nullptr);
+    }
+    VC_HIP(hipMemcpy(dt, tab.data(), tab.size(), hipMemcpyHostToDevice));
+    VC_TRY(launch_frame_table(dt, dd.out(), b, h, w, dims, nullptr));
+    return dd.read_back(out, kernel);
+}
+
+// Grows the slot's raw YUV buffer to `bytes` (first YUV batch of the slot, or a pitch wider than any before).  Everything the copy
+// stream still has in flight reads the old buffer, hence the wait.
+int ingest_raw_reserve(vc_engine* e, int slot, size_t bytes) {
+    if (bytes <= e->yuv_raw_bytes[slot]) return VC_OK;
+    VC_HIP(hipStreamSynchronize(e->cstream));
+    const size_t tight = (size_t)e->cfg.max_batch * e->cfg.max_frame_h * e->cfg.max_frame_w * 3 / 2;
+    e->yuv_raw_bytes[slot] = 0;
+    VC_TRY(dev_realloc(e, (void**)&e->d_yuv_raw[slot], std::max(bytes, tight)));
+    e->yuv_raw_bytes[slot] = std::max(bytes, tight);
+    return VC_OK;
+}
+
+// One batch from a validated list of per-frame sources into the next ingest slot.  dims == nullptr: a uniform batch of h x w frames,
+// frame f at f * h * w * 3.  Otherwise a sized batch: frame f in cell f (stride = the cell), h x w the largest frame, and the slot
+// remembers the dims for vc_stream_submit_sized.  On the copy stream: one copy per host frame (BGR straight into its place in the slot,
+// YUV into the slot's raw buffer at its raw_off), one copy of the table only if something launches (per-slot pinned table -> per-slot
+// device table: the slot rules guarantee that the slot's previous batch, and with it the previous copy of the table, is complete), at
+// most one launch, the slot's event.
+int stage_frame_list(vc_engine* e, const vc_frame_src* frames, int b, int h, int w, const vc_frame_dims* dims, size_t stride, const std::vector<YuvGeom>& geo,
+                     const int64_t* raw_off, size_t raw_bytes, void** frames_dev_out) {
+    int slot = 0;
+    VC_TRY(ingest_take_slot(e, b, h, w, &slot));
+    if (!e->h_frame_tab[slot]) {
+        VC_TRY(host_alloc(e, &e->h_frame_tab[slot], frame_table_bytes(e->cfg.max_batch, true)));
+        VC_TRY(dev_alloc(e, &e->d_frame_tab[slot], frame_table_bytes(e->cfg.max_batch, true)));
+    }
+    VC_TRY(ingest_raw_reserve(e, slot, raw_bytes));
+    bool launch = false;
+    for (int f = 0; f < b; ++f) {
+        const vc_frame_src& s = frames[f];
+        const int fh = dims ? dims[f].h : h, fw = dims ? dims[f].w : w;
+        const uint8_t* src = (const uint8_t*)s.data;
+        if (s.kind == VC_SRC_BGR_HOST) {
+            VC_HIP(hipMemcpyAsync(e->d_ingest[slot] + (size_t)f * stride, s.data, (size_t)fh * fw * 3, hipMemcpyHostToDevice, e->cstream));
+            src = nullptr;                                  // already in place
+        } else if (s.kind == VC_SRC_YUV_HOST) {
+            uint8_t* raw = e->d_yuv_raw[slot] + raw_off[f];
+            VC_HIP(hipMemcpyAsync(raw, s.data, yuv_batch_bytes(geo[f], 1), hipMemcpyHostToDevice, e->cstream));
+            src = raw;
+        }
+        frame_table_set(e->h_frame_tab[slot], b, f, s, geo[f], src, e->d_ingest[slot], stride, fh, fw, dims != nullptr);
+        launch = launch || src;
+    }
+    if (launch) {
+        VC_HIP(hipMemcpyAsync(e->d_frame_tab[slot], e->h_frame_tab[slot], frame_table_bytes(b, dims != nullptr), hipMemcpyHostToDevice, e->cstream));
+        VC_TRY(launch_frame_table(e->d_frame_tab[slot], e->d_ingest[slot], b, h, w, dims, e->cstream));
+    }
+    if (dims) e->ingest_dims[slot].assign(dims, dims + b);
+    return ingest_publish(e, slot, frames_dev_out);
 }
 
 }  // namespace
@@ -483,29 +505,15 @@ int vc_yuv_to_bgr_host(const vc_yuv_desc* d, const uint8_t* yuv, int b, int h, i
     VC_CHECK(yuv && bgr_out, VC_ERR_ARG, "null argument");
     YuvGeom g;
     VC_TRY(yuv_resolve(d, b, h, w, g));
-    const size_t in_bytes = yuv_batch_bytes(g, b), out_bytes = (size_t)b * h * w * 3, guard = 256;
-    vc_engine tmp;
-    uint8_t *ds = nullptr, *dd = nullptr;
-    int st = dev_alloc(&tmp, (void**)&ds, in_bytes);
-    if (st == VC_OK) st = dev_alloc(&tmp, (void**)&dd, out_bytes + 2 * guard);
-    if (st == VC_OK && (hipMemcpy(ds, yuv, in_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemset(dd, 0xA5, out_bytes + 2 * guard) != hipSuccess)) {
-        set_error("upload failed");
-        st = VC_ERR_HIP;
-    }
-    if (st == VC_OK) st = launch_yuv_to_bgr(g, ds, dd + guard, b, nullptr);
-    if (st == VC_OK) {
-        uint8_t edge[512];
-        if (hipMemcpy(bgr_out, dd + guard, out_bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(edge, dd, guard, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(edge + guard, dd + guard + out_bytes, guard, hipMemcpyDeviceToHost) != hipSuccess) {
-            set_error("yuv_to_bgr_kernel failed: %s", hipGetErrorString(hipGetLastError()));
-            st = VC_ERR_HIP;
-        }
-        for (size_t i = 0; i < 2 * guard && st == VC_OK; ++i)
-            if (edge[i] != 0xA5) { set_error("yuv_to_bgr_kernel wrote outside its output (guard byte %zu)", i); st = VC_ERR_HIP; }
-    }
-    for (void* q : tmp.allocs) (void)hipFree(q);
-    tmp.allocs.clear();
-    return st;
+    const size_t in_bytes = yuv_batch_bytes(g, b);
+    DevScratch mem;
+    uint8_t* ds = nullptr;
+    GuardedOut dd;
+    VC_TRY(mem.alloc(&ds, in_bytes));
+    VC_TRY(dd.alloc(mem, (size_t)b * h * w * 3));
+    VC_HIP(hipMemcpy(ds, yuv, in_bytes, hipMemcpyHostToDevice));
+    VC_TRY(launch_yuv_to_bgr(g, ds, dd.out(), b, nullptr));
+    return dd.read_back(bgr_out, "yuv_to_bgr_kernel");
 }
 
 int vc_yuv_to_bgr_dev(const vc_yuv_desc* d, const void* yuv_dev, int b, int h, int w, void* bgr_dev) {
@@ -522,14 +530,7 @@ int vc_stream_stage_yuv_host(vc_engine* e, const vc_yuv_desc* d, const uint8_t* 
     int slot = 0;
     VC_TRY(ingest_take_slot(e, b, h, w, &slot));
     const size_t bytes = yuv_batch_bytes(g, b);
-    if (bytes > e->yuv_raw_bytes[slot]) {
-        // first YUV batch of this slot (or a pitch wider than any before): everything the copy stream still has in flight reads the old buffer
-        VC_HIP(hipStreamSynchronize(e->cstream));
-        const size_t tight = (size_t)e->cfg.max_batch * e->cfg.max_frame_h * e->cfg.max_frame_w * 3 / 2;
-        e->yuv_raw_bytes[slot] = 0;
-        VC_TRY(dev_realloc(e, (void**)&e->d_yuv_raw[slot], std::max(bytes, tight)));
-        e->yuv_raw_bytes[slot] = std::max(bytes, tight);
-    }
+    VC_TRY(ingest_raw_reserve(e, slot, bytes));
     VC_HIP(hipMemcpyAsync(e->d_yuv_raw[slot], yuv_host, bytes, hipMemcpyHostToDevice, e->cstream));
     VC_TRY(launch_yuv_to_bgr(g, e->d_yuv_raw[slot], e->d_ingest[slot], b, e->cstream));
     return ingest_publish(e, slot, frames_dev_out);
@@ -551,52 +552,12 @@ int vc_frames_layout_host(const vc_frame_src* frames, int b, int h, int w, int64
     return frames_resolve(frames, b, h, w, false, geo, raw_off, raw_bytes);
 }
 
-// Parity entry point of frames_to_bgr_kernel.  Every frame is uploaded to an address congruent to its host pointer mod 16, so that the
-// caller chooses the 16-byte or the generic path by where it puts the frame; the output sits between two guard blocks as above.
+// Parity entry point of frames_to_bgr_kernel (frames_to_bgr_parity).
 int vc_frames_to_bgr_host(const vc_frame_src* frames, int b, int h, int w, uint8_t* bgr_out) {
     VC_CHECK(bgr_out, VC_ERR_ARG, "null argument");
     std::vector<YuvGeom> geo;
     VC_TRY(frames_resolve(frames, b, h, w, true, geo, nullptr, nullptr));
-    const size_t frame_out = (size_t)h * w * 3, out_bytes = (size_t)b * frame_out, guard = 256;
-    std::vector<size_t> off((size_t)b), len((size_t)b);
-    size_t in_bytes = 0;
-    for (int f = 0; f < b; ++f) {
-        len[f] = frames[f].kind == VC_SRC_YUV_HOST ? yuv_batch_bytes(geo[f], 1) : frame_out;
-        off[f] = (in_bytes + 15) / 16 * 16 + (uintptr_t)frames[f].data % 16;
-        in_bytes = off[f] + len[f];
-    }
-    vc_engine tmp;
-    uint8_t *ds = nullptr, *dd = nullptr;
-    FrameEntry* dt = nullptr;
-    int st = dev_alloc(&tmp, (void**)&ds, in_bytes);
-    if (st == VC_OK) st = dev_alloc(&tmp, (void**)&dd, out_bytes + 2 * guard);
-    if (st == VC_OK) st = dev_alloc(&tmp, (void**)&dt, (size_t)b * sizeof(FrameEntry));
-    if (st == VC_OK) {
-        std::vector<FrameEntry> tab((size_t)b);
-        bool ok = hipMemset(dd, 0xA5, out_bytes + 2 * guard) == hipSuccess;
-        for (int f = 0; f < b && ok; ++f) {
-            ok = hipMemcpy(ds + off[f], frames[f].data, len[f], hipMemcpyHostToDevice) == hipSuccess;
-            tab[f] = frame_entry(frames[f].kind, geo[f], ds + off[f], dd + guard + (size_t)f * frame_out, h, w);
-        }
-        if (!ok || hipMemcpy(dt, tab.data(), (size_t)b * sizeof(FrameEntry), hipMemcpyHostToDevice) != hipSuccess) {
-            set_error("upload failed");
-            st = VC_ERR_HIP;
-        }
-    }
-    if (st == VC_OK) st = launch_frames_to_bgr(dt, dd + guard, b, h, w, nullptr);
-    if (st == VC_OK) {
-        uint8_t edge[512];
-        if (hipMemcpy(bgr_out, dd + guard, out_bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(edge, dd, guard, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(edge + guard, dd + guard + out_bytes, guard, hipMemcpyDeviceToHost) != hipSuccess) {
-            set_error("frames_to_bgr_kernel failed: %s", hipGetErrorString(hipGetLastError()));
-            st = VC_ERR_HIP;
-        }
-        for (size_t i = 0; i < 2 * guard && st == VC_OK; ++i)
-            if (edge[i] != 0xA5) { set_error("frames_to_bgr_kernel wrote outside its output (guard byte %zu)", i); st = VC_ERR_HIP; }
-    }
-    for (void* q : tmp.allocs) (void)hipFree(q);
-    tmp.allocs.clear();
-    return st;
+    return frames_to_bgr_parity(frames, b, h, w, nullptr, (size_t)h * w * 3, geo, bgr_out, "frames_to_bgr_kernel");
 }
 
 // The kernel on the caller's own device buffers (measurement), null stream, no wait.  With `frames` the table is built and uploaded
@@ -617,55 +578,14 @@ int vc_frames_to_bgr_dev(const vc_frame_src* frames, int b, int h, int w, void* 
     return launch_frames_to_bgr((const FrameEntry*)table_dev, (uint8_t*)bgr_dev, b, h, w, nullptr);
 }
 
-// One batch from per-frame sources.  On the copy stream: one copy per host frame (BGR straight into its place in the slot, YUV into
-// the slot's raw buffer at its vc_frames_layout_host offset), one copy of the frame table (per-slot pinned table -> per-slot device
-// table: the slot rules guarantee that the slot's previous batch, and with it the previous copy of the table, is complete), at most one
-// launch, the slot's event.
+// One batch from per-frame sources (stage_frame_list).
 int vc_stream_stage_frames(vc_engine* e, const vc_frame_src* frames, int b, int h, int w, void** frames_dev_out) {
     VC_CHECK(e && frames_dev_out, VC_ERR_ARG, "null argument");
     std::vector<YuvGeom> geo;
     std::vector<int64_t> raw_off((size_t)std::max(b, 1));
     size_t raw_bytes = 0;
     VC_TRY(frames_resolve(frames, b, h, w, false, geo, raw_off.data(), &raw_bytes));
-    int slot = 0;
-    VC_TRY(ingest_take_slot(e, b, h, w, &slot));
-    if (!e->h_frame_tab[slot]) {
-        VC_TRY(host_alloc(e, &e->h_frame_tab[slot], (size_t)e->cfg.max_batch * sizeof(FrameEntry)));
-        VC_TRY(dev_alloc(e, &e->d_frame_tab[slot], (size_t)e->cfg.max_batch * sizeof(FrameEntry)));
-    }
-    if (raw_bytes > e->yuv_raw_bytes[slot]) {
-        // as in vc_stream_stage_yuv_host: everything the copy stream still has in flight reads the old buffer
-        VC_HIP(hipStreamSynchronize(e->cstream));
-        const size_t tight = (size_t)e->cfg.max_batch * e->cfg.max_frame_h * e->cfg.max_frame_w * 3 / 2;
-        e->yuv_raw_bytes[slot] = 0;
-        VC_TRY(dev_realloc(e, (void**)&e->d_yuv_raw[slot], std::max(raw_bytes, tight)));
-        e->yuv_raw_bytes[slot] = std::max(raw_bytes, tight);
-    }
-    FrameEntry* tab = (FrameEntry*)e->h_frame_tab[slot];
-    const size_t frame_out = (size_t)h * w * 3;
-    bool launch = false;
-    for (int f = 0; f < b; ++f) {
-        const vc_frame_src& s = frames[f];
-        uint8_t* dst = e->d_ingest[slot] + (size_t)f * frame_out;
-        const uint8_t* src = (const uint8_t*)s.data;
-        if (s.kind == VC_SRC_BGR_HOST) {
-            VC_HIP(hipMemcpyAsync(dst, s.data, frame_out, hipMemcpyHostToDevice, e->cstream));
-            tab[f] = FrameEntry{};                          // FRAME_NONE: already in place
-            continue;
-        }
-        if (s.kind == VC_SRC_YUV_HOST) {
-            uint8_t* raw = e->d_yuv_raw[slot] + raw_off[f];
-            VC_HIP(hipMemcpyAsync(raw, s.data, yuv_batch_bytes(geo[f], 1), hipMemcpyHostToDevice, e->cstream));
-            src = raw;
-        }
-        tab[f] = frame_entry(s.kind, geo[f], src, dst, h, w);
-        launch = true;
-    }
-    if (launch) {
-        VC_HIP(hipMemcpyAsync(e->d_frame_tab[slot], tab, (size_t)b * sizeof(FrameEntry), hipMemcpyHostToDevice, e->cstream));
-        VC_TRY(launch_frames_to_bgr((const FrameEntry*)e->d_frame_tab[slot], e->d_ingest[slot], b, h, w, e->cstream));
-    }
-    return ingest_publish(e, slot, frames_dev_out);
+    return stage_frame_list(e, frames, b, h, w, nullptr, (size_t)h * w * 3, geo, raw_off.data(), raw_bytes, frames_dev_out);
 }
 
 // ---- sized batches -------------------------------------------------------------------------------------------------------------------
@@ -680,121 +600,34 @@ int vc_frames_layout_sized_host(const vc_frame_src* frames, const vc_frame_dims*
                                 int* net_h, int* net_w) {
     VC_CHECK(raw_off && raw_bytes && cell && net_h && net_w, VC_ERR_ARG, "null argument");
     std::vector<YuvGeom> geo;
-    SizedLayout lay;
-    VC_TRY(frames_resolve_sized(frames, dims, b, img_size, false, geo, raw_off, raw_bytes, lay));
-    *cell = lay.cell; *net_h = lay.net_h; *net_w = lay.net_w;
+    SizedDims sd;
+    VC_TRY(frames_resolve_sized(frames, dims, b, img_size, false, geo, raw_off, raw_bytes, sd));
+    *cell = sd.cell; *net_h = sd.net_h; *net_w = sd.net_w;
     return VC_OK;
 }
 
-// Parity entry point of frames_to_bgr_sized_kernel.  The caller's cells are uploaded between two guard blocks, converted into and read
-// back: what the kernel leaves alone inside a cell comes back as the caller filled it.  Frames are uploaded to addresses congruent to
-// their host pointers mod 16, as in vc_frames_to_bgr_host.  Network shapes are not compared here (img_size 1 gives every frame 32 x 32).
+// Parity entry point of frames_to_bgr_sized_kernel (frames_to_bgr_parity).  Network shapes are not compared here (img_size 1 gives every
+// frame 32 x 32).
 int vc_frames_to_bgr_sized_host(const vc_frame_src* frames, const vc_frame_dims* dims, int b, uint8_t* cells) {
     VC_CHECK(cells, VC_ERR_ARG, "null argument");
     std::vector<YuvGeom> geo;
-    SizedLayout lay;
-    VC_TRY(frames_resolve_sized(frames, dims, b, 1, true, geo, nullptr, nullptr, lay));
-    const size_t out_bytes = (size_t)b * lay.cell, guard = 256;
-    std::vector<size_t> off((size_t)b), len((size_t)b);
-    size_t in_bytes = 0;
-    for (int f = 0; f < b; ++f) {
-        len[f] = frames[f].kind == VC_SRC_YUV_HOST ? yuv_batch_bytes(geo[f], 1) : (size_t)dims[f].h * dims[f].w * 3;
-        off[f] = (in_bytes + 15) / 16 * 16 + (uintptr_t)frames[f].data % 16;
-        in_bytes = off[f] + len[f];
-    }
-    vc_engine tmp;
-    uint8_t *ds = nullptr, *dd = nullptr, *dt = nullptr;
-    const size_t tab_bytes = (size_t)b * (sizeof(FrameEntry) + sizeof(FrameCell));
-    int st = dev_alloc(&tmp, (void**)&ds, in_bytes);
-    if (st == VC_OK) st = dev_alloc(&tmp, (void**)&dd, out_bytes + 2 * guard);
-    if (st == VC_OK) st = dev_alloc(&tmp, (void**)&dt, tab_bytes);
-    if (st == VC_OK) {
-        std::vector<uint8_t> tabs(tab_bytes);
-        FrameEntry* tab = (FrameEntry*)tabs.data();
-        FrameCell* cl = (FrameCell*)(tabs.data() + (size_t)b * sizeof(FrameEntry));
-        bool ok = hipMemset(dd, 0xA5, out_bytes + 2 * guard) == hipSuccess && hipMemcpy(dd + guard, cells, out_bytes, hipMemcpyHostToDevice) == hipSuccess;
-        for (int f = 0; f < b && ok; ++f) {
-            ok = hipMemcpy(ds + off[f], frames[f].data, len[f], hipMemcpyHostToDevice) == hipSuccess;
-            tab[f] = frame_entry(frames[f].kind, geo[f], ds + off[f], dd + guard + (size_t)f * lay.cell, dims[f].h, dims[f].w);
-            cl[f] = FrameCell{(unsigned long long)f * lay.cell, dims[f].h, dims[f].w};
-        }
-        if (!ok || hipMemcpy(dt, tabs.data(), tab_bytes, hipMemcpyHostToDevice) != hipSuccess) {
-            set_error("upload failed");
-            st = VC_ERR_HIP;
-        }
-    }
-    if (st == VC_OK) st = launch_frames_to_bgr_sized((const FrameEntry*)dt, (const FrameCell*)(dt + (size_t)b * sizeof(FrameEntry)), dd + guard, b, dims, nullptr);
-    if (st == VC_OK) {
-        uint8_t edge[512];
-        if (hipMemcpy(cells, dd + guard, out_bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(edge, dd, guard, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(edge + guard, dd + guard + out_bytes, guard, hipMemcpyDeviceToHost) != hipSuccess) {
-            set_error("frames_to_bgr_sized_kernel failed: %s", hipGetErrorString(hipGetLastError()));
-            st = VC_ERR_HIP;
-        }
-        for (size_t i = 0; i < 2 * guard && st == VC_OK; ++i)
-            if (edge[i] != 0xA5) { set_error("frames_to_bgr_sized_kernel wrote outside its output (guard byte %zu)", i); st = VC_ERR_HIP; }
-    }
-    for (void* q : tmp.allocs) (void)hipFree(q);
-    tmp.allocs.clear();
-    return st;
+    SizedDims sd;
+    VC_TRY(frames_resolve_sized(frames, dims, b, 1, true, geo, nullptr, nullptr, sd));
+    return frames_to_bgr_parity(frames, b, sd.max_h, sd.max_w, dims, sd.cell, geo, cells, "frames_to_bgr_sized_kernel");
 }
 
-// vc_stream_stage_frames with every frame's own size: frame f lands in cell f of the slot.  The per-slot tables hold the frame entries
-// followed by the cells, so one copy still carries both; a slot remembers the dims of its sized batch for vc_stream_submit_sized.
+// vc_stream_stage_frames with every frame's own size: frame f lands in cell f of the slot (stage_frame_list).
 int vc_stream_stage_frames_sized(vc_engine* e, const vc_frame_src* frames, const vc_frame_dims* dims, int b, void** frames_dev_out) {
     VC_CHECK(e && frames_dev_out, VC_ERR_ARG, "null argument");
     std::vector<YuvGeom> geo;
     std::vector<int64_t> raw_off((size_t)std::max(b, 1));
     size_t raw_bytes = 0;
-    SizedLayout lay;
-    VC_TRY(frames_resolve_sized(frames, dims, b, e->cfg.img_size, false, geo, raw_off.data(), &raw_bytes, lay));
+    SizedDims sd;
+    VC_TRY(frames_resolve_sized(frames, dims, b, e->cfg.img_size, false, geo, raw_off.data(), &raw_bytes, sd));
     VC_CHECK(e->finalized && e->cfg.with_detector, VC_ERR_STATE, "engine not finalized");
-    VC_CHECK(b <= e->cfg.max_batch && lay.max_h <= e->cfg.max_frame_h && lay.max_w <= e->cfg.max_frame_w && (size_t)b * lay.cell <= ingest_slot_bytes(e), VC_ERR_CAPACITY,
-             "batch of %d frames up to %dx%d (%zu-byte cells) exceeds max_batch / max_frame_h / max_frame_w", b, lay.max_h, lay.max_w, lay.cell);
-    int slot = 0;
-    VC_TRY(ingest_take_slot(e, b, lay.max_h, lay.max_w, &slot));
-    const size_t entry_bytes = sizeof(FrameEntry) + sizeof(FrameCell);
-    if (!e->h_sized_tab[slot]) {
-        VC_TRY(host_alloc(e, &e->h_sized_tab[slot], (size_t)e->cfg.max_batch * entry_bytes));
-        VC_TRY(dev_alloc(e, &e->d_sized_tab[slot], (size_t)e->cfg.max_batch * entry_bytes));
-    }
-    if (raw_bytes > e->yuv_raw_bytes[slot]) {
-        // as in vc_stream_stage_yuv_host: everything the copy stream still has in flight reads the old buffer
-        VC_HIP(hipStreamSynchronize(e->cstream));
-        const size_t tight = (size_t)e->cfg.max_batch * e->cfg.max_frame_h * e->cfg.max_frame_w * 3 / 2;
-        e->yuv_raw_bytes[slot] = 0;
-        VC_TRY(dev_realloc(e, (void**)&e->d_yuv_raw[slot], std::max(raw_bytes, tight)));
-        e->yuv_raw_bytes[slot] = std::max(raw_bytes, tight);
-    }
-    FrameEntry* tab = (FrameEntry*)e->h_sized_tab[slot];
-    FrameCell* cl = (FrameCell*)((uint8_t*)e->h_sized_tab[slot] + (size_t)b * sizeof(FrameEntry));
-    bool launch = false;
-    for (int f = 0; f < b; ++f) {
-        const vc_frame_src& s = frames[f];
-        const int h = dims[f].h, w = dims[f].w;
-        uint8_t* dst = e->d_ingest[slot] + (size_t)f * lay.cell;
-        const uint8_t* src = (const uint8_t*)s.data;
-        cl[f] = FrameCell{(unsigned long long)f * lay.cell, h, w};
-        if (s.kind == VC_SRC_BGR_HOST) {
-            VC_HIP(hipMemcpyAsync(dst, s.data, (size_t)h * w * 3, hipMemcpyHostToDevice, e->cstream));
-            tab[f] = FrameEntry{};                          // FRAME_NONE: already in place
-            continue;
-        }
-        if (s.kind == VC_SRC_YUV_HOST) {
-            uint8_t* raw = e->d_yuv_raw[slot] + raw_off[f];
-            VC_HIP(hipMemcpyAsync(raw, s.data, yuv_batch_bytes(geo[f], 1), hipMemcpyHostToDevice, e->cstream));
-            src = raw;
-        }
-        tab[f] = frame_entry(s.kind, geo[f], src, dst, h, w);
-        launch = true;
-    }
-    if (launch) {
-        uint8_t* dt = (uint8_t*)e->d_sized_tab[slot];
-        VC_HIP(hipMemcpyAsync(dt, tab, (size_t)b * entry_bytes, hipMemcpyHostToDevice, e->cstream));
-        VC_TRY(launch_frames_to_bgr_sized((const FrameEntry*)dt, (const FrameCell*)(dt + (size_t)b * sizeof(FrameEntry)), e->d_ingest[slot], b, dims, e->cstream));
-    }
-    e->ingest_dims[slot].assign(dims, dims + b);
-    return ingest_publish(e, slot, frames_dev_out);
+    VC_CHECK(b <= e->cfg.max_batch && sd.max_h <= e->cfg.max_frame_h && sd.max_w <= e->cfg.max_frame_w && (size_t)b * sd.cell <= ingest_slot_bytes(e), VC_ERR_CAPACITY,
+             "batch of %d frames up to %dx%d (%zu-byte cells) exceeds max_batch / max_frame_h / max_frame_w", b, sd.max_h, sd.max_w, sd.cell);
+    return stage_frame_list(e, frames, b, sd.max_h, sd.max_w, dims, sd.cell, geo, raw_off.data(), raw_bytes, frames_dev_out);
 }
 
 }  // extern "C"

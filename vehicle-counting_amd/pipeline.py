@@ -383,23 +383,38 @@ class CountingPipeline:
         (`engine.autoshape_net_size`) is the same -- at size 640, 1920x1080, 1280x720, 640x360 and 320x180 all run at 384x640.  Each
         batch is a sized batch (`stream_stage_frames_sized`): one detector pass, and every camera still gets the result of running
         alone.  Cameras whose network shapes differ are refused; run each group of equal shapes in a call of its own."""
-        if mixed_sizes or host_frames or any(isinstance(s, YuvFrameSource) for s in sources):
-            return self._run_streams_frames(sources, cam_names, zone_paths, batch, host_frames, mixed_sizes)
         import torch
         S = len(sources)
-        shapes = {s.frames.shape[1:] for s in sources}
-        assert len(shapes) == 1, "run_streams: all cameras must deliver frames of one size"
-        h, w, _ = next(iter(shapes))
-        stages = [self._stages(n, s.video_info, z) for n, s, z in zip(cam_names, sources, zone_paths)]
-        tids = np.array([st[0].tracker_ids for st in stages], np.int32)                 # [S][num_classes]
         order = []                                                                       # (camera, frame) round-robin, exhausted cameras drop out
         for t in range(max(len(s) for s in sources)):
             order.extend((c, t) for c in range(S) if t < len(sources[c]))
         cams = np.array([c for c, _ in order], np.int32)
         fidx = np.array([t for _, t in order], np.int64)
-        dev = torch.from_numpy(np.stack([sources[c].frames[t] for c, t in order])).to(f"cuda:{self.engine.cfg.device}")
-        objs = [{"frames": [], "tracks": [], "labels": [], "boxes": []} for _ in range(S)]
         starts = list(range(0, len(order), batch))
+
+        def span(n):
+            f0 = starts[n]
+            return f0, min(batch, len(order) - f0)
+
+        # the three modes differ in how batch n is staged, submitted and run: stage(n), submit(n), run(n, tids, cams of the batch)
+        if mixed_sizes or host_frames or any(isinstance(s, YuvFrameSource) for s in sources):
+            stage, submit, run = self._frames_batches(sources, cam_names, host_frames, mixed_sizes, order, span)
+        else:
+            shapes = {s.frames.shape[1:] for s in sources}
+            assert len(shapes) == 1, "run_streams: all cameras must deliver frames of one size"
+            h, w, _ = next(iter(shapes))
+            dev = torch.from_numpy(np.stack([sources[c].frames[t] for c, t in order])).to(f"cuda:{self.engine.cfg.device}")
+
+            def batch_ptr(n):
+                f0, b = span(n)
+                return dev[f0:f0 + b].data_ptr(), b
+
+            stage = lambda n: None                                                       # the whole clip is on the device already
+            submit = lambda n: self.engine.stream_submit(*batch_ptr(n), h, w)
+            run = lambda n, tids, bcams: self.engine.stream_run_async_multi(tids, bcams, *batch_ptr(n), h, w)
+        stages = [self._stages(n, s.video_info, z) for n, s, z in zip(cam_names, sources, zone_paths)]
+        tids = np.array([st[0].tracker_ids for st in stages], np.int32)                 # [S][num_classes]
+        objs = [{"frames": [], "tracks": [], "labels": [], "boxes": []} for _ in range(S)]
 
         def record(f0, rows, fb):
             g = f0 + fb                                                                  # global position of each row's frame
@@ -411,31 +426,30 @@ class CountingPipeline:
                 o["labels"].extend(rows[sel, 5].tolist())
                 o["boxes"].extend(list(rows[sel, :4].copy()))
 
-        def span(n):
-            f0 = starts[n]
-            return f0, min(batch, len(order) - f0)
-
         with self._video(*[st[0] for st in stages]):
-            f0, b = span(0)
-            self.engine.stream_submit(dev[f0:f0 + b].data_ptr(), b, h, w)
+            for n in range(min(2, len(starts))):            # staging order = batch order (four slots, round-robin)
+                stage(n)
+            if starts:
+                submit(0)
             for n in range(len(starts)):
                 f0, b = span(n)
+                if n + 2 < len(starts):                     # gather batch n+2 under the detector of batch n+1
+                    stage(n + 2)
                 if n + 1 < len(starts):
-                    g0, gb = span(n + 1)
-                    self.engine.stream_submit(dev[g0:g0 + gb].data_ptr(), gb, h, w)
-                self.engine.stream_run_async_multi(tids, cams[f0:f0 + b], dev[f0:f0 + b].data_ptr(), b, h, w)
+                    submit(n + 1)
+                run(n, tids, cams[f0:f0 + b])
                 if n > 0:
                     record(starts[n - 1], *self.engine.stream_collect()[:2])
             if starts:
                 record(starts[-1], *self.engine.stream_collect()[:2])
         return [self._finish(st[1], o, n) for st, o, n in zip(stages, objs, cam_names)]
 
-    def _run_streams_frames(self, sources, cam_names, zone_paths, batch, host_frames, mixed_sizes=False):
-        """run_streams over per-camera clips: camera c frame t is read at base_c + t * stride_c with that camera's descriptor."""
+    def _frames_batches(self, sources, cam_names, host_frames, mixed_sizes, order, span):
+        """run_streams over per-camera clips: camera c frame t is read at base_c + t * stride_c with that camera's descriptor.  Returns
+        (stage, submit, run) for the batches of `order` that `span` cuts out; they keep the clips alive."""
         import torch
 
         from .engine import frame_src
-        S = len(sources)
         yuv = [isinstance(s, YuvFrameSource) for s in sources]
         sizes = [(s.h, s.w) if y else tuple(s.frames.shape[1:3]) for s, y in zip(sources, yuv)]
         if mixed_sizes:
@@ -450,42 +464,19 @@ class CountingPipeline:
         # each camera's clip where its decoder would leave it: one tensor per camera, never an interleaved copy
         clips = [torch.from_numpy(s.data if y else s.frames.reshape(len(s.frames), -1)) for s, y in zip(sources, yuv)]
         clips = [c.pin_memory() if host_frames else c.to(f"cuda:{self.engine.cfg.device}") for c in clips]
-        base, stride = [c.data_ptr() for c in clips], [c.shape[1] for c in clips]
+        stride = [c.shape[1] for c in clips]
         kind = [("yuv" if y else "bgr") + ("_host" if host_frames else "_dev") for y in yuv]
         desc = [s.desc if y else None for s, y in zip(sources, yuv)]
-        stages = [self._stages(n, s.video_info, z) for n, s, z in zip(cam_names, sources, zone_paths)]
-        tids = np.array([st[0].tracker_ids for st in stages], np.int32)                 # [S][num_classes]
-        order = []                                                                       # (camera, frame) round-robin, exhausted cameras drop out
-        for t in range(max(len(s) for s in sources)):
-            order.extend((c, t) for c in range(S) if t < len(sources[c]))
-        cams = np.array([c for c, _ in order], np.int32)
-        fidx = np.array([t for _, t in order], np.int64)
-        objs = [{"frames": [], "tracks": [], "labels": [], "boxes": []} for _ in range(S)]
-        starts = list(range(0, len(order), batch))
         ptr = {}
-
-        def record(f0, rows, fb):
-            g = f0 + fb                                                                  # global position of each row's frame
-            for c in range(S):
-                sel = cams[g] == c
-                o = objs[c]
-                o["frames"].extend((fidx[g[sel]] + 1).tolist())
-                o["tracks"].extend(rows[sel, 4].tolist())
-                o["labels"].extend(rows[sel, 5].tolist())
-                o["boxes"].extend(list(rows[sel, :4].copy()))
-
-        def span(n):
-            f0 = starts[n]
-            return f0, min(batch, len(order) - f0)
-
-        def stage(n):
-            f0, b = span(n)
-            srcs = [frame_src(kind[c], base[c] + t * stride[c], desc[c]) for c, t in order[f0:f0 + b]]
-            ptr[n] = self.engine.stream_stage_frames_sized(srcs, dims(n)) if mixed_sizes else self.engine.stream_stage_frames(srcs, h, w)
 
         def dims(n):
             f0, b = span(n)
             return [sizes[c] for c, _ in order[f0:f0 + b]]
+
+        def stage(n):
+            f0, b = span(n)
+            srcs = [frame_src(kind[c], clips[c].data_ptr() + t * stride[c], desc[c]) for c, t in order[f0:f0 + b]]
+            ptr[n] = self.engine.stream_stage_frames_sized(srcs, dims(n)) if mixed_sizes else self.engine.stream_stage_frames(srcs, h, w)
 
         def submit(n):
             if mixed_sizes:
@@ -493,27 +484,13 @@ class CountingPipeline:
             else:
                 self.engine.stream_submit(ptr[n], span(n)[1], h, w)
 
-        with self._video(*[st[0] for st in stages]):
-            for n in range(min(2, len(starts))):            # staging order = batch order (four slots, round-robin)
-                stage(n)
-            if starts:
-                submit(0)
-            for n in range(len(starts)):
-                f0, b = span(n)
-                if n + 2 < len(starts):                     # gather batch n+2 under the detector of batch n+1
-                    stage(n + 2)
-                if n + 1 < len(starts):
-                    submit(n + 1)
-                if mixed_sizes:
-                    self.engine.stream_run_async_multi_sized(tids, cams[f0:f0 + b], ptr[n], dims(n))
-                else:
-                    self.engine.stream_run_async_multi(tids, cams[f0:f0 + b], ptr[n], b, h, w)
-                if n > 0:
-                    record(starts[n - 1], *self.engine.stream_collect()[:2])
-                ptr.pop(n - 1, None)
-            if starts:
-                record(starts[-1], *self.engine.stream_collect()[:2])
-        return [self._finish(st[1], o, n) for st, o, n in zip(stages, objs, cam_names)]
+        def run(n, tids, bcams):
+            if mixed_sizes:
+                self.engine.stream_run_async_multi_sized(tids, bcams, ptr.pop(n), dims(n))
+            else:
+                self.engine.stream_run_async_multi(tids, bcams, ptr.pop(n), span(n)[1], h, w)
+
+        return stage, submit, run
 
     def run_frame_sharded(self, source, cam_name, zone_path, chunk=8, device=None):
         """ONE camera stream on several GPUs, on the product's own batched path: the stateless front end shards by
