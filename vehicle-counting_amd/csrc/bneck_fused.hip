@@ -14,11 +14,17 @@
 // 128 frames at 80 x 80) is neither written nor read back and the 1x1 -- a launch at the HBM roof of its own -- disappears.  The
 // consumer waves re-lay their bf16 m values from the accumulator layout (lane = 4 channels of a pixel) into MFMA B operands (lane = 8
 // consecutive channels of a pixel, all four k quarters the same pixel) with three rounds of v_permlane16/32_swap, no LDS round trip;
-// y2 is read from HBM in operand order; cv3's weights (32 KB) take the rest of the LDS (157 of 160 KB).  k order = channel order:
+// y2 is read from HBM in operand order; cv3's weights (32 KB) and bias take the rest of the LDS (157.5 of 160 KB).  k order = channel order:
 // bit-identical to the separate launch.  Measured per 128 frames at 80 x 80: 0.195 ms against 0.100 + 0.117 for the two launches.
 // (cv3 as a third pipeline stage on the PRODUCER waves -- m handed over in the b1 buffer the consumers have just read, two workgroup
 // barriers per tile -- was built, bit-identical, and measured 0.28 ms: with 144 SiLU values per lane and tile the kernel is bound by the
 // quarter-rate transcendentals of its three epilogues, not by which wave runs them, and the second barrier costs more than it balances.)
+//
+// Epilogue rule: a consumer wave issues every global load of a tile (shortcut, y2) BEFORE the tile's first output store and reads what it
+// needs between its stores (cv3's bias) from LDS.  Stores count on vmcnt and retire in issue order (tools/ubench/vmcnt_order.hip), so a
+// wait for a load issued behind a store is a wait for the store's acknowledgement: with cv3's bias fetched from global memory per channel
+// tile the tile paid seven of them.  Per 256 frames at 80 x 80: 0.474 -> 0.387 ms with the shortcut, 0.417 -> 0.340 without; the plain
+// Bottleneck, whose four stores now follow its last wait, 0.248 -> 0.246 (profiles/epilogue_waits.md).
 #include <algorithm>
 
 #include "kernels.h"
@@ -77,6 +83,8 @@ __global__ __launch_bounds__(BN_NW * 64) void bneck_fused_kernel(const BnArgs a)
     __shared__ uint4 w1s[2 * 4 * 64];                      // 8 KB: cv1, [k step][channel tile][lane]
     __shared__ uint4 w2s[18 * 4 * 64];                     // 72 KB: cv2, [k step = 2 tap + half][channel tile][lane]
     __shared__ uint4 w3s[CV3 ? 4 * 8 * 64 : 1];            // CV3: 32 KB: cv3, [k step][channel tile][lane]
+    __shared__ float b3s[CV3 ? 128 : 4];                   // CV3: cv3's bias: its epilogue reads it BETWEEN the tile's stores, where a global load would wait for them
+    static_assert(sizeof(bs) + sizeof(w1s) + sizeof(w2s) + sizeof(w3s) + sizeof(b3s) <= 160 * 1024, "static LDS of bneck_fused_kernel exceeds a CU's 160 KB");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = lane & 15, kq = lane >> 4;
     constexpr int NT = BN_NW * 64;
@@ -93,6 +101,7 @@ __global__ __launch_bounds__(BN_NW * 64) void bneck_fused_kernel(const BnArgs a)
             const int l = i & 63, ct = (i >> 6) & 7, s = i >> 9;
             w3s[i] = a.w3[(size_t)(ct * 16 + (l & 15)) * a.kw3 + 4 * s + (l >> 4)];
         }
+        if (threadIdx.x < 128) b3s[threadIdx.x] = a.b3[threadIdx.x];
     }
     const bool producer = wave >= 4;
     const int gw = wave & 3;
@@ -172,7 +181,9 @@ __global__ __launch_bounds__(BN_NW * 64) void bneck_fused_kernel(const BnArgs a)
             const int tx = t % a.tiles_x, ty = (t / a.tiles_x) % a.tiles_y, b = t / (a.tiles_x * a.tiles_y);
             const int oy0 = ty * BN_TH, ox0 = tx * BN_TW;
             const char* bsb = (const char*)bs[(k - 1) & 1];
-            uint2 rs[4][2];                                 // the shortcut: this lane's 4 channels of its pixel per (channel tile, row), read ahead
+            // the shortcut: this lane's 4 channels of its pixel per (channel tile, row), read ahead.  (Zero without one: left uninitialised,
+            // the registers were carried from tile to tile and their copy opened every tile with s_waitcnt vmcnt(0), the previous tile's stores.)
+            uint2 rs[4][2] = {};
             if (RES) {
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
@@ -181,6 +192,18 @@ __global__ __launch_bounds__(BN_NW * 64) void bneck_fused_kernel(const BnArgs a)
                     const uint16_t* px = a.x + (((size_t)b * a.H + min(oy, a.H - 1)) * a.W + min(ox, a.W - 1)) * a.in_cs + a.in_co + kq * 4;
 #pragma unroll
                     for (int ct = 0; ct < 4; ++ct) rs[ct][q] = ok ? *(const uint2*)(px + ct * 16) : make_uint2(0u, 0u);
+                }
+            }
+            uint4 y2f[2][2];                                // CV3: this lane's y2 operands, [row][k step], read ahead of the 3x3 like the shortcut (issued in front of
+            // the 3x3's epilogue they were waited for at once: its first use of rs drains the whole counter)
+            if constexpr (CV3) {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const int oy = oy0 + gw * 2 + q, ox = ox0 + col;
+                    const bool ok = oy < a.H && ox < a.W;
+                    const uint16_t* px = a.y2 + (((size_t)b * a.H + min(oy, a.H - 1)) * a.W + min(ox, a.W - 1)) * a.y2_cs + kq * 8;
+                    y2f[q][0] = ok ? *(const uint4*)px : make_uint4(0u, 0u, 0u, 0u);
+                    y2f[q][1] = ok ? *(const uint4*)(px + 32) : make_uint4(0u, 0u, 0u, 0u);
                 }
             }
             f32x4b acc[4][2];
@@ -210,18 +233,7 @@ __global__ __launch_bounds__(BN_NW * 64) void bneck_fused_kernel(const BnArgs a)
                     for (int q = 0; q < 2; ++q) acc[ct][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfr[st & 1][ct].h, bfr[st & 1][q].h, acc[ct][q], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            uint4 y2f[2][2];                                // CV3: this lane's y2 operands, [row][k step], read ahead of the 3x3's epilogue
-            if constexpr (CV3) {
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const int oy = oy0 + gw * 2 + q, ox = ox0 + col;
-                    const bool ok = oy < a.H && ox < a.W;
-                    const uint16_t* px = a.y2 + (((size_t)b * a.H + min(oy, a.H - 1)) * a.W + min(ox, a.W - 1)) * a.y2_cs + kq * 8;
-                    y2f[q][0] = ok ? *(const uint4*)px : make_uint4(0u, 0u, 0u, 0u);
-                    y2f[q][1] = ok ? *(const uint4*)(px + 32) : make_uint4(0u, 0u, 0u, 0u);
-                }
-            }
-            uint4 mo[4];                                    // CV3: m as stored below, lane (col, kq) = channels 16 ct + 8 (kq >> 1) .. + 7 of row kq & 1
+            uint4 mo[4];                                    // m as stored (CV3: as cv3 takes it), lane (col, kq) = channels 16 ct + 8 (kq >> 1) .. + 7 of row kq & 1
 #pragma unroll
             for (int ct = 0; ct < 4; ++ct) {
                 uint2 P[2];
@@ -243,13 +255,17 @@ __global__ __launch_bounds__(BN_NW * 64) void bneck_fused_kernel(const BnArgs a)
                 }
                 const u32x2b sx = __builtin_amdgcn_permlane16_swap(P[0].x, P[1].x, false, false);
                 const u32x2b sy = __builtin_amdgcn_permlane16_swap(P[0].y, P[1].y, false, false);
-                const uint4 o4 = make_uint4(sx.x, sy.x, sx.y, sy.y);
-                if constexpr (CV3) {
-                    mo[ct] = o4;
-                } else {
-                    const int oy = oy0 + gw * 2 + (odd ? 1 : 0), ox = ox0 + col;
-                    if (oy < a.H && ox < a.W)
-                        *(uint4*)(a.y + (((size_t)b * a.H + oy) * a.W + ox) * a.out_cs + a.out_co + ct * 16 + (kq & ~1) * 4) = o4;
+                mo[ct] = make_uint4(sx.x, sy.x, sx.y, sy.y);
+            }
+            if constexpr (!CV3) {
+                // the four stores AFTER the last use of the shortcut: stores count on vmcnt and retire in issue order, so a wait for rs behind
+                // a store waits for the store's acknowledgement too (five such waits per tile when each channel tile was stored as it was ready)
+                __builtin_amdgcn_sched_barrier(0);
+                const int oy = oy0 + gw * 2 + (odd ? 1 : 0), ox = ox0 + col;
+                if (oy < a.H && ox < a.W) {
+                    uint16_t* po = a.y + (((size_t)b * a.H + oy) * a.W + ox) * a.out_cs + a.out_co + (kq & ~1) * 4;
+#pragma unroll
+                    for (int ct = 0; ct < 4; ++ct) *(uint4*)(po + ct * 16) = mo[ct];
                 }
             }
             if constexpr (CV3) {
@@ -285,8 +301,13 @@ __global__ __launch_bounds__(BN_NW * 64) void bneck_fused_kernel(const BnArgs a)
                 for (int ct = 0; ct < 8; ++ct)
 #pragma unroll
                     for (int q = 0; q < 2; ++q) zacc[ct][q] = (f32x4b){0.f, 0.f, 0.f, 0.f};
-                // (the weight fragment reads pipelined by hand one group of four ahead of the MFMAs, as in the 3x3, and the eight bias loads hoisted:
-                // 0.195 -> 0.265 ms -- the compiler's own schedule is the better one at 256 VGPRs; removed)
+                // (Hand-pipelined weight fragment reads were tried twice and removed twice.  First one group of four ahead of the MFMAs together
+                // with the eight bias loads hoisted into registers: 0.195 -> 0.265 ms per 128 frames at 256 VGPRs.  Then, with the bias in LDS
+                // (b3s), as a ring of four inline ds_read_b128 with counted lgkmcnt, each read issued behind the MFMAs four fragments earlier: it
+                // fits without spills only with cv1's / cv2's biases in LDS too (246 VGPRs), and per 256 frames the launch with the shortcut took
+                // 0.407 ms against 0.387 with hipcc's own schedule, the one without 0.349 against 0.340 (the biases in LDS alone: 0.400 / 0.338,
+                // and the plain Bottleneck 0.270 against 0.246) -- profiles/epilogue_waits.md.  The producer wave on the same SIMD fills the
+                // LDS round trips of this loop; what the tile waited for were the stores, see b3s.)
 #pragma unroll
                 for (int st = 0; st < 4; ++st) {
                     ChunkB bq[2];
@@ -302,7 +323,7 @@ __global__ __launch_bounds__(BN_NW * 64) void bneck_fused_kernel(const BnArgs a)
                 }
 #pragma unroll
                 for (int ct = 0; ct < 8; ++ct) {
-                    const float4 b3 = *(const float4*)(a.b3 + ct * 16 + kq * 4);
+                    const float4 b3 = *(const float4*)(b3s + ct * 16 + kq * 4);
                     uint2 P[2];
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
