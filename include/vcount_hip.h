@@ -480,6 +480,31 @@ int vc_zone_filter_host(const double* polygon_xy, int n_points, const int64_t* b
 /* candidates (already conf-filtered, in the reference's candidate order): boxes xyxy, conf, class -> kept rows */
 int vc_nms_host(const float* boxes4, const float* conf, const int* cls, int n, float iou, int max_det, int max_cand,
                 float* out6, int* out_n);
+/* The same three kernels on a batch: frame f has counts[f] <= max_cand candidates at boxes4 / conf / cls + f * max_cand (candidate
+ * order = position, as above) and its own scale_coords geometry geom4[f] = {net_h, net_w, src_h, src_w} (the engine's scale_geom_host;
+ * geom4 == NULL or net_h <= 0: network pixels, no rescale and no clamp, like vc_nms_host).  out6: [b][max_det][6], out_n: [b]. */
+int vc_nms_batch_host(const float* boxes4, const float* conf, const int* cls, const int* counts, int b, float iou, int max_det, int max_cand,
+                      const int* geom4, float* out6, int* out_n);
+/* The detector's tail on explicit logits, without an engine or a network: decode_kernel<f32 | bf16>, or head_compact_kernel +
+ * decode_sparse_kernel wired as the bf16 engine wires them (objectness plane = channels a * (nc + 5) + 4 of the logits, the head conv's
+ * input rows = the dense logits themselves, cap = every pixel of the batch).  The bf16 and the sparse mode round the logits to bf16. */
+typedef struct vc_decode_desc {
+    int b, nc;
+    int mode;            /* 0 dense f32, 1 dense bf16, 2 sparse (bf16) */
+    int ny[3], nx[3];
+    float stride[3];
+    float anchors[18];   /* [level][anchor][w, h] in pixels */
+    float conf;
+    int max_cand;
+} vc_decode_desc;
+/* logits[i]: float32 [b][ny[i]][nx[i]][round_up(3 * (nc + 5), 8)].  Candidates of frame f (slot order is arbitrary; idx = position in
+ * the reference's flattened prediction) at cand_* + f * max_cand, min(cand_count[f], max_cand) of them; overflow[f] = 1 when more than
+ * max_cand passed.  Sparse mode, when hc_count is given: hc_count[i] pixels of level i gathered, their indices (frame-major) in hc_list[i]
+ * (room for b * ny[i] * nx[i] each).  out6 != NULL chains the NMS over the SAME device buffers (iou, max_det, geom4 as in
+ * vc_nms_batch_host): out_n[f] = -1 for a frame whose overflow flag is set. */
+int vc_decode_host(const vc_decode_desc* d, const float* const* logits, int* cand_count, int* overflow, float* cand_box, float* cand_conf,
+                   int* cand_cls, int* cand_idx, int* hc_count, int* const* hc_list, float iou, int max_det, const int* geom4, float* out6,
+                   int* out_n);
 
 #ifdef __cplusplus
 }

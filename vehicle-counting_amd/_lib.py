@@ -68,6 +68,13 @@ class FrameDims(C.Structure):
     _fields_ = [("h", C.c_int), ("w", C.c_int)]
 
 
+class DecodeDesc(C.Structure):
+    """vc_decode_desc: the Detect levels, thresholds and mode of vc_decode_host."""
+    _fields_ = [("b", C.c_int), ("nc", C.c_int), ("mode", C.c_int), ("ny", C.c_int * 3), ("nx", C.c_int * 3), ("stride", C.c_float * 3),
+                ("anchors", C.c_float * 18), ("conf", C.c_float), ("max_cand", C.c_int)]
+
+
+DECODE_MODE_ID = {"f32": 0, "bf16": 1, "sparse": 2}
 FRAME_ENTRY_BYTES = 64       # VC_FRAME_ENTRY_BYTES
 
 
@@ -179,6 +186,8 @@ SIGNATURES = {
     "vc_letterbox_host": [_pu8, _i, _i, _i, _i, _i, _pf],
     "vc_zone_filter_host": [_pd, _i, _pl, _i, _pu8],
     "vc_nms_host": [_pf, _pf, _pi, _i, _f, _i, _i, _pf, _pi],
+    "vc_nms_batch_host": [_pf, _pf, _pi, _pi, _i, _f, _i, _i, _pi, _pf, _pi],
+    "vc_decode_host": [_P(DecodeDesc), _P(_pf), _pi, _pi, _pf, _pf, _pi, _pi, _pi, _P(_pi), _f, _i, _pi, _pf, _pi],
 }
 _RESTYPE = {"vc_last_error": C.c_char_p}
 

@@ -412,7 +412,8 @@ void scale_geom_host(const ScaleGeom& g, float out5[5]) {
 
 int launch_nms(int B, int max_cand, int max_det, float iou, const float* geom_dev, DetectPostBuffers& pb, hipStream_t s) {
     VC_CHECK(max_cand % 64 == 0 && max_cand <= 8192, VC_ERR_ARG, "nms: max_candidates must be a multiple of 64 and <= 8192");
-    hipLaunchKernelGGL(rank_sort_kernel, dim3(max_cand / 256, B), dim3(256), 0, s, max_cand, pb);
+    // (rounded up: max_cand is a multiple of 64, not of 256 -- 64 gave an empty grid, 320 left candidates 256.. unsorted)
+    hipLaunchKernelGGL(rank_sort_kernel, dim3((max_cand + 255) / 256, B), dim3(256), 0, s, max_cand, pb);
     const int tiles = std::min(max_cand / 64, 8);
     hipLaunchKernelGGL(nms_mask_kernel, dim3(tiles, tiles, B), dim3(64), 0, s, max_cand, iou, pb);
     // kept_idx holds one entry per kept box: never more than min(max_det, max_cand) (upstream's max_nms is 30 000)

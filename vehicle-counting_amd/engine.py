@@ -777,3 +777,63 @@ def nms(boxes, conf, cls, iou=0.45, max_det=300, max_cand=4096):
     L.check(L.lib().vc_nms_host(L.ptr(b, C.c_float), L.ptr(c, C.c_float), L.ptr(k, C.c_int), len(c), iou, max_det, max_cand,
                                 L.ptr(out, C.c_float), C.byref(n)))
     return out[: n.value].copy()
+
+
+def _geom_array(geoms, b):
+    if geoms is None:
+        return None
+    g = np.ascontiguousarray(geoms, dtype=np.int32).reshape(-1, 4)
+    assert len(g) == b, "one (net_h, net_w, src_h, src_w) per frame"
+    return g
+
+
+def nms_batch(boxes, conf, cls, counts, iou=0.45, max_det=300, max_cand=4096, geoms=None):
+    """vc_nms_batch_host: rank_sort + nms_mask + nms_scan on a batch of explicit candidate lists.  boxes / conf / cls: one array per frame
+    (candidate order = position) or padded [b][max_cand] arrays with `counts`; geoms: per frame (net_h, net_w, src_h, src_w) for
+    scale_coords, a row of zeros or None = network pixels.  Returns ([b][max_det][6] rows, [b] counts)."""
+    b = len(counts)
+    bx, cf, cl = np.zeros((b, max_cand, 4), np.float32), np.zeros((b, max_cand), np.float32), np.zeros((b, max_cand), np.int32)
+    for f, n in enumerate(counts):
+        bx[f, :n], cf[f, :n], cl[f, :n] = np.reshape(boxes[f], (-1, 4))[:n], np.reshape(conf[f], -1)[:n], np.reshape(cls[f], -1)[:n]
+    cnt = np.ascontiguousarray(counts, dtype=np.int32)
+    g = _geom_array(geoms, b)
+    out, n_out = np.zeros((b, max_det, 6), np.float32), np.zeros(b, np.int32)
+    L.check(L.lib().vc_nms_batch_host(L.ptr(bx, C.c_float), L.ptr(cf, C.c_float), L.ptr(cl, C.c_int), L.ptr(cnt, C.c_int), b, iou, max_det, max_cand,
+                                      L.ptr(g, C.c_int), L.ptr(out, C.c_float), L.ptr(n_out, C.c_int)))
+    return out, n_out
+
+
+def decode(logits, nc, strides, anchors, conf=0.25, max_cand=4096, mode="f32", nms=None):
+    """vc_decode_host: the Detect decode + candidate filter on explicit logits.  logits: three float32 arrays [b][ny][nx][round_up(3 * (nc + 5), 8)];
+    mode "f32" / "bf16" (decode_kernel) or "sparse" (head_compact_kernel + decode_sparse_kernel).  Returns a dict: cand_count, overflow ([b]),
+    box / conf / cls / idx ([b][max_cand], the first min(cand_count, max_cand) rows of a frame valid, in arbitrary order), in sparse mode
+    hc_lists (three arrays of gathered pixel indices); with nms = dict(iou=, max_det=, geoms=) the NMS runs on the same device buffers and
+    det ([b][max_det][6]) / det_count ([b], -1 = the frame's overflow flag) are added."""
+    lg = [L.f32(x) for x in logits]
+    b = lg[0].shape[0]
+    lcs = (3 * (nc + 5) + 7) // 8 * 8
+    d = L.DecodeDesc(b=b, nc=nc, mode=L.DECODE_MODE_ID[mode], conf=conf, max_cand=max_cand)
+    for i, x in enumerate(lg):
+        assert x.ndim == 4 and x.shape[0] == b and x.shape[3] == lcs, (x.shape, lcs)
+        d.ny[i], d.nx[i], d.stride[i] = x.shape[1], x.shape[2], float(strides[i])
+    d.anchors[:] = [float(v) for v in np.reshape(anchors, -1)]
+    lp = (C.POINTER(C.c_float) * 3)(*[L.ptr(x, C.c_float) for x in lg])
+    r = {"cand_count": np.zeros(b, np.int32), "overflow": np.zeros(b, np.int32), "box": np.zeros((b, max_cand, 4), np.float32),
+         "conf": np.zeros((b, max_cand), np.float32), "cls": np.zeros((b, max_cand), np.int32), "idx": np.zeros((b, max_cand), np.int32)}
+    hc_count, lists, hl = None, None, None
+    if mode == "sparse":
+        hc_count = np.zeros(3, np.int32)
+        lists = [np.zeros(x.shape[0] * x.shape[1] * x.shape[2], np.int32) for x in lg]
+        hl = (C.POINTER(C.c_int) * 3)(*[L.ptr(x, C.c_int) for x in lists])
+    iou, max_det, g, det, det_n = 0.0, 0, None, None, None
+    if nms is not None:
+        iou, max_det, g = nms.get("iou", 0.45), nms.get("max_det", 300), _geom_array(nms.get("geoms"), b)
+        det, det_n = np.zeros((b, max_det, 6), np.float32), np.zeros(b, np.int32)
+    L.check(L.lib().vc_decode_host(C.byref(d), lp, L.ptr(r["cand_count"], C.c_int), L.ptr(r["overflow"], C.c_int), L.ptr(r["box"], C.c_float),
+                                   L.ptr(r["conf"], C.c_float), L.ptr(r["cls"], C.c_int), L.ptr(r["idx"], C.c_int), L.ptr(hc_count, C.c_int), hl,
+                                   iou, max_det, L.ptr(g, C.c_int), L.ptr(det, C.c_float), L.ptr(det_n, C.c_int)))
+    if mode == "sparse":
+        r["hc_lists"] = [x[:n] for x, n in zip(lists, hc_count)]
+    if nms is not None:
+        r["det"], r["det_count"] = det, det_n
+    return r
