@@ -76,7 +76,7 @@ def test_conv2d(case, precision):
 @pytest.mark.parametrize("slots", [0, 8])
 @pytest.mark.parametrize("cfg", list(range(32)) + list(range(36, 50)) + [55] + list(range(60, 69)))     # (56 - 59, split-K: tests/test_gpu_round6.py; 64 - 68: paired workgroups)
 def test_conv2d_every_tile_config(cfg, slots, monkeypatch):
-    """Every entry of conv_igemm.hip's tile table (tile shape x K chunk x ring depth) on a padded 3x3 with a ragged
+    """Every entry of the implicit-GEMM and halo lists of conv_cfgs.h's tile table (tile shape x K chunk x ring depth) on a padded 3x3 with a ragged
     pixel tail, a ragged channel tail and a K extent shorter than the deepest ring, and on a strided 1x1."""
     s2halo = 44 <= cfg <= 49
     v2 = cfg == 55                                               # conv3x3_halo_v2_kernel (conv_halo_v2.hip)
@@ -122,6 +122,28 @@ def test_conv2d_every_tile_config(cfg, slots, monkeypatch):
                 np.testing.assert_allclose(y, ref, rtol=1e-4, atol=1e-4)
             else:
                 np.testing.assert_allclose(y, ref, rtol=2 ** -7, atol=2e-3)
+
+
+def test_conv2d_falls_back_when_the_chosen_family_refuses(monkeypatch):
+    """launch_conv's fall-back (conv_dispatch.hip): a tile configuration whose family does not take the shape -- conv3x3_halo_v2_kernel
+    (55) on a map wider than 64 columns -- is replaced by the heuristic's implicit-GEMM tile, here 3 (Cout > 64, five 128 x 128 tiles):
+    bit for bit the launch of configuration 3.  Under VC_CONV_STRICT the refusal reaches the caller instead."""
+    B, H, W, Ci, Co = 1, 9, 70, 64, 72
+    rng = np.random.default_rng(55)
+    x = rng.standard_normal((B, H, W, Ci), dtype=np.float32)
+    w = (rng.standard_normal((Co, Ci, 3, 3), dtype=np.float32) / np.sqrt(Ci * 9)).astype(np.float32)
+    b = rng.standard_normal(Co, dtype=np.float32) * 0.1
+    monkeypatch.delenv("VC_CONV_STRICT", raising=False)
+    monkeypatch.setenv("VC_CONV_CFG", "3")
+    y3 = E.conv2d(x, w, b, stride=1, pad=1, act=1, precision="bf16")
+    monkeypatch.setenv("VC_CONV_CFG", "55")
+    y55 = E.conv2d(x, w, b, stride=1, pad=1, act=1, precision="bf16")
+    np.testing.assert_array_equal(y55, y3)
+    np.testing.assert_allclose(y55, torch_conv(x, w, b, 1, 1, 1, None, 0, "bf16"), rtol=2 ** -7, atol=2e-3)
+    monkeypatch.setenv("VC_CONV_STRICT", "1")
+    from vehicle_counting_amd import _lib as L
+    with pytest.raises(L.VcError):
+        E.conv2d(x, w, b, stride=1, pad=1, act=1, precision="bf16")
 
 
 @pytest.mark.parametrize("slots", [0, 8])

@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "conv_launch.h"
 
 namespace vc {
 
@@ -281,15 +282,8 @@ int launch_c3_fused(const ConvP& p12, const ConvP& pm1, const ConvP& pm2, const 
     a.B = p12.B; a.H = p12.H; a.W = p12.W;
     a.tiles_x = (a.W + C3_TW - 1) / C3_TW; a.tiles_y = (a.H + C3_TH - 1) / C3_TH;
     const int ntiles = a.B * a.tiles_x * a.tiles_y;
-    static const int slots_hw = [] {
-        int per_cu = 2, dev = 0, cus = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c3_fused_kernel<false>, C3_NW * 64, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-        return per_cu * cus;
-    }();
-    static const int slots_reserve = getenv("VC_CONV_RESERVE") ? atoi(getenv("VC_CONV_RESERVE")) : 64;
-    const int grid = std::min(ntiles, std::max(256, slots_hw - slots_reserve / 2));   // persistent; two workgroups per CU: half the usual number of slots stays free
+    static const int slots_hw = resident_workgroups(c3_fused_kernel<false>, C3_NW * 64);
+    const int grid = std::min(ntiles, std::max(256, slots_hw - conv_slots_reserve() / 2));   // persistent; two workgroups per CU: half the usual number of slots stays free
     a.abl = p12.ablate;                                                              // diagnostics only (engine option "c3_ablate", tools/ff_ablate.py)
     if (a.abl) launch_timed(p12, c3_fused_kernel<true>, dim3(grid), dim3(C3_NW * 64), 0, s, a);
     else launch_timed(p12, c3_fused_kernel<false>, dim3(grid), dim3(C3_NW * 64), 0, s, a);

@@ -1,5 +1,5 @@
-// Device-side pieces shared by the convolution kernels (conv_igemm.hip, conv_halo_v2.hip): MFMA fragment types, the LDS swizzle,
-// the in-place MFMA statement and the epilogues (bias, activation, residual, bf16 / fp8 pack, concat-slice and split-destination stores).
+// Device-side pieces shared by the convolution kernels (conv_igemm.hip, conv_halo.hip, conv_halo_v2.hip, conv_halo_s2.hip, conv_pointwise.hip):
+// MFMA fragment types, the LDS swizzle, the XCD-aware tile order, the in-place MFMA statement and the epilogues (bias, activation, residual, bf16 / fp8 pack, concat-slice and split-destination stores).
 #pragma once
 #include "vc_common.h"
 
@@ -23,6 +23,16 @@ template <int KC>
 __device__ __forceinline__ int lds_slot(int row, int chunk) {
     if constexpr (KC == 4) return row * 4 + (chunk ^ ((0x78 >> (((row >> 2) & 3) * 2)) & 3));
     else return row * 8 + (chunk ^ (row & 7));
+}
+
+// XCD-aware tile order: the dispatcher places block b on XCD b % 8; each XCD gets a contiguous range of the launch's n tiles, so the tiles
+// that share an operand (the channel tiles of one pixel tile) hit the same private L2.  v: block index (virtual block of a persistent
+// workgroup: v = b + k * grid with a grid that is a multiple of 8, so all of them share b's XCD).
+// conv_igemm_kernel keeps the same expression written out (VC_TILE_OF, with n >> 3 and n & 7 held across its tile walk): through this
+// function the compiler orders its scalar code differently, and no kernel's code changes for the sake of one spelling.
+__device__ __forceinline__ int xcd_tile_of(int v, int n) {
+    const int q = n >> 3, r = n & 7, xcd = v & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (v >> 3);
 }
 
 __device__ __forceinline__ float act_apply(float v, int act, bool precise) {

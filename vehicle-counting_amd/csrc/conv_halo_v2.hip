@@ -1,5 +1,5 @@
 // Halo-staged 3x3 / stride 1 / pad 1 convolution (bf16), second form: row-aligned tiles, streamed weight fragments, look-ahead
-// fragment reads and a patch fetch spread over the K loop.  Tile configuration 55 of conv_igemm.hip's table.
+// fragment reads and a patch fetch spread over the K loop.  Tile configuration 55 of conv_cfgs.h.
 // Same rows of the reference as conv_igemm.hip: the 3x3 convolutions of ultralytics/yolov5 v6.0 `Bottleneck` blocks that
 // /root/reference/networks/yolo.py:70 executes and of the DeepSORT appearance net's BasicBlocks,
 // /root/reference/networks/deepsort/deep/model.py:5-98 (row B5).
@@ -25,6 +25,8 @@
 
 #include "vc_common.h"
 #include "conv_device.h"
+#include "conv_cfgs.h"
+#include "conv_launch.h"
 
 namespace vc {
 
@@ -48,11 +50,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_v2_kernel(const ConvP p, 
 
     const int nblk = gridDim.x;
     const int tiles_c = (p.Cout + BC - 1) / BC;
-    int tile;
-    {
-        const int b = blockIdx.x, q = nblk >> 3, r = nblk & 7, xcd = b & 7;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
+    const int tile = xcd_tile_of(blockIdx.x, nblk);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (p.dbg && tid == 0) p.dbg[(size_t)blockIdx.x * 8] = wall_clock64();
     const int uwave = __builtin_amdgcn_readfirstlane(wave);
@@ -254,8 +252,7 @@ static bool v2_applicable(const ConvP& p) {
 }
 
 int launch_halo_v2_cfg(const ConvP& p_in, int cfg, hipStream_t s) {
-    static const bool enabled = !(getenv("VC_CONV_HALO_V2") && atoi(getenv("VC_CONV_HALO_V2")) == 0);      // A/B switch
-    if (cfg != 55 || !enabled || !v2_applicable(p_in)) return VC_ERR_ARG;      // quietly: the autotuner skips it, launch_conv falls back
+    if (cfg != kCfgHaloV2 || !conv_switches().halo_v2 || !v2_applicable(p_in)) return VC_ERR_ARG;      // quietly: the autotuner skips it, launch_conv falls back
     ConvP p = p_in;
     const int R = v2_rows(p);
     const int rows = p.B * p.H;

@@ -377,8 +377,8 @@ int vc_engine_finalize(vc_engine* e) {
 }
 
 // Kernel-selection switches of a live engine (the parity tests compare a fused kernel with the launches it replaces on the same
-// engine).  Initial values come from the environment at vc_engine_create; the launch path itself never calls getenv (what is left in
-// the launchers are function-local statics initialised once per process: VC_CONV_RESERVE, VC_CONV_PERSIST and the A/B switches).
+// engine).  Initial values come from the environment at vc_engine_create; the launch path itself never calls getenv (what the conv
+// launchers consult is one struct read once per process, conv_launch.h::conv_switches: VC_CONV_RESERVE, VC_CONV_PERSIST and the A/B switches).
 int vc_engine_set_option(vc_engine* e, const char* name, int value) {
     VC_CHECK(e && name, VC_ERR_ARG, "null argument");
     const std::string n = name;

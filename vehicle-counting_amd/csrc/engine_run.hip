@@ -75,7 +75,7 @@ static int tuned_cfg(vc_engine* e, const ConvP& c, hipStream_t s) {
     }
     int best = -1;
     float best_ms = 1e30f;
-    static const bool stream_on = getenv("VC_CONV_STREAM") && atoi(getenv("VC_CONV_STREAM")) != 0;   // conv1x1_stream_kernel: wins alone, loses beside the ReID queue (conv_igemm.hip)
+    static const bool stream_on = getenv("VC_CONV_STREAM") && atoi(getenv("VC_CONV_STREAM")) != 0;   // conv1x1_stream_kernel: wins alone, loses beside the ReID queue (conv_pointwise.hip)
     for (int cfg = 0; cfg < conv_num_cfgs(); ++cfg) {
         if (conv_stream_cfg(cfg) && !stream_on) continue;
         if (launch_conv_cfg(c, cfg, s) != VC_OK) continue;          // warm-up (instruction cache, L2)

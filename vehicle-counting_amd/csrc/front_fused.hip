@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "conv_launch.h"
 
 namespace vc {
 
@@ -497,17 +498,10 @@ bool front_fused_resize_ok(const LetterboxGeom& g) {
 int launch_front_fused(const ConvP& p0, const ConvP& p1, const uint8_t* src8, const LetterboxGeom& g, hipStream_t s) {
     const int tiles_x = (p1.Wo + FF_TW - 1) / FF_TW, tiles_y = (p1.Ho + FF_TH - 1) / FF_TH;
     const int ntiles = p1.B * tiles_x * tiles_y;
-    static const int slots_reserve = getenv("VC_CONV_RESERVE") ? atoi(getenv("VC_CONV_RESERVE")) : 64;
-    static const int slots_hw = [] {
-        int per_cu = 1, dev = 0, cus = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, front_fused_kernel<true>, FF_NW * 64, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-        return per_cu * cus;
-    }();
+    static const int slots_hw = resident_workgroups(front_fused_kernel<true>, FF_NW * 64);
     // (tiles handed out by an atomic counter instead of the static stride -- late-starting workgroups, e.g. behind the tracker's, would not carry
     // a full share -- measured 7.09 against 7.13 ms per bench step over five alternating runs: inside the spread, not kept)
-    const int grid = std::min(ntiles, std::max(256, slots_hw - slots_reserve));   // persistent: every workgroup walks tiles; at one workgroup per CU nothing is held back (as in launch_one)
+    const int grid = std::min(ntiles, std::max(256, slots_hw - conv_slots_reserve()));   // persistent: every workgroup walks tiles; at one workgroup per CU nothing is held back (as in launch_one)
     const uint4* x = (const uint4*)p0.in;
     uint16_t* y = (uint16_t*)p1.out;
     static const bool dbg_on = getenv("VC_FF_DBG") != nullptr;

@@ -111,9 +111,9 @@ __global__ __launch_bounds__(256) void stem_direct_kernel(const uint4* __restric
 #pragma unroll
                 for (int pt = 0; pt < 4; ++pt) acc[ct][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][ct].h, xf[pt].h, acc[ct][pt], 0, 0, 0);
         }
-        // epilogue: bias + SiLU (same expression as conv_igemm.hip::act_apply, fast path).  A lane holds 4 consecutive channels of a
+        // epilogue: bias + SiLU (same expression as conv_device.h::act_apply, fast path).  A lane holds 4 consecutive channels of a
         // pixel; lane pairs (lane, lane ^ 16) swap halves across two pixel tiles so that each lane stores 8 channels (16 bytes) of
-        // ONE pixel -- half the store instructions (see conv_igemm.hip::conv_epilogue).
+        // ONE pixel -- half the store instructions (see conv_device.h::conv_epilogue).
         const bool odd = (kq & 1) != 0;
 #pragma unroll
         for (int pt = 0; pt < 4; pt += 2) {
@@ -167,7 +167,7 @@ static int launch_stem_impl(const ConvP& p, const uint8_t* src8, const Letterbox
     const int q_cs = q8 ? q8->cs : 0, q_co = q8 ? q8->co : 0;
     const int tiles_x = (p.Wo + STEM_TW - 1) / STEM_TW, tiles_y = (p.Ho + STEM_TH - 1) / STEM_TH;
     const int ntiles = p.B * tiles_x * tiles_y;
-    const int grid = std::min(ntiles, 256 * 3 - 64); // 3 workgroups per CU can be resident (VGPRs); 64 slots stay free for the tracker stream (conv_igemm.hip)
+    const int grid = std::min(ntiles, 256 * 3 - 64); // 3 workgroups per CU can be resident (VGPRs); 64 slots stay free for the tracker stream (conv_launch.h)
     const uint4* x = (const uint4*)p.in; const uint4* w = (const uint4*)p.w;
     uint16_t* y = (uint16_t*)p.out;
     const int kw8 = p.Kp / 8;

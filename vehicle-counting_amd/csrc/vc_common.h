@@ -129,7 +129,7 @@ __host__ __device__ inline void lin_coef(int d, int src, double scale, int& s0, 
     c1 = r1 < -32768 ? -32768 : (r1 > 32767 ? 32767 : r1);
 }
 
-// ---- convolution as implicit GEMM (conv_igemm.hip) ----------------------------------------------
+// ---- convolution (conv_dispatch.hip and the kernel families it dispatches to) --------------------
 enum Act : int { ACT_NONE = 0, ACT_SILU = 1, ACT_RELU = 2 };
 enum ResMode : int { RES_NONE = 0, RES_AFTER_ACT = 1, RES_BEFORE_ACT = 2 };
 
@@ -154,7 +154,7 @@ struct ConvP {
     float act_scale, inv_act_scale;
     int out_bf16;
     int M;               // B*Ho*Wo
-    int cfg;             // tile configuration index (conv_igemm.hip kCfg), -1 = heuristic
+    int cfg;             // tile configuration index (conv_cfgs.h), -1 = heuristic
     hipEvent_t ev_start, ev_stop;   // optional (in-flight profiling): receive the kernel's own start / stop timestamps (hipExtLaunchKernel)
     int ntiles;          // set by the launcher: output tiles of the chosen configuration (the grid may be smaller: persistent)
     // optional second destination: output channels >= split go to out2 (two 1x1 convs over the same input fused into
@@ -190,7 +190,12 @@ static inline void launch_timed(const ConvP& p, K kernel, dim3 grid, dim3 block,
 
 int launch_conv(const ConvP& p, hipStream_t s);
 int launch_conv_cfg(const ConvP& p, int cfg, hipStream_t s);     // no argument checks: for the autotuner
-int launch_halo_v2_cfg(const ConvP& p, int cfg, hipStream_t s);  // conv_halo_v2.hip: tile configuration 55
+// one launcher per kernel family (conv_cfgs.h: which ids are whose); VC_ERR_ARG without a message = the family does not take this shape
+int launch_igemm_cfg(const ConvP& p, int cfg, hipStream_t s);      // conv_igemm.hip
+int launch_halo_cfg(const ConvP& p, int cfg, hipStream_t s);       // conv_halo.hip
+int launch_halo_v2_cfg(const ConvP& p, int cfg, hipStream_t s);    // conv_halo_v2.hip
+int launch_halo_s2_cfg(const ConvP& p, int cfg, hipStream_t s);    // conv_halo_s2.hip
+int launch_pointwise_cfg(const ConvP& p, int cfg, hipStream_t s);  // conv_pointwise.hip
 bool s2halo_pw_applicable(const ConvP& p, const ConvP& q);      // conv3x3s2_halo_kernel<..., F2>: a 3x3 / s2 conv and the pointwise conv that alone reads it, one launch
 int launch_s2halo_pw(ConvP p, ConvP q, hipStream_t s);
 int conv_num_cfgs();
