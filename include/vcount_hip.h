@@ -58,7 +58,7 @@ typedef struct vc_engine vc_engine;
 typedef struct vc_engine_config {
     int device;            /* HIP device ordinal */
     int precision;         /* VC_PREC_* */
-    int yolo_variant;      /* 0 = yolov5s, 1 = yolov5m, 2 = yolov5l  (configs/configs.yaml: model_name) */
+    int yolo_variant;      /* 0 = yolov5s, 1 = yolov5m, 2 = yolov5l, 3 = yolov5x (bf16 / fp32 only)  (configs/configs.yaml: model_name) */
     int num_classes;       /* detector classes == tracker fan-out (modules/__init__.py:33) */
     int img_size;          /* AutoShape `size`, 640 in the reference (quirk Q8) */
     int max_batch;         /* frames per detect launch */
@@ -88,12 +88,13 @@ int vc_engine_param_count(const vc_engine* e, int net, int* n);
 int vc_engine_param_info(const vc_engine* e, int net, int index, char* name, int name_cap, int dims[4] /* O,I,kh,kw */);
 int vc_engine_set_param(vc_engine* e, int net, const char* name, const float* w_oihw, const float* bias);
 /* Detect anchors in pixels, 3 levels x 3 anchors x (w, h) = `model.24.anchors * stride` of an ultralytics checkpoint (custom
- * weights loaded by /root/reference/networks/yolo.py:58 may carry autoanchor values).  Default: the COCO set of yolov5{s,m,l}.yaml. */
+ * weights loaded by /root/reference/networks/yolo.py:58 may carry autoanchor values).  Default: the COCO set of yolov5{s,m,l,x}.yaml. */
 int vc_engine_set_anchors(vc_engine* e, const float* anchors18);
 int vc_engine_finalize(vc_engine* e); /* packs + uploads weights; detector/ReID calls are valid afterwards */
 /* Kernel-selection switches of a live engine (defaults come from the environment at vc_engine_create: VC_C3_FUSED, VC_BNECK_FUSED,
  * VC_FRONT_FUSED, VC_CROP_PER_PIXEL, VC_DOT_ARENA_MB).  Names: "c3_fused", "bneck_fused", "bneck_cv3" (0 / 1), "front_fused" (0 off, 1 stream path,
- * 2 always), "crop_per_pixel", "sparse_head", "reid_block_fused", "fuse_upsample", "sppf_sep", "fuse_s2_pw", "head_side" (0 / 1; head_side: the P3 / P4 Detect-head ops on their own stream
+ * 2 always), "crop_per_pixel", "sparse_head", "reid_block_fused", "fuse_upsample", "sppf_sep", "fuse_s2_pw", "stem_direct", "head_side" (0 / 1; stem_direct: 0 sends
+ * the bf16 detector stem through the implicit GEMM like any other layer, for every variant; head_side: the P3 / P4 Detect-head ops on their own stream
  * beside the neck layers that follow them), "dot_arena_mb" (largest appearance-table arena the tracker may allocate; 0 = compute the
  * appearance rows inside the walk).  The parity tests use it to compare a fused kernel with the launches it replaces.
  * "embed_kept_only" (default 1, environment VC_EMBED_KEPT_ONLY): crop and embed only the boxes DeepSort.update's own filter keeps

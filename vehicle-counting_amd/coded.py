@@ -149,6 +149,15 @@ def coded_yolo(variant="yolov5s", nc=80, seed=1702, clutter=0.3):
     sd = synth_yolo(variant, nc=nc, seed=seed, det_scale=1.0, obj_shift=-12.0)
     gd, gw = YOLO_VARIANTS[variant]
     ch = [_c8(c * gw) for c in (64, 128, 256, 512, 1024)]
+    if gd > 1.0:
+        # YOLOv5x: a third more Bottlenecks per C3 than YOLOv5l, the deepest variant synth_yolo's residual-branch gain was chosen for.
+        # Twelve shortcut sums in layer 6 lift the random channels' rms past 1, where SiLU stops shrinking them and every later conv
+        # (gain 2.6) multiplies it: rms 30 at the heads, whose random rows then swamp the plate's logits (2092 objectness logits above
+        # the threshold on a frame with 8 plates).  Residual branches scaled by 1 / gd^2 keep every layer's rms where s / m / l have it
+        # (0.2 .. 0.8).  gd <= 1: nothing changes.
+        for k in sd:
+            if ".m." in k and ".cv2.conv." in k and not k.startswith("model.24."):
+                sd[k] = (sd[k] * np.float32(1.0 / (gd * gd))).astype(np.float32)
 
     def wire(name, outs, carried):
         """outs: {out channel: [(in channel, tap row, tap col, weight), ...]}; `carried`: the input channels that hold plate bits.

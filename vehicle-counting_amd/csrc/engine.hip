@@ -165,8 +165,10 @@ int vc_engine_config_default(vc_engine_config* c) {
 
 int vc_engine_create(const vc_engine_config* cfg, vc_engine** out) {
     VC_CHECK(cfg && out, VC_ERR_ARG, "null argument");
-    VC_CHECK(cfg->yolo_variant >= 0 && cfg->yolo_variant <= 2, VC_ERR_ARG, "yolo_variant must be 0..2");
+    VC_CHECK(cfg->yolo_variant >= 0 && cfg->yolo_variant <= 3, VC_ERR_ARG, "yolo_variant must be 0..3");
     VC_CHECK(cfg->precision == VC_PREC_BF16 || cfg->precision == VC_PREC_F32 || cfg->precision == VC_PREC_FP8, VC_ERR_ARG, "bad precision");
+    // (no quantisation scales, no folded e4m3 stem copy and no fp8 parity figures exist for the 80 .. 1280-wide layers)
+    VC_CHECK(!(cfg->yolo_variant == 3 && cfg->precision == VC_PREC_FP8), VC_ERR_ARG, "the fp8 path is not built for yolov5x (yolo_variant 3): use bf16 or f32");
     VC_CHECK(cfg->max_candidates % 64 == 0 && cfg->max_candidates >= 64 && cfg->max_candidates <= 8192, VC_ERR_ARG,
              "max_candidates must be a multiple of 64 in [64, 8192]");
     VC_CHECK(cfg->max_batch >= 1 && cfg->num_classes >= 1 && cfg->max_det >= 1, VC_ERR_ARG, "bad sizes");
@@ -394,6 +396,7 @@ int vc_engine_set_option(vc_engine* e, const char* name, int value) {
     else if (n == "fuse_upsample") e->opt.fuse_upsample = value;
     else if (n == "sppf_sep") e->opt.sppf_sep = value;
     else if (n == "fuse_s2_pw") e->opt.fuse_s2_pw = value;
+    else if (n == "stem_direct") e->opt.stem_direct = value;
     else if (n == "ff_ablate") e->opt.ff_ablate = value;            // diagnostics (wrong results): tools/ff_ablate.py
     else if (n == "c3_ablate") e->opt.c3_ablate = value;
     else if (n == "dot_arena_mb") { VC_CHECK(value >= 0, VC_ERR_ARG, "dot_arena_mb must be >= 0"); e->dot_arena_max_floats = (size_t)value * 262144; }

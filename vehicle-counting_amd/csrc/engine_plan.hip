@@ -2,7 +2,7 @@
 // engine_run.hip executes the plans, engine.hip owns the engine and the C ABI.
 //
 // Graph sources restated here (independently of oracle/yolov5.py, they only meet at the parameter names):
-//   ultralytics/yolov5 v6.0 models/yolov5{s,m,l}.yaml + models/common.py (Conv, Bottleneck, C3, SPPF, Concat) +
+//   ultralytics/yolov5 v6.0 models/yolov5{s,m,l,x}.yaml + models/common.py (Conv, Bottleneck, C3, SPPF, Concat) +
 //   models/yolo.py (Detect), loaded by /root/reference/networks/yolo.py:58;
 //   /root/reference/networks/deepsort/deep/model.py:5-98 (BasicBlock, make_layers, Net(reid=True)).
 // Concat never copies: producers write straight into channel slices of the consumer's buffer.
@@ -71,7 +71,7 @@ struct PlanBuilder {
 };
 
 // ------------------------------------------------------------------------------------------------ YOLOv5 v6.0
-static const double kYoloMult[3][2] = {{0.33, 0.50}, {0.67, 0.75}, {1.0, 1.0}};   // depth, width (s, m, l)
+static const double kYoloMult[4][2] = {{0.33, 0.50}, {0.67, 0.75}, {1.0, 1.0}, {1.33, 1.25}};   // depth, width (s, m, l, x)
 const float kAnchors[3][6] = {{10, 13, 16, 30, 33, 23}, {30, 61, 62, 45, 59, 119}, {116, 90, 156, 198, 373, 326}};
 
 static void yolo_c3_params(Net& n, int idx, int cin, int cout, int reps) {

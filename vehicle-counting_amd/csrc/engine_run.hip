@@ -151,9 +151,10 @@ static int conv_select(ConvCtx& c, double fl, double by, ConvLaunch& L) {
 
     const bool front_ok = e->opt.front_fused > 0 && o1 && front_fused_applicable(cp, o1->conv);
     c.u8_src = e->stem_src && cp.in == e->ybuf["in"].ptr;
-    if (c.u8_src && !(stem_u8_applicable(cp, e->stem_geom) || (front_ok && front_fused_resize_ok(e->stem_geom)))) {
+    const bool stem_ok = e->opt.stem_direct != 0 && stem_direct_applicable(cp);
+    if (c.u8_src && !((stem_ok && stem_u8_applicable(cp, e->stem_geom)) || (front_ok && front_fused_resize_ok(e->stem_geom)))) {
         // run_detector_dev decided the fold-in from the engine's widths, this op list decides which kernel runs: should they ever
-        // disagree (a plan or layout change), the letterbox kernel runs now and the pass goes on from its tensor
+        // disagree (a plan or layout change, option "stem_direct" 0), the letterbox kernel runs now and the pass goes on from its tensor
         ProfScope ps(e, VC_PROF_DETECT_AUX, 0, 0, c.s);
         VC_TRY(launch_letterbox(e->stem_src, e->ybuf["in"].ptr, cp.B, e->stem_geom, e->aux_prec, c.s));
         e->stem_src = nullptr; e->in_stale = false;
@@ -197,7 +198,7 @@ static int conv_select(ConvCtx& c, double fl, double by, ConvLaunch& L) {
             x.e->l0_stale = true;                                     // layer 0 lived in LDS only
             return (int)VC_OK;
         };
-    } else if (stem_direct_applicable(cp)) {
+    } else if (stem_ok) {
         // YOLO stem, bf16: direct convolution (stem_direct.hip).  fp8 engine: the stem also writes the e4m3 copy the next layer reads
         // (TO_FP8 of its own output, folded in)
         L.cfg = 100;
@@ -413,7 +414,7 @@ int run_detector_dev(vc_engine* e, const uint8_t* d_frames, int B, int h, int w,
     // frames that need the resize (1280 x 720 -> 384 x 640, Q8): only front_fused_kernel evaluates it at patch-build time, so the fold-in
     // needs that kernel to be the one that runs (YOLOv5s widths, bf16 engine, option on) and the tile's source footprint to fit its staging
     const bool resize_ok = !same_scale && ((uintptr_t)d_frames & 3) == 0 && e->prec == PREC_BF16 && e->opt.front_fused > 0 && e->ch[0] == 32 && e->ch[1] == 64 && front_fused_resize_ok(g);
-    const bool fuse = e->aux_prec == PREC_BF16 && (same_scale || resize_ok) && e->ch[0] % 16 == 0 && e->ch[0] <= 64;
+    const bool fuse = e->aux_prec == PREC_BF16 && (same_scale || resize_ok) && e->ch[0] % 16 == 0 && e->ch[0] <= 80;
     e->stem_src = fuse ? d_frames : nullptr;
     e->stem_geom = g;
     e->in_stale = fuse;

@@ -159,13 +159,16 @@ __global__ __launch_bounds__(256) void stem_direct_kernel(const uint4* __restric
 bool stem_direct_applicable(const ConvP& p) {
     return p.prec == PREC_BF16 && p.kh == 6 && p.kw == 3 && p.sh == 2 && p.sw == 1 && p.ph == 2 && p.pw == 1 && p.Cin == 8 && p.in_cs == 8 &&
            p.in_co == 0 && p.act == ACT_SILU && p.res_mode == RES_NONE && !p.out_f32 && p.split == 0 && p.Cout % 16 == 0 && p.Cout >= 16 &&
-           p.Cout <= 64 && p.Kp >= 160 && p.out_cs % 8 == 0 && p.out_co % 8 == 0;
+           p.Cout <= 80 && p.Kp >= 160 && p.out_cs % 8 == 0 && p.out_co % 8 == 0;
 }
+
+int launch_stem_direct_wide(const ConvP& p, const uint8_t* src8, const LetterboxGeom& g, int tiles_x, int tiles_y, hipStream_t s);   // stem_direct_wide.hip: Cout = 80
 
 static int launch_stem_impl(const ConvP& p, const uint8_t* src8, const LetterboxGeom& g, hipStream_t s, const View* q8 = nullptr, float q_inv_scale = 1.0f) {
     uint8_t* y8 = q8 ? (uint8_t*)q8->ptr : nullptr;
     const int q_cs = q8 ? q8->cs : 0, q_co = q8 ? q8->co : 0;
     const int tiles_x = (p.Wo + STEM_TW - 1) / STEM_TW, tiles_y = (p.Ho + STEM_TH - 1) / STEM_TH;
+    if (p.Cout == 80) return q8 ? VC_ERR_ARG : launch_stem_direct_wide(p, src8, g, tiles_x, tiles_y, s);     // (no fp8 engine has an 80-channel stem)
     const int ntiles = p.B * tiles_x * tiles_y;
     const int grid = std::min(ntiles, 256 * 3 - 64); // 3 workgroups per CU can be resident (VGPRs); 64 slots stay free for the tracker stream (conv_launch.h)
     const uint4* x = (const uint4*)p.in; const uint4* w = (const uint4*)p.w;

@@ -8,7 +8,7 @@ import numpy as np
 from . import _lib as L
 from .weights import fold_reid
 
-YOLO_VARIANT_ID = {"yolov5s": 0, "yolov5m": 1, "yolov5l": 2}
+YOLO_VARIANT_ID = {"yolov5s": 0, "yolov5m": 1, "yolov5l": 2, "yolov5x": 3}
 
 
 class Engine:
@@ -77,7 +77,7 @@ class Engine:
         L.check(L.lib().vc_engine_sync(self._h))
 
     def set_option(self, name, value):
-        """Kernel-selection switch of the live engine ("c3_fused", "bneck_fused", "bneck_cv3", "front_fused", "sparse_head", "reid_block_fused", "crop_per_pixel", "dot_arena_mb"; diagnostics: "ff_ablate", "c3_ablate"), or "embed_kept_only" (1: crop and embed only the boxes DeepSort.update's own filter keeps; 0: every box)."""
+        """Kernel-selection switch of the live engine ("c3_fused", "bneck_fused", "bneck_cv3", "front_fused", "sparse_head", "reid_block_fused", "stem_direct", "crop_per_pixel", "dot_arena_mb"; diagnostics: "ff_ablate", "c3_ablate"), or "embed_kept_only" (1: crop and embed only the boxes DeepSort.update's own filter keeps; 0: every box)."""
         L.check(L.lib().vc_engine_set_option(self._h, name.encode(), int(value)))
 
     def stream_reset(self):

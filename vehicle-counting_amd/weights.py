@@ -19,7 +19,7 @@ import math
 
 import numpy as np
 
-YOLO_VARIANTS = {"yolov5s": (0.33, 0.50), "yolov5m": (0.67, 0.75), "yolov5l": (1.0, 1.0)}
+YOLO_VARIANTS = {"yolov5s": (0.33, 0.50), "yolov5m": (0.67, 0.75), "yolov5l": (1.0, 1.0), "yolov5x": (1.33, 1.25)}
 YOLO_BN_EPS = 1e-3      # ultralytics initialises BatchNorm2d eps=1e-3
 REID_BN_EPS = 1e-5
 
