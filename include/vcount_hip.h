@@ -506,6 +506,31 @@ typedef struct vc_decode_desc {
 int vc_decode_host(const vc_decode_desc* d, const float* const* logits, int* cand_count, int* overflow, float* cand_box, float* cand_conf,
                    int* cand_cls, int* cand_idx, int* hc_count, int* const* hc_list, float iou, int max_det, const int* geom4, float* out6,
                    int* out_n);
+/* The pool, resample, layout and cast kernels between the convolutions, each through the launch function the engine calls, on host
+ * float arrays.  Values are converted to `precision` on the way in and back to float on the way out; a caller that passes values the
+ * element type represents gets the kernel's own bits.  A channel slice is (cs, co): channel c of a pixel at cs * pixel + co + c.
+ * Everything a kernel writes lies between guard blocks: a write outside the buffer is VC_ERR_HIP, not a plausible result. */
+#define VC_SPPF_RAN_SEP 1    /* sppf_pool_sep_kernel: the register form */
+#define VC_SPPF_RAN_WIDE 2   /* sppf_pool_wide_kernel: the plane in LDS */
+#define VC_SPPF_RAN_PLAIN 3  /* sppf_pool_kernel: every output reads its 13 x 13 window (f32 / bf16) */
+#define VC_SPPF_RAN_FP8 4    /* sppf_pool_fp8_kernel: the same for e4m3 planes */
+/* buf [b][h][w][cs], in and out: SPPF of channels [co, co + c) into [co + c, co + 4c); form as the engine's sppf_sep option.
+ * ran_kernel / ran_ws (nullable): the kernel that ran (VC_SPPF_RAN_*) and its slice width in 32-bit words. */
+int vc_sppf_pool_host(float* buf, int b, int h, int w, int cs, int co, int c, int precision, int form, int* ran_kernel, int* ran_ws);
+/* src [b][h][w][c] -> channels [co, co + c) of dst [b][2h][2w][cs] (in and out); f32, bf16, fp8 */
+int vc_upsample2x_host(const float* src, int b, int h, int w, int c, float* dst, int cs, int co, int precision);
+/* MaxPool2d(3, 2, 1): src [b][h][w][c] -> channels [co, co + c) of dst [b][(h - 1) / 2 + 1][(w - 1) / 2 + 1][cs] (in and out); f32, bf16 */
+int vc_maxpool3s2_host(const float* src, int b, int h, int w, int c, float* dst, int cs, int co, int precision);
+/* AvgPool over the whole h x w map + L2 normalisation: x [k][h][w][512] -> out [k][512] (always f32); f32, bf16 */
+int vc_avgpool_l2norm_host(const float* x, int k, int h, int w, int precision, float* out);
+/* x [k][c][h][w] -> out [k][h][w][cpad], channels >= c zero; cpad must be the ReID input buffer's (4 in f32, 8 in bf16) */
+int vc_nchw_to_nhwc_pad_host(const float* x, int k, int c, int h, int w, int cpad, int precision, float* out);
+/* bf16 -> e4m3fn of value x inv_scale: channels [src_co, src_co + c) of src [npix][src_cs] (floats, rounded to bf16) into bytes
+ * [dst_co, dst_co + c) of dst [npix][dst_cs] (in and out) */
+int vc_bf16_to_fp8_host(const float* src, int npix, int c, int src_cs, int src_co, float inv_scale, uint8_t* dst, int dst_cs, int dst_co);
+/* The ReID stem in one kernel (bf16): conv3x3(3 -> 64) + bias + ReLU + MaxPool2d(3, 2, 1).  crops [k][50][50][3], w [64][3][3][3],
+ * bias [64] -> out [k][25][25][64] */
+int vc_reid_stem_pool_host(const float* crops, int k, const float* w, const float* bias, float* out);
 
 #ifdef __cplusplus
 }

@@ -188,7 +188,15 @@ SIGNATURES = {
     "vc_nms_host": [_pf, _pf, _pi, _i, _f, _i, _i, _pf, _pi],
     "vc_nms_batch_host": [_pf, _pf, _pi, _pi, _i, _f, _i, _i, _pi, _pf, _pi],
     "vc_decode_host": [_P(DecodeDesc), _P(_pf), _pi, _pi, _pf, _pf, _pi, _pi, _pi, _P(_pi), _f, _i, _pi, _pf, _pi],
+    "vc_sppf_pool_host": [_pf, _i, _i, _i, _i, _i, _i, _i, _i, _pi, _pi],
+    "vc_upsample2x_host": [_pf, _i, _i, _i, _i, _pf, _i, _i, _i],
+    "vc_maxpool3s2_host": [_pf, _i, _i, _i, _i, _pf, _i, _i, _i],
+    "vc_avgpool_l2norm_host": [_pf, _i, _i, _i, _i, _pf],
+    "vc_nchw_to_nhwc_pad_host": [_pf, _i, _i, _i, _i, _i, _i, _pf],
+    "vc_bf16_to_fp8_host": [_pf, _i, _i, _i, _i, _f, _pu8, _i, _i],
+    "vc_reid_stem_pool_host": [_pf, _i, _pf, _pf, _pf],
 }
+SPPF_RAN = {1: "sep", 2: "wide", 3: "plain", 4: "fp8"}       # VC_SPPF_RAN_*
 _RESTYPE = {"vc_last_error": C.c_char_p}
 
 _lib = None

@@ -7,6 +7,7 @@
 // (/root/reference/networks/deepsort/deep_sort.py:89-95,119-129 and deep/feature_extractor.py:26-39), B5 pools
 // (/root/reference/networks/deepsort/deep/model.py:58,70,93).
 #include "kernels.h"
+#include "sppf_keys.h"
 
 #pragma clang fp contract(off)   // restated arithmetic must round like the reference's separate mul/add
 
@@ -295,109 +296,16 @@ __global__ __launch_bounds__(256) void sppf_pool_kernel(View cat, int C) {
     }
 }
 
-// LDS version: one workgroup per (frame, channel vector) keeps the whole H x W plane in LDS and applies the three chained
-// 5x5 max-pools as separable row / column passes (6 passes over 400 positions at 20x20 instead of 169 global reads per output).
-template <bool F32>
-__global__ __launch_bounds__(256) void sppf_pool_lds_kernel(View cat, int C) {
-    using V = Vec<F32>;
-    constexpr int ES = F32 ? 4 : 2;
-    extern __shared__ __attribute__((aligned(16))) float sm[];          // two planes of [H*W][N] floats
-    const int cv = C / V::N;
-    const int b = blockIdx.x / cv, c = (blockIdx.x % cv) * V::N;
-    const int H = cat.H, W = cat.W, n = H * W;
-    float* P = sm;
-    float* T = sm + (size_t)n * V::N;
-    char* base = (char*)cat.ptr + (((size_t)b * n) * cat.cs + cat.co + c) * ES;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const V v = V::load(base + (size_t)i * cat.cs * ES);
-#pragma unroll
-        for (int j = 0; j < V::N; ++j) P[i * V::N + j] = v.v[j];
-    }
-    __syncthreads();
-    for (int round = 1; round <= 3; ++round) {
-        for (int i = threadIdx.x; i < n; i += blockDim.x) {              // row pass
-            const int y = i / W, x = i - y * W;
-            const int x0 = max(x - 2, 0), x1 = min(x + 2, W - 1);
-#pragma unroll
-            for (int j = 0; j < V::N; ++j) {
-                float m = -INFINITY;
-                for (int xx = x0; xx <= x1; ++xx) m = fmaxf(m, P[(y * W + xx) * V::N + j]);
-                T[i * V::N + j] = m;
-            }
-        }
-        __syncthreads();
-        for (int i = threadIdx.x; i < n; i += blockDim.x) {              // column pass + store of this round's slice
-            const int y = i / W, x = i - y * W;
-            const int y0 = max(y - 2, 0), y1 = min(y + 2, H - 1);
-            V o;
-#pragma unroll
-            for (int j = 0; j < V::N; ++j) {
-                float m = -INFINITY;
-                for (int yy = y0; yy <= y1; ++yy) m = fmaxf(m, T[(yy * W + x) * V::N + j]);
-                o.v[j] = m;
-            }
-            o.store(base + ((size_t)i * cat.cs + (size_t)round * C) * ES);
-#pragma unroll
-            for (int j = 0; j < V::N; ++j) P[i * V::N + j] = o.v[j];      // own position only: no hazard with other threads' T reads
-        }
-        __syncthreads();
-    }
-}
-
-// Wide LDS version (the one that runs at 20x20): one workgroup per (frame, 32 words of channels = 64 bf16 / 32 fp32 channels).
-// A lane owns one 4-byte word of a position, so a position's slice is one coalesced 128-byte read/write and every LDS access
+// Wide LDS version (option sppf_sep 0, and planes with a side above 40): one workgroup per (frame, WS words of channels; 16 words =
+// 32 bf16 / 16 fp32 channels).  A lane owns one 4-byte word of a position, so a position's slice is one coalesced read/write and every LDS access
 // of a wave is 64 consecutive words; the three chained 5x5 max-pools are separable row / column passes on the LDS plane.
 // max() of bf16 values is exact on the two halves of a word (no rounding anywhere).
-// Order-preserving keys: a float's bits compare like unsigned integers once negative values have all bits flipped and
+// Order-preserving keys (sppf_keys.h): a float's bits compare like unsigned integers once negative values have all bits flipped and
 // non-negative ones the sign bit set.  bf16 pairs are keyed per half, so the 30 max() of a position are one v_pk_max_u16
 // (v_max_u32 for fp32) each instead of an unpack / two fmaxf / repack; keys are turned back into values on the way out.
 // (No NaNs reach this kernel: its input is the SiLU output of a finite convolution.)
 // fp8 (e4m3fn) planes: max-pooling only selects, so it runs on an order-preserving integer key of the byte (sign-magnitude ->
 // biased unsigned) and stores the winner's byte; 4 channels per thread.
-__device__ __forceinline__ unsigned int fp8_key4(unsigned int v) {           // per byte: b ^ (b & 0x80 ? 0xff : 0x80)
-    const unsigned int neg = (v >> 7) & 0x01010101u;
-    return v ^ (0x80808080u | (neg * 0x7fu));
-}
-__device__ __forceinline__ unsigned int fp8_unkey4(unsigned int k) {        // inverse: key >= 0x80 was a positive byte (k ^ 0x80), else negative (k ^ 0xff)
-    const unsigned int pos = (k >> 7) & 0x01010101u;
-    return k ^ (0xffffffffu ^ (pos * 0x7fu));
-}
-__device__ __forceinline__ unsigned int umax4(unsigned int a, unsigned int b) {
-    unsigned int r = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { const unsigned int x = (a >> (8 * i)) & 0xff, y = (b >> (8 * i)) & 0xff; r |= (x > y ? x : y) << (8 * i); }
-    return r;
-}
-template <bool F32>
-__device__ __forceinline__ uint32_t to_key(uint32_t v) {
-    if (F32) return v ^ (((int32_t)v >> 31) | 0x80000000u);
-    const uint32_t neg = (v >> 15) & 0x00010001u;                     // sign of each half
-    return v ^ ((neg * 0x7fffu) | 0x80008000u);                        // negative: flip all 16 bits, else flip the sign bit
-}
-template <bool F32>
-__device__ __forceinline__ uint32_t from_key(uint32_t k) {
-    if (F32) return k ^ ((~((int32_t)k >> 31)) | 0x80000000u);
-    const uint32_t pos = (k >> 15) & 0x00010001u;                     // key has its top bit set <=> the value was non-negative
-    return k ^ (((pos ^ 0x00010001u) * 0x7fffu) | 0x80008000u);
-}
-template <bool F32>
-__device__ __forceinline__ uint32_t kmax(uint32_t a, uint32_t b) {
-    if (F32) return a > b ? a : b;
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
-}
-
-// element type of the plane: 0 = fp32, 1 = bf16 pairs, 2 = fp8 (e4m3fn) quads
-template <int ET> __device__ __forceinline__ uint32_t word_key(uint32_t v) { return ET == 2 ? fp8_key4(v) : to_key<ET == 0>(v); }
-template <int ET> __device__ __forceinline__ uint32_t word_unkey(uint32_t k) { return ET == 2 ? fp8_unkey4(k) : from_key<ET == 0>(k); }
-template <int ET> __device__ __forceinline__ uint32_t word_max(uint32_t a, uint32_t b) {
-    if (ET == 2) {
-        typedef unsigned char u8x4 __attribute__((ext_vector_type(4)));
-        return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u8x4, a), __builtin_bit_cast(u8x4, b)));
-    }
-    return kmax<ET == 0>(a, b);
-}
-
 template <int ET, int WS>          // WS 32-bit words of a pixel per workgroup (32: 128-byte slices ... 4: 16-byte slices)
 __global__ __launch_bounds__(1024) void sppf_pool_wide_kernel(View cat, int C) {
     constexpr int ES = ET == 0 ? 4 : (ET == 1 ? 2 : 1);
@@ -554,8 +462,9 @@ __global__ __launch_bounds__(256) void sppf_pool_fp8_kernel(View cat, int C) {
     }
 }
 
-int launch_sppf_pool(const View& cat, int C, int prec, int form, hipStream_t s) {
+int launch_sppf_pool(const View& cat, int C, int prec, int form, hipStream_t s, SppfRan* ran) {
     const int es = prec == PREC_F32 ? 4 : (prec == PREC_FP8 ? 1 : 2);
+    if (ran) *ran = SppfRan{0, 0};
     VC_CHECK(C % 4 == 0 && cat.cs % 4 == 0 && cat.co % 4 == 0, VC_ERR_ARG, "sppf: channel alignment");
     // form 1 (the engine's default): the register form wherever the plane is at most 40 x 40 -- every SPPF input of 640^2 ... 1280^2 frames
     const int maxd = std::max(cat.H, cat.W);
@@ -576,18 +485,19 @@ int launch_sppf_pool(const View& cat, int C, int prec, int form, hipStream_t s) 
             if (prec == PREC_F32) VC_SPPF_SEP(0) else if (prec == PREC_FP8) VC_SPPF_SEP(2) else VC_SPPF_SEP(1)
 #undef VC_SPPF_SEP
             VC_HIP(hipGetLastError());
+            if (ran) *ran = SppfRan{VC_SPPF_RAN_SEP, ws};
             return VC_OK;
         }
     }
     // The wide LDS kernel with the widest slice that fits: 64-byte (or narrower) slices when two such workgroups fit a CU's LDS
     // (every workgroup of a 128-frame batch is then resident at once -- the kernel is six LDS passes and seven barriers long, i.e.
-    // latency-bound), wider ones otherwise.
+    // latency-bound); a plane whose 16-byte slice alone needs more than that takes a CU's LDS for itself.  (A slice wider than 64 bytes
+    // never wins: where it fits in 150 KB, the 64-byte slice of the same channel count fits in 76 KB.)
     const size_t plane = (size_t)2 * cat.H * cat.W * 4;                  // bytes per word of slice width
     int ws = 0;
     for (int cand : {16, 8, 4})
         if (!ws && plane * cand <= 76 * 1024 && C % (cand * 4 / es) == 0) ws = cand;
-    for (int cand : {32, 16, 8, 4})
-        if (!ws && plane * cand <= 150 * 1024 && C % (cand * 4 / es) == 0) ws = cand;
+    if (!ws && plane * 4 <= 150 * 1024 && C % (16 / es) == 0) ws = 4;
     if (ws && (cat.cs * es) % 4 == 0 && (cat.co * es) % 4 == 0) {
         const int cw = ws * 4 / es;
         const size_t lds_wide = plane * ws;
@@ -598,33 +508,30 @@ int launch_sppf_pool(const View& cat, int C, int prec, int form, hipStream_t s) 
             return (int)VC_OK;
         };
         int rc = VC_ERR_ARG;
-#define VC_SPPF_GO(ET) rc = ws == 32 ? go(sppf_pool_wide_kernel<ET, 32>) : ws == 16 ? go(sppf_pool_wide_kernel<ET, 16>) : ws == 8 ? go(sppf_pool_wide_kernel<ET, 8>) : go(sppf_pool_wide_kernel<ET, 4>)
+#define VC_SPPF_GO(ET) rc = ws == 16 ? go(sppf_pool_wide_kernel<ET, 16>) : ws == 8 ? go(sppf_pool_wide_kernel<ET, 8>) : go(sppf_pool_wide_kernel<ET, 4>)
         if (prec == PREC_F32) { VC_SPPF_GO(0); } else if (prec == PREC_FP8) { VC_SPPF_GO(2); } else { VC_SPPF_GO(1); }
 #undef VC_SPPF_GO
         VC_CHECK(rc == VC_OK, VC_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for the SPPF pool kernel");
         VC_HIP(hipGetLastError());
+        if (ran) *ran = SppfRan{VC_SPPF_RAN_WIDE, ws};
         return VC_OK;
     }
+    // What is left: planes whose 16-byte slice does not fit the LDS twice (more than 4800 positions), and channel counts that are no
+    // multiple of the narrowest slice (fp8 with C % 16 != 0).  Every output reads its own 13 x 13 window.
     if (prec == PREC_FP8) {
         const long total = (long)cat.B * cat.H * cat.W * (C / 4);
         hipLaunchKernelGGL(sppf_pool_fp8_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, cat, C);
         VC_HIP(hipGetLastError());
+        if (ran) *ran = SppfRan{VC_SPPF_RAN_FP8, 1};
         return VC_OK;
     }
     const int n = prec == PREC_F32 ? 4 : 8;
     VC_CHECK(C % n == 0 && cat.cs % n == 0 && cat.co % n == 0, VC_ERR_ARG, "sppf: channel alignment");
-    const size_t lds = (size_t)2 * cat.H * cat.W * n * sizeof(float);
-    if (lds <= 150 * 1024) {
-        const int blocks = cat.B * (C / n);
-        if (prec == PREC_F32) hipLaunchKernelGGL(sppf_pool_lds_kernel<true>, dim3(blocks), dim3(256), lds, s, cat, C);
-        else hipLaunchKernelGGL(sppf_pool_lds_kernel<false>, dim3(blocks), dim3(256), lds, s, cat, C);
-        VC_HIP(hipGetLastError());
-        return VC_OK;
-    }
     const long total = (long)cat.B * cat.H * cat.W * (C / n);
     if (prec == PREC_F32) hipLaunchKernelGGL(sppf_pool_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, s, cat, C);
     else hipLaunchKernelGGL(sppf_pool_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, s, cat, C);
     VC_HIP(hipGetLastError());
+    if (ran) *ran = SppfRan{VC_SPPF_RAN_PLAIN, 4};
     return VC_OK;
 }
 
@@ -886,7 +793,8 @@ __global__ __launch_bounds__(256) void maxpool3s2_kernel(View src, View dst) {
 
 int launch_maxpool3s2(const View& src, const View& dst, int prec, hipStream_t s) {
     const int n = prec == PREC_F32 ? 4 : 8;
-    VC_CHECK(src.C % n == 0 && src.cs % n == 0 && dst.cs % n == 0, VC_ERR_ARG, "maxpool: alignment");
+    VC_CHECK(src.C % n == 0 && src.cs % n == 0 && src.co % n == 0 && dst.cs % n == 0 && dst.co % n == 0, VC_ERR_ARG, "maxpool: alignment");
+    VC_CHECK(dst.H == (src.H - 1) / 2 + 1 && dst.W == (src.W - 1) / 2 + 1 && dst.B == src.B, VC_ERR_ARG, "maxpool: shape");
     const long total = (long)dst.B * dst.H * dst.W * (src.C / n);
     if (total <= 0) return VC_OK;
     if (prec == PREC_F32) hipLaunchKernelGGL(maxpool3s2_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, s, src, dst);

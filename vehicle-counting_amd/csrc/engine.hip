@@ -810,6 +810,158 @@ int vc_letterbox_host(const uint8_t* rgb, int h, int w, int net_h, int net_w, in
     return VC_OK;
 }
 
+// ---- the pool, resample, layout and cast kernels on host arrays (include/vcount_hip.h) ------------------------------------------------
+// n floats -> elements of `prec` (exact for values the type represents) and back
+static std::vector<uint8_t> to_elems(const float* src, size_t n, int prec) {
+    const int es = elem_size(prec);
+    std::vector<uint8_t> buf(n * es);
+    for (size_t i = 0; i < n; ++i) {
+        if (es == 4) ((float*)buf.data())[i] = src[i];
+        else if (es == 2) ((uint16_t*)buf.data())[i] = f32_to_bf16(src[i]);
+        else buf[i] = f32_to_e4m3(src[i]);
+    }
+    return buf;
+}
+static void from_elems(const std::vector<uint8_t>& buf, size_t n, int prec, float* dst) {
+    const int es = elem_size(prec);
+    for (size_t i = 0; i < n; ++i)
+        dst[i] = es == 4 ? ((const float*)buf.data())[i] : es == 2 ? bf16_to_f32(((const uint16_t*)buf.data())[i]) : e4m3_to_f32(buf[i]);
+}
+static int upload_elems(DevScratch& mem, const float* src, size_t n, int prec, void** dst) {
+    const std::vector<uint8_t> buf = to_elems(src, n, prec);
+    VC_TRY(mem.alloc(dst, buf.size()));
+    VC_HIP(hipMemcpy(*dst, buf.data(), buf.size(), hipMemcpyHostToDevice));
+    return VC_OK;
+}
+// the caller's float array as the guarded device buffer a kernel writes into, and back
+static int guarded_elems(DevScratch& mem, GuardedOut& g, const float* init, size_t n, int prec) {
+    const std::vector<uint8_t> buf = to_elems(init, n, prec);
+    return g.alloc(mem, buf.size(), buf.data());
+}
+static int read_elems(const GuardedOut& g, size_t n, int prec, float* dst, const char* kernel) {
+    std::vector<uint8_t> buf(g.bytes);
+    VC_TRY(g.read_back(buf.data(), kernel));
+    from_elems(buf, n, prec, dst);
+    return VC_OK;
+}
+static bool prec_known(int prec, bool fp8_too) { return prec == PREC_F32 || prec == PREC_BF16 || (fp8_too && prec == PREC_FP8); }
+
+int vc_sppf_pool_host(float* buf, int b, int h, int w, int cs, int co, int c, int precision, int form, int* ran_kernel, int* ran_ws) {
+    VC_CHECK(buf && b >= 1 && h >= 1 && w >= 1 && c >= 1 && co >= 0 && cs >= co + 4 * c, VC_ERR_ARG, "sppf: bad shape");
+    VC_CHECK(prec_known(precision, true) && (form == 0 || form == 1), VC_ERR_ARG, "sppf: bad precision or form");
+    if (ran_kernel) *ran_kernel = 0;
+    if (ran_ws) *ran_ws = 0;
+    DevScratch mem;
+    GuardedOut dd;
+    const size_t n = (size_t)b * h * w * cs;
+    VC_TRY(guarded_elems(mem, dd, buf, n, precision));
+    const View cat{dd.out(), b, h, w, c, cs, co, elem_size(precision)};
+    SppfRan ran{0, 0};
+    VC_TRY(launch_sppf_pool(cat, c, precision, form, nullptr, &ran));
+    VC_TRY(read_elems(dd, n, precision, buf, "the SPPF pool kernel"));
+    if (ran_kernel) *ran_kernel = ran.kernel;
+    if (ran_ws) *ran_ws = ran.ws;
+    return VC_OK;
+}
+
+int vc_upsample2x_host(const float* src, int b, int h, int w, int c, float* dst, int cs, int co, int precision) {
+    VC_CHECK(src && dst && b >= 1 && h >= 1 && w >= 1 && c >= 1 && co >= 0 && cs >= co + c, VC_ERR_ARG, "upsample: bad shape");
+    VC_CHECK(prec_known(precision, true), VC_ERR_ARG, "upsample: bad precision");
+    DevScratch mem;
+    GuardedOut dd;
+    void* ds = nullptr;
+    const size_t n = (size_t)b * 2 * h * 2 * w * cs;
+    VC_TRY(upload_elems(mem, src, (size_t)b * h * w * c, precision, &ds));
+    VC_TRY(guarded_elems(mem, dd, dst, n, precision));
+    const View a{ds, b, h, w, c, c, 0, elem_size(precision)}, d{dd.out(), b, 2 * h, 2 * w, c, cs, co, elem_size(precision)};
+    VC_TRY(launch_upsample2x(a, d, precision, nullptr));
+    return read_elems(dd, n, precision, dst, "upsample2x_kernel");
+}
+
+int vc_maxpool3s2_host(const float* src, int b, int h, int w, int c, float* dst, int cs, int co, int precision) {
+    VC_CHECK(src && dst && b >= 1 && h >= 1 && w >= 1 && c >= 1 && co >= 0 && cs >= co + c, VC_ERR_ARG, "maxpool: bad shape");
+    VC_CHECK(prec_known(precision, false), VC_ERR_ARG, "maxpool: precision must be VC_PREC_BF16 or VC_PREC_F32");
+    DevScratch mem;
+    GuardedOut dd;
+    void* ds = nullptr;
+    const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
+    const size_t n = (size_t)b * ho * wo * cs;
+    VC_TRY(upload_elems(mem, src, (size_t)b * h * w * c, precision, &ds));
+    VC_TRY(guarded_elems(mem, dd, dst, n, precision));
+    const View a{ds, b, h, w, c, c, 0, elem_size(precision)}, d{dd.out(), b, ho, wo, c, cs, co, elem_size(precision)};
+    VC_TRY(launch_maxpool3s2(a, d, precision, nullptr));
+    return read_elems(dd, n, precision, dst, "maxpool3s2_kernel");
+}
+
+int vc_avgpool_l2norm_host(const float* x, int k, int h, int w, int precision, float* out) {
+    VC_CHECK(x && out && k >= 1 && h >= 1 && w >= 1, VC_ERR_ARG, "avgpool: bad shape");
+    VC_CHECK(prec_known(precision, false), VC_ERR_ARG, "avgpool: precision must be VC_PREC_BF16 or VC_PREC_F32");
+    DevScratch mem;
+    GuardedOut dd;
+    void* ds = nullptr;
+    VC_TRY(upload_elems(mem, x, (size_t)k * h * w * VC_FEAT_DIM, precision, &ds));
+    VC_TRY(dd.alloc(mem, (size_t)k * VC_FEAT_DIM * sizeof(float)));
+    const View a{ds, k, h, w, VC_FEAT_DIM, VC_FEAT_DIM, 0, elem_size(precision)};
+    VC_TRY(launch_avgpool_l2norm(a, (float*)dd.out(), precision, nullptr));
+    return dd.read_back((uint8_t*)out, "avgpool_l2norm_kernel");
+}
+
+int vc_nchw_to_nhwc_pad_host(const float* x, int k, int c, int h, int w, int cpad, int precision, float* out) {
+    VC_CHECK(x && out && k >= 1 && c >= 1 && h >= 1 && w >= 1, VC_ERR_ARG, "layout: bad shape");
+    VC_CHECK(prec_known(precision, false), VC_ERR_ARG, "layout: precision must be VC_PREC_BF16 or VC_PREC_F32");
+    VC_CHECK(cpad == reid_cpad(precision) && c <= cpad, VC_ERR_ARG, "layout: cpad must be %d at this precision", reid_cpad(precision));
+    DevScratch mem;
+    GuardedOut dd;
+    void* ds = nullptr;
+    const size_t n = (size_t)k * h * w * cpad;
+    VC_TRY(upload_elems(mem, x, (size_t)k * c * h * w, PREC_F32, &ds));
+    VC_TRY(dd.alloc(mem, n * elem_size(precision)));
+    VC_TRY(launch_nchw_to_nhwc_pad((const float*)ds, k, c, h, w, dd.out(), cpad, precision, nullptr));
+    return read_elems(dd, n, precision, out, "nchw_to_nhwc_pad_kernel");
+}
+
+int vc_bf16_to_fp8_host(const float* src, int npix, int c, int src_cs, int src_co, float inv_scale, uint8_t* dst, int dst_cs, int dst_co) {
+    VC_CHECK(src && dst && npix >= 1 && c >= 1 && src_co >= 0 && src_cs >= src_co + c && dst_co >= 0 && dst_cs >= dst_co + c, VC_ERR_ARG, "bf16 -> fp8: bad shape");
+    DevScratch mem;
+    GuardedOut dd;
+    void* ds = nullptr;
+    VC_TRY(upload_elems(mem, src, (size_t)npix * src_cs, PREC_BF16, &ds));
+    VC_TRY(dd.alloc(mem, (size_t)npix * dst_cs, dst));
+    const View a{ds, 1, 1, npix, c, src_cs, src_co, 2}, d{dd.out(), 1, 1, npix, c, dst_cs, dst_co, 1};
+    VC_TRY(launch_bf16_to_fp8(a, d, inv_scale, nullptr));
+    return dd.read_back(dst, "bf16_to_fp8_kernel");
+}
+
+int vc_reid_stem_pool_host(const float* crops, int k, const float* w, const float* bias, float* out) {
+    VC_CHECK(crops && w && bias && out && k >= 1, VC_ERR_ARG, "reid stem: bad argument");
+    constexpr int S = VC_REID_SIZE, P = (S - 1) / 2 + 1, CO = 64;
+    DevScratch mem;
+    ConvParam p;
+    p.name = "host"; p.O = CO; p.I = 3; p.kh = 3; p.kw = 3; p.set = true;
+    p.w.assign(w, w + (size_t)CO * 3 * 3 * 3);
+    p.b.assign(bias, bias + CO);
+    VC_TRY(pack_and_upload(mem.allocs, p, PREC_BF16));
+    const size_t npix = (size_t)k * S * S;
+    std::vector<float> x8(npix * p.cin_eff, 0.f);                     // channels 3 .. cin_eff - 1 stay zero, as in the ReID input buffer
+    for (size_t i = 0; i < npix; ++i)
+        for (int ch = 0; ch < 3; ++ch) x8[i * p.cin_eff + ch] = crops[i * 3 + ch];
+    void* dx = nullptr;
+    VC_TRY(upload_elems(mem, x8.data(), x8.size(), PREC_BF16, &dx));
+    GuardedOut dd;
+    const size_t n = (size_t)k * P * P * CO;
+    VC_TRY(dd.alloc(mem, n * 2));
+    ConvP cp{};
+    cp.in = dx; cp.w = p.d_w; cp.bias = p.d_b; cp.out = nullptr;      // the conv's own output never exists
+    cp.B = k; cp.H = S; cp.W = S; cp.Cin = p.cin_eff; cp.in_cs = p.cin_eff; cp.in_co = 0;
+    cp.Ho = S; cp.Wo = S; cp.Cout = CO; cp.out_cs = CO; cp.out_co = 0;
+    cp.kh = cp.kw = 3; cp.sh = cp.sw = 1; cp.ph = cp.pw = 1;
+    cp.K = p.K; cp.Kp = p.Kp; cp.act = ACT_RELU; cp.res_mode = RES_NONE; cp.out_f32 = 0; cp.prec = PREC_BF16;
+    cp.act_scale = cp.inv_act_scale = 1.0f; cp.M = k * S * S; cp.cfg = -1;
+    VC_CHECK(reid_stem_applicable(cp, CO, 0), VC_ERR_ARG, "reid stem: the fused kernel does not take this convolution");
+    VC_TRY(launch_reid_stem_pool(cp, dd.out(), nullptr));
+    return read_elems(dd, n, PREC_BF16, out, "reid_stem_pool_kernel");
+}
+
 // ---- sized batches: the letterbox and crop kernels with their per-frame tables, on host arrays --------------------------------------
 // frames of their own sizes uploaded into cells (include/vcount_hip.h) -> *cells_out (device, in mem); *cell_out: the cell size.
 // Network shapes are not compared here (img_size 1 gives every frame 32 x 32).

@@ -34,7 +34,10 @@ LetterboxFrame letterbox_frame(long long src_off, const LetterboxGeom& g);
 // tab: B entries in device memory.  dst as launch_letterbox; per frame the values are those of launch_letterbox on that frame alone.
 int launch_letterbox_frames(const uint8_t* src, const LetterboxFrame* tab, void* dst, int B, int net_h, int net_w, int swap_rb, int prec, hipStream_t s);
 // SPPF: x = view slice [0,C); writes maxpool5, maxpool5∘2, maxpool5∘3 into slices [C,2C), [2C,3C), [3C,4C) of the same buffer.
-int launch_sppf_pool(const View& cat, int C, int prec, int form, hipStream_t s);   // form 1: register form where it applies, 0: the LDS-plane forms
+// form 1: the register form where it applies, 0: the LDS-plane form.  ran (tests; the engine leaves it null): which kernel the call launched
+// (VC_SPPF_RAN_*, include/vcount_hip.h; 0 = none) and the 32-bit words of a pixel one workgroup (register / LDS form) or thread took.
+struct SppfRan { int kernel, ws; };
+int launch_sppf_pool(const View& cat, int C, int prec, int form, hipStream_t s, SppfRan* ran = nullptr);
 int launch_upsample2x(const View& src, const View& dst, int prec, hipStream_t s);
 // bf16 NHWC -> OCP e4m3fn, value x inv_scale, clamped to +-448 (the stem's output entering the fp8 layers)
 int launch_bf16_to_fp8(const View& src, const View& dst, float inv_scale, hipStream_t s);

@@ -540,6 +540,72 @@ def letterbox(rgb, net_h, net_w, precision="f32"):
     return out
 
 
+def sppf_pool(buf, c, co, precision="bf16", form=1):
+    """launch_sppf_pool on a whole concat buffer (B, H, W, cs): channels [co, co + c) pooled into [co + c, co + 4c).
+    Returns (buffer after the launch, name of the kernel that ran, its slice width in 32-bit words)."""
+    a = L.f32(buf).copy()
+    B, H, W, cs = a.shape
+    kern, ws = C.c_int(), C.c_int()
+    L.check(L.lib().vc_sppf_pool_host(L.ptr(a, C.c_float), B, H, W, cs, co, c, L.PREC_ID[precision], form, C.byref(kern), C.byref(ws)))
+    return a, L.SPPF_RAN[kern.value], ws.value
+
+
+def upsample2x(src, dst, co, precision="bf16"):
+    """upsample2x_kernel: src (B, H, W, c) into channels [co, co + c) of a copy of dst (B, 2H, 2W, cs)."""
+    s, d = L.f32(src), L.f32(dst).copy()
+    B, H, W, c = s.shape
+    assert d.shape[:3] == (B, 2 * H, 2 * W)
+    L.check(L.lib().vc_upsample2x_host(L.ptr(s, C.c_float), B, H, W, c, L.ptr(d, C.c_float), d.shape[3], co, L.PREC_ID[precision]))
+    return d
+
+
+def maxpool3s2(src, dst, co, precision="bf16"):
+    """maxpool3s2_kernel (MaxPool2d(3, 2, 1)): src (B, H, W, c) into channels [co, co + c) of a copy of dst (B, Ho, Wo, cs)."""
+    s, d = L.f32(src), L.f32(dst).copy()
+    B, H, W, c = s.shape
+    assert d.shape[:3] == (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1)
+    L.check(L.lib().vc_maxpool3s2_host(L.ptr(s, C.c_float), B, H, W, c, L.ptr(d, C.c_float), d.shape[3], co, L.PREC_ID[precision]))
+    return d
+
+
+def avgpool_l2norm(x, precision="f32"):
+    """avgpool_l2norm_kernel: (k, h, w, 512) -> (k, 512) float32."""
+    a = L.f32(x)
+    k, h, w, c = a.shape
+    assert c == L.FEAT_DIM
+    out = np.zeros((k, L.FEAT_DIM), np.float32)
+    L.check(L.lib().vc_avgpool_l2norm_host(L.ptr(a, C.c_float), k, h, w, L.PREC_ID[precision], L.ptr(out, C.c_float)))
+    return out
+
+
+def nchw_to_nhwc_pad(x, precision="f32"):
+    """nchw_to_nhwc_pad_kernel: (k, C, H, W) -> (k, H, W, cpad) with the ReID input buffer's cpad (4 in f32, 8 in bf16)."""
+    a = L.f32(x)
+    k, c, h, w = a.shape
+    cpad = 4 if precision == "f32" else 8
+    out = np.full((k, h, w, cpad), np.nan, np.float32)
+    L.check(L.lib().vc_nchw_to_nhwc_pad_host(L.ptr(a, C.c_float), k, c, h, w, cpad, L.PREC_ID[precision], L.ptr(out, C.c_float)))
+    return out
+
+
+def bf16_to_fp8(src, c, src_co, inv_scale, dst, dst_co):
+    """bf16_to_fp8_kernel: channels [src_co, src_co + c) of src (npix, src_cs) float -> e4m3fn bytes [dst_co, dst_co + c) of a copy of
+    dst (npix, dst_cs) uint8."""
+    s, d = L.f32(src), np.ascontiguousarray(dst, dtype=np.uint8).copy()
+    assert s.ndim == 2 and d.ndim == 2 and len(s) == len(d)
+    L.check(L.lib().vc_bf16_to_fp8_host(L.ptr(s, C.c_float), len(s), c, s.shape[1], src_co, float(inv_scale), L.ptr(d, C.c_uint8), d.shape[1], dst_co))
+    return d
+
+
+def reid_stem_pool(crops, w_oihw, bias):
+    """reid_stem_pool_kernel (bf16): crops (k, 50, 50, 3), weights (64, 3, 3, 3), bias (64,) -> (k, 25, 25, 64)."""
+    x, w, b = L.f32(crops), L.f32(w_oihw), L.f32(bias)
+    assert x.shape[1:] == (50, 50, 3) and w.shape == (64, 3, 3, 3) and b.shape == (64,)
+    out = np.zeros((len(x), 25, 25, 64), np.float32)
+    L.check(L.lib().vc_reid_stem_pool_host(L.ptr(x, C.c_float), len(x), L.ptr(w, C.c_float), L.ptr(b, C.c_float), L.ptr(out, C.c_float)))
+    return out
+
+
 def yuv_desc(fmt="nv12", matrix="bt601", full_range=False, pitch_y=0, pitch_c=0, offset_c=0, offset_v=0, frame_stride=0):
     """vc_yuv_desc: layout of 4:2:0 frames in bytes (0 = tightly packed; include/vcount_hip.h)."""
     if fmt not in L.PIX_ID:
