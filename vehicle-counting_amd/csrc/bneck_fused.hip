@@ -28,6 +28,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "conv_launch.h"
 
 namespace vc {
 
@@ -70,6 +71,7 @@ struct BnArgs {
     const uint4* w3; const float* b3; int kw3;
     const uint16_t* y2; int y2_cs;
     uint16_t* z; int z_cs, z_co;
+    long long* dbg;                        // diagnostics (VC_BN_DBG): per workgroup its first and last wall_clock64(); null in production
 };
 
 // Two groups of four waves work on DIFFERENT tiles at the same time: the producers (waves 4-7) compute b1 of tile k + 1 -- few MFMAs,
@@ -79,6 +81,7 @@ struct BnArgs {
 template <bool CV3>
 __global__ __launch_bounds__(BN_NW * 64) void bneck_fused_kernel(const BnArgs a) {
     const bool RES = a.res != 0;                            // launch-uniform: the block has a shortcut
+    if (a.dbg && threadIdx.x == 0) a.dbg[(size_t)blockIdx.x * 2] = wall_clock64();
     __shared__ uint4 bs[2][2 * BN_NP * 4];                 // 2 x 22.5 KB: b1 of two tiles, [32-channel plane][pixel slot][4 chunks]
     __shared__ uint4 w1s[2 * 4 * 64];                      // 8 KB: cv1, [k step][channel tile][lane]
     __shared__ uint4 w2s[18 * 4 * 64];                     // 72 KB: cv2, [k step = 2 tap + half][channel tile][lane]
@@ -343,6 +346,7 @@ __global__ __launch_bounds__(BN_NW * 64) void bneck_fused_kernel(const BnArgs a)
         }
         __syncthreads();                                    // bs[k & 1] is complete, bs[(k - 1) & 1] is free again
     }
+    if (a.dbg && threadIdx.x == 0) a.dbg[(size_t)blockIdx.x * 2 + 1] = wall_clock64();
 }
 
 // pm1 = Bottleneck.cv1, pm2 = Bottleneck.cv2 as engine_plan.hip::yolo_c3 builds them
@@ -400,8 +404,12 @@ int launch_bneck_cv3_fused(const ConvP& pm1, const ConvP& pm2, const ConvP& p3, 
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
     a.res = pm2.res_mode == RES_AFTER_ACT ? 1 : 0;
-    launch_timed(pm1, bneck_fused_kernel<true>, dim3(std::min(ntiles, bneck_grid_cap(cus))), dim3(BN_NW * 64), 0, s, a);
+    const int grid = std::min(ntiles, bneck_grid_cap(cus));
+    static WgStamps stamps("VC_BN_DBG", "bneck cv3", 1024, 2, 0, 1);
+    a.dbg = stamps.next(grid, ntiles, s);
+    launch_timed(pm1, bneck_fused_kernel<true>, dim3(grid), dim3(BN_NW * 64), 0, s, a);
     VC_HIP(hipGetLastError());
+    if (a.dbg) stamps.report(s, [](const long long*, int, int) {});
     return VC_OK;
 }
 
@@ -423,8 +431,11 @@ int launch_bneck_fused(const ConvP& pm1, const ConvP& pm2, hipStream_t s) {
     }();
     const int grid = std::min(ntiles, bneck_grid_cap(cus));                // persistent, one workgroup per CU (128 KB of LDS)
     a.res = pm2.res_mode == RES_AFTER_ACT ? 1 : 0;
+    static WgStamps stamps("VC_BN_DBG", "bneck", 1024, 2, 0, 1);
+    a.dbg = stamps.next(grid, ntiles, s);
     launch_timed(pm1, bneck_fused_kernel<false>, dim3(grid), dim3(BN_NW * 64), 0, s, a);
     VC_HIP(hipGetLastError());
+    if (a.dbg) stamps.report(s, [](const long long*, int, int) {});
     return VC_OK;
 }
 

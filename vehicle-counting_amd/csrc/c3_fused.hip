@@ -63,11 +63,14 @@ struct C3Args {
     uint16_t* y; int out_cs, out_co;
     int B, H, W, tiles_x, tiles_y;
     int abl;                               // diagnostics (VC_C3_ABLATE, wrong results): 1 no transcendentals, 2 no global fetch, 4 no output stores,
-};                                         // 8 no 3x3 pass, 16 no cv12 pass, 32 no m.cv1 pass, 64 no cv3 pass
+                                           // 8 no 3x3 pass, 16 no cv12 pass, 32 no m.cv1 pass, 64 no cv3 pass
+    long long* dbg;                        // diagnostics (VC_C3_DBG): per workgroup its first and last wall_clock64(); null in production
+};
 
 template <bool DIAG>
 __global__ __launch_bounds__(C3_NW * 64, 2) void c3_fused_kernel(const C3Args a) {
     const int abl = DIAG ? a.abl : 0;
+    if (a.dbg && threadIdx.x == 0) a.dbg[(size_t)blockIdx.x * 2] = wall_clock64();
     __shared__ uint4 xa[2 * C3_NP * 4];                    // 24 KB: x planes [k step][pixel slot][4 chunks]; plane 0 becomes b1
     __shared__ uint4 yb[C3_NP * 4];                        // 12 KB: y1 on the halo region, m in place on the interior
     __shared__ uint4 yc[C3_TH * C3_TW * 4];                // 8 KB: y2 on the interior
@@ -118,6 +121,9 @@ __global__ __launch_bounds__(C3_NW * 64, 2) void c3_fused_kernel(const C3Args a)
     char* ycb = (char*)yc;
     const bool odd = (kq & 1) != 0;
     if ((int)blockIdx.x < ntiles) fetch(blockIdx.x);
+    // (tiles claimed from a counter as in front_fused.hip, the claim issued one tile ahead: bit-identical, and late workgroups then took only
+    // their first tile, but 480 workgroups claiming a 7 us tile each slowed every tile down -- lifetimes 710 - 790 us where the stride loop has
+    // 600 (p50) - 780 (p90) -- and the step lost 2 % with this kernel alone converted; profiles/dyn_tiles.md)
     for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const int tx = t % a.tiles_x, ty = (t / a.tiles_x) % a.tiles_y, b = t / (a.tiles_x * a.tiles_y);
         const int oy0 = ty * C3_TH, ox0 = tx * C3_TW;
@@ -252,6 +258,7 @@ __global__ __launch_bounds__(C3_NW * 64, 2) void c3_fused_kernel(const C3Args a)
             }
         }
     }
+    if (a.dbg && threadIdx.x == 0) a.dbg[(size_t)blockIdx.x * 2 + 1] = wall_clock64();
 }
 
 // the four launches of engine_plan.hip::yolo_c3 for n = 1 with a shortcut: cv1 | cv2 (one launch, two destinations), m.cv1, m.cv2, cv3
@@ -285,9 +292,12 @@ int launch_c3_fused(const ConvP& p12, const ConvP& pm1, const ConvP& pm2, const 
     static const int slots_hw = resident_workgroups(c3_fused_kernel<false>, C3_NW * 64);
     const int grid = std::min(ntiles, std::max(256, slots_hw - conv_slots_reserve() / 2));   // persistent; two workgroups per CU: half the usual number of slots stays free
     a.abl = p12.ablate;                                                              // diagnostics only (engine option "c3_ablate", tools/ff_ablate.py)
+    static WgStamps stamps("VC_C3_DBG", "c3", 1024, 2, 0, 1);
+    a.dbg = stamps.next(grid, ntiles, s);
     if (a.abl) launch_timed(p12, c3_fused_kernel<true>, dim3(grid), dim3(C3_NW * 64), 0, s, a);
     else launch_timed(p12, c3_fused_kernel<false>, dim3(grid), dim3(C3_NW * 64), 0, s, a);
     VC_HIP(hipGetLastError());
+    if (a.dbg) stamps.report(s, [](const long long*, int, int) {});
     return VC_OK;
 }
 

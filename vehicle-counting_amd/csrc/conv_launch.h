@@ -1,7 +1,11 @@
 // Host-side pieces the launchers of the convolution kernels share (the conv_*.hip family files, front_fused.hip, c3_fused.hip): the
 // device query, the resident-workgroup count of a kernel, and the process-wide A/B and diagnostic switches.
 #pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
 #include <cstdlib>
+#include <vector>
 
 #include "vc_common.h"
 #include "conv_geom.h"
@@ -66,5 +70,59 @@ static int resident_workgroups(K kernel, int threads = 256) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess || per_cu < 1) per_cu = 1;
     return per_cu * device_cus();
 }
+
+// Diagnostics of the fused persistent kernels (VC_FF_DBG / VC_C3_DBG / VC_BN_DBG = n): every workgroup stamps wall_clock64() (100 MHz) when it
+// starts and when it leaves.  The stamps of n launches collect in device memory with nothing but a memset in the stream -- no allocation,
+// no host wait: the launches run inside the pipeline as they always do -- and are read back and printed after the n-th.  n = 1 reports every launch at once.
+// Record of a workgroup: `stride` 64-bit words, the start stamp in word w0, the end stamp in word w1.
+struct WgStamps {
+    const char* name;
+    int n = 0, used = 0, stride = 0, w0 = 0, w1 = 0;
+    long long* d = nullptr;
+    size_t per_launch = 0;                       // words
+    std::vector<int> grids, tiles;
+    WgStamps(const char* env, const char* kernel, int max_grid, int stride_, int w0_, int w1_) : name(kernel), stride(stride_), w0(w0_), w1(w1_) {
+        const char* v = getenv(env);
+        n = v ? std::max(1, atoi(v)) : 0;
+        per_launch = (size_t)max_grid * stride;
+        if (n && hipMalloc((void**)&d, (size_t)n * per_launch * 8) != hipSuccess) { d = nullptr; n = 0; }
+    }
+    long long* next(int grid, int ntiles, hipStream_t s) {                  // this launch's records, zeroed in stream order; null = off
+        if (!d || used >= n || (size_t)grid * stride > per_launch) return nullptr;
+        long long* p = d + (size_t)used++ * per_launch;
+        hipMemsetAsync(p, 0, (size_t)grid * stride * 8, s);
+        grids.push_back(grid); tiles.push_back(ntiles);
+        return p;
+    }
+    template <class F>
+    void report(hipStream_t s, F extra) {                                    // after a launch: prints once `n` launches have been collected
+        if (!d || used < n) return;
+        hipStreamSynchronize(s);
+        std::vector<long long> h(per_launch);
+        for (int l = 0; l < used; ++l) {
+            const int grid = grids[l];
+            if (hipMemcpy(h.data(), d + (size_t)l * per_launch, (size_t)grid * stride * 8, hipMemcpyDeviceToHost) != hipSuccess) break;
+            std::vector<double> st, du;
+            long long lo = INT64_MAX, hi = 0;
+            for (int b = 0; b < grid; ++b) { const long long* t = &h[(size_t)b * stride]; if (t[w0] && t[w1]) { lo = std::min(lo, t[w0]); hi = std::max(hi, t[w1]); } }
+            int late = 0;
+            for (int b = 0; b < grid; ++b) {
+                const long long* t = &h[(size_t)b * stride];
+                if (!t[w0] || !t[w1]) continue;
+                st.push_back((double)(t[w0] - lo) / 100); du.push_back((double)(t[w1] - t[w0]) / 100);
+                late += t[w0] - lo > 10000;                                  // more than 0.1 ms after the first
+            }
+            const size_t m = st.size();
+            if (!m) continue;
+            std::sort(st.begin(), st.end()); std::sort(du.begin(), du.end());
+            fprintf(stderr, "[vc %s dbg] launch %d: %d tiles on %d workgroups; start offsets us p10/p50/p90/max %.1f %.1f %.1f %.1f ; lifetimes us p10/p50/p90/max %.1f %.1f %.1f %.1f ; "
+                            "%d workgroups (%.1f %%) start > 100 us late ; first start -> last end %.1f us\n",
+                    name, l, tiles[l], grid, st[m / 10], st[m / 2], st[m * 9 / 10], st[m - 1], du[m / 10], du[m / 2], du[m * 9 / 10], du[m - 1], late, 100.0 * late / m,
+                    (double)(hi - lo) / 100);
+            extra(h.data(), grid, tiles[l]);
+        }
+        used = 0; grids.clear(); tiles.clear();
+    }
+};
 
 }  // namespace vc

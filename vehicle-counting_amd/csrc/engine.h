@@ -135,13 +135,22 @@ struct vc_engine {
     hipStream_t rstream = nullptr;   // ReID of the next batch (stream path), concurrent with detector and tracker
     hipStream_t hstream = nullptr;   // Detect-head ops of the P3 / P4 levels, beside the neck layers that follow them (Op::side)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // Tile counters of the fused persistent kernels (vc_common.h: tile_claim): a ring of {next, done} pairs, one per 64-byte line, zeroed once
+    // here; the kernels leave a pair zero.  A launch takes the next pair (tile_ctr_next).  Launches of one stream run one after the other, so a
+    // pair could only be shared by two running kernels if one stream fell a whole ring of such launches behind another: 1 024 pairs, one
+    // launch per detector pass today, and the host waits for a batch's rows before it submits the next but one.
+    static constexpr unsigned kTileCtrPairs = 1024;
+    unsigned* d_tile_ctr = nullptr;
+    unsigned tile_ctr_seq = 0;
+    unsigned tile_ctr_ring = kTileCtrPairs;   // pairs in use (option "dyn_tiles_ring", tests: 1 = every launch gets the pair the one before it left)
+    int conv_slots = 0;              // VC_CONV_SLOTS at creation (tests): grid of front_fused_kernel, ConvP::slots
     void* d_zero = nullptr; size_t zero_bytes = 0; bool want_hc_count = false;   // per-pass counters cleared by one memset (engine_plan.hip)
     hipEvent_t ev_det[2] = {nullptr, nullptr};
     hipEvent_t ev_reid[3] = {nullptr, nullptr, nullptr};
     bool finalized = false;
     // kernel-selection switches: read from the environment ONCE at engine creation (VC_C3_FUSED, VC_BNECK_FUSED, VC_FRONT_FUSED,
     // VC_CROP_PER_PIXEL, VC_DOT_ARENA_MB), changed afterwards only through vc_engine_set_option -- nothing on the launch path calls getenv per launch
-    struct Options { int c3_fused = 1, bneck_fused = 1, bneck_cv3 = 1, front_fused = 1, crop_per_pixel = 0, sparse_head = 1, ff_ablate = 0, c3_ablate = 0, reid_block_fused = 1, head_side = 1, fuse_upsample = 1, sppf_sep = 1, fuse_s2_pw = 1, stem_direct = 1, embed_kept_only = 1; } opt;
+    struct Options { int c3_fused = 1, bneck_fused = 1, bneck_cv3 = 1, front_fused = 1, crop_per_pixel = 0, sparse_head = 1, ff_ablate = 0, c3_ablate = 0, reid_block_fused = 1, dyn_tiles = 1, head_side = 1, fuse_upsample = 1, sppf_sep = 1, fuse_s2_pw = 1, stem_direct = 1, embed_kept_only = 1; } opt;
     std::vector<void*> allocs;       // everything hipMalloc'ed, freed on destroy
     std::vector<void*> host_allocs;  // hipHostMalloc'ed
 
@@ -314,6 +323,11 @@ namespace vc {
 // engine.hip
 int dev_alloc(std::vector<void*>& allocs, void** p, size_t bytes);   // the one allocation routine: hipMalloc, recorded in `allocs`
 inline int dev_alloc(vc_engine* e, void** p, size_t bytes) { return dev_alloc(e->allocs, p, bytes); }
+// the counter pair of the next fused launch; null (option "dyn_tiles" 0) = the fixed stride
+inline unsigned* tile_ctr_next(vc_engine* e) {
+    if (!e->d_tile_ctr || !e->opt.dyn_tiles) return nullptr;
+    return e->d_tile_ctr + (size_t)(e->tile_ctr_seq++ % e->tile_ctr_ring) * 16;
+}
 // Device scratch memory of the stateless host-array entry points (vc_*_host): freed when the owner goes out of scope, so every early
 // VC_TRY / VC_HIP / VC_CHECK return releases it.
 struct DevScratch {

@@ -193,6 +193,7 @@ static int conv_select(ConvCtx& c, double fl, double by, ConvLaunch& L) {
         // YOLO layers 0 + 1 in one kernel (front_fused.hip): layer 0 never reaches HBM.  The log line keeps the stem's own N / K / k / s.
         L.cfg = 102; L.n_ops = 2; L.flops = fl + conv_flops(*o1); L.bytes = in_bytes + w_bytes(op) + w_bytes(*o1) + out_bytes(*o1);
         cp.ablate = e->opt.ff_ablate;
+        cp.slots = e->conv_slots; cp.tile_ctr = tile_ctr_next(e);
         L.launch = [](ConvCtx& x) {
             VC_TRY(launch_front_fused(x.cp, x.op[1].conv, x.u8_src ? x.e->stem_src : nullptr, x.e->stem_geom, x.s));
             x.e->l0_stale = true;                                     // layer 0 lived in LDS only

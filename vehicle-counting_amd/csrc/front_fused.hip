@@ -71,7 +71,7 @@ template <bool U8, bool DIAG = false, bool RS = false>
 __global__ __launch_bounds__(FF_NW * 64, FF_NW == 8 ? 1 : 2) void front_fused_kernel(const uint4* __restrict__ x, const uint4* __restrict__ w0, const float* __restrict__ b0,
                                                              const uint4* __restrict__ w1, const float* __restrict__ b1, uint16_t* __restrict__ y,
                                                              int B, int H, int Wp, int H0, int W0, int H1, int W1, int kw8_0, int kw8_1, int out_cs,
-                                                             int out_co, int tiles_x, int tiles_y, const uint8_t* __restrict__ src8, LetterboxGeom g, long long* dbg, int abl_arg, FrontRS rs) {
+                                                             int out_co, int tiles_x, int tiles_y, const uint8_t* __restrict__ src8, LetterboxGeom g, long long* dbg, int abl_arg, FrontRS rs, unsigned* ctr) {
     const int abl = DIAG ? abl_arg : 0;        // the production instance folds every ablation branch away (they fragment the MFMA loops)
     // abl (VC_FF_ABLATE, diagnostics with WRONG results; 0 in production): 1 no transcendentals, 2 no stem MFMAs, 4 no stem LDS stores,
     // 8 no output stores, 16 no stem phase, 32 no conv phase, 64 no patch writes, 128 no global fetch, 256 no patch reads in the stem
@@ -80,8 +80,10 @@ __global__ __launch_bounds__(FF_NW * 64, FF_NW == 8 ? 1 : 2) void front_fused_ke
     __shared__ uint4 w1s[9 * 4 * 64];                      // 36.9 KB: layer-1 weights, [tap][channel tile][lane] = one fragment load per wave
     __shared__ int4 rs_col[RS ? 2 * FF_PC + 2 : 1];        // resize mode: per tensor column of the patch (byte offset of tap 0 / tap 1 in a staged row, a0, a1 or -1)
     __shared__ int4 rs_row[RS ? FF_PR + 2 : 1];            // per tensor row of the patch (byte offset of source row y0 / y1 in the staging area, b0, b1 or -1)
+    __shared__ int nxt_s;                                  // claimed tiles (ctr): the tile after this one, from thread 0 to the workgroup
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = lane & 15, kq = lane >> 4;
+    if (dbg && lane == 0) dbg[((size_t)blockIdx.x * FF_NW + wave) * 8 + 4] = wall_clock64();      // VC_FF_DBG: this wave's first stamp
     // weights in registers for the whole launch
     ChunkF wf0[5][2];
 #pragma unroll
@@ -212,10 +214,17 @@ __global__ __launch_bounds__(FF_NW * 64, FF_NW == 8 ? 1 : 2) void front_fused_ke
     const bool odd = (kq & 1) != 0;
     char* l0b = (char*)l0t;
     if ((int)blockIdx.x < ntiles) { if constexpr (U8) fetch_raw(blockIdx.x); else fetch(blockIdx.x); }
-    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    // Tiles after a workgroup's first (blockIdx.x) are claimed from the launch's counter pair (tile_claim, vc_common.h) when there is one: a
+    // workgroup that starts late -- its CU held by another queue's kernel -- then takes what is left instead of a fixed 1 / gridDim.x of the tiles.
+    // The claim is issued at the top of a tile and read where the next tile's fetch is issued, behind the patch phase (2.3 us) and the
+    // barrier that ends it.  ctr == nullptr: the fixed stride.
+    int tn;
+    for (int t = blockIdx.x; t < ntiles; t = tn) {
         const int tx = t % tiles_x, ty = (t / tiles_x) % tiles_y, b = t / (tiles_x * tiles_y);
         const int oy0 = ty * FF_TH, ox0 = tx * FF_TW;
         const int gy0 = 2 * oy0 - 1, gx0 = 2 * ox0 - 1;
+        int claimed = 0;
+        if (ctr && threadIdx.x == 0) claimed = tile_claim(ctr);
         long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0;
         if (dbg) ts0 = wall_clock64();
         __syncthreads();                                    // the previous tile's LDS reads are done
@@ -323,9 +332,11 @@ __global__ __launch_bounds__(FF_NW * 64, FF_NW == 8 ? 1 : 2) void front_fused_ke
                 if (i < FF_PR * FF_PC && !(abl & 64)) { const int pr = i / FF_PC; patch[pr * FF_PP + (i - pr * FF_PC)] = patch_chunk(pre[k]); }
             }
         }
+        if (ctr && threadIdx.x == 0) nxt_s = claimed;       // (its readers of the previous tile are two barriers back)
         __syncthreads();
         if (dbg) ts1 = wall_clock64();
-        if (t + (int)gridDim.x < ntiles) { if constexpr (U8) fetch_raw(t + gridDim.x); else fetch(t + gridDim.x); }
+        tn = ctr ? nxt_s : t + (int)gridDim.x;
+        if (tn < ntiles) { if constexpr (U8) fetch_raw(tn); else fetch(tn); }
         // ---- layer 0 on the region.  Pixel tiles are ROW-ALIGNED so that a tile's coordinates cost no division: tile r < 33 = row r,
         // even columns 0 .. 30; tile 33 + r = row r, odd columns 1 .. 31; tiles 66 .. 68 = the 33 pixels of column 32, one row per lane.
         // LDS slot of a pixel: plane (column parity) * 561 + row * 17 + column / 2, as before. ------------------------------------------
@@ -451,6 +462,8 @@ __global__ __launch_bounds__(FF_NW * 64, FF_NW == 8 ? 1 : 2) void front_fused_ke
             d[0] += ts1 - ts0; d[1] += ts2 - ts1; d[3] += ts3 - ts2;
         }
     }
+    if (ctr && threadIdx.x == 0) tile_claims_done(ctr);
+    if (dbg && lane == 0) dbg[((size_t)blockIdx.x * FF_NW + wave) * 8 + 5] = wall_clock64();      // ... and its last
 }
 
 // p0 = the stem as launch_conv sees it (stem_direct_applicable), p1 = the conv that consumes its output
@@ -499,35 +512,31 @@ int launch_front_fused(const ConvP& p0, const ConvP& p1, const uint8_t* src8, co
     const int tiles_x = (p1.Wo + FF_TW - 1) / FF_TW, tiles_y = (p1.Ho + FF_TH - 1) / FF_TH;
     const int ntiles = p1.B * tiles_x * tiles_y;
     static const int slots_hw = resident_workgroups(front_fused_kernel<true>, FF_NW * 64);
-    // (tiles handed out by an atomic counter instead of the static stride -- late-starting workgroups, e.g. behind the tracker's, would not carry
-    // a full share -- measured 7.09 against 7.13 ms per bench step over five alternating runs: inside the spread, not kept)
-    const int grid = std::min(ntiles, std::max(256, slots_hw - conv_slots_reserve()));   // persistent: every workgroup walks tiles; at one workgroup per CU nothing is held back (as in launch_one)
+    // (p0.slots: the tests' grid override.  p0.tile_ctr: with claimed tiles a launch inside the pipeline takes 1.00 ms on average where the stride
+    // loop took 1.67 -- two workgroups that start one lifetime late doubled it -- and the step 11.02 ms instead of 11.19; profiles/dyn_tiles.md)
+    const int grid = p0.slots > 0 ? std::min(ntiles, p0.slots) : std::min(ntiles, std::max(256, slots_hw - conv_slots_reserve()));   // persistent: every workgroup walks tiles; at one workgroup per CU nothing is held back (as in launch_one)
     const uint4* x = (const uint4*)p0.in;
     uint16_t* y = (uint16_t*)p1.out;
-    static const bool dbg_on = getenv("VC_FF_DBG") != nullptr;
     const int abl = p0.ablate;                                                        // diagnostics only (engine option "ff_ablate", tools/ff_ablate.py)
-    long long* dbg = nullptr;
-    if (dbg_on && hipMalloc((void**)&dbg, (size_t)grid * FF_NW * 64) == hipSuccess) hipMemsetAsync(dbg, 0, (size_t)grid * FF_NW * 64, s);
+    static WgStamps stamps("VC_FF_DBG", "ff", 1024, FF_NW * 8, 4, 5);                 // per wave: phase sums in words 0, 1, 3, first / last stamp in 4, 5
+    long long* dbg = stamps.next(grid, ntiles, s);
     const bool resize = src8 && !(g.unpad_h == g.src_h && g.unpad_w == g.src_w && g.src_w % 2 == 0 && g.left % 2 == 0);
     FrontRS rs{0, 0, 1.0, 1.0};
     if (resize && !front_rs_plan(g, rs)) { set_error("front_fused: the resize geometry %dx%d -> %dx%d does not fit the staging area", g.src_h, g.src_w, g.unpad_h, g.unpad_w); return VC_ERR_ARG; }
-#define FF_ARGS x, (const uint4*)p0.w, p0.bias, (const uint4*)p1.w, p1.bias, y, p0.B, p0.H, p0.W, p0.Ho, p0.Wo, p1.Ho, p1.Wo, p0.Kp / 8, p1.Kp / 8, p1.out_cs, p1.out_co, tiles_x, tiles_y, src8, g, dbg, abl, rs
+#define FF_ARGS x, (const uint4*)p0.w, p0.bias, (const uint4*)p1.w, p1.bias, y, p0.B, p0.H, p0.W, p0.Ho, p0.Wo, p1.Ho, p1.Wo, p0.Kp / 8, p1.Kp / 8, p1.out_cs, p1.out_co, tiles_x, tiles_y, src8, g, dbg, abl, rs, p0.tile_ctr
     if (resize) launch_timed(p0, front_fused_kernel<true, false, true>, dim3(grid), dim3(FF_NW * 64), 0, s, FF_ARGS);
     else if (src8 && abl) launch_timed(p0, front_fused_kernel<true, true>, dim3(grid), dim3(FF_NW * 64), 0, s, FF_ARGS);
     else if (src8) launch_timed(p0, front_fused_kernel<true>, dim3(grid), dim3(FF_NW * 64), 0, s, FF_ARGS);
     else launch_timed(p0, front_fused_kernel<false>, dim3(grid), dim3(FF_NW * 64), 0, s, FF_ARGS);
 #undef FF_ARGS
     VC_HIP(hipGetLastError());
-    if (dbg) {
-        hipStreamSynchronize(s);
-        std::vector<long long> h((size_t)grid * FF_NW * 8);
-        hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost);
-        hipFree(dbg);
-        double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (size_t i = 0; i < h.size(); ++i) a[i & 7] += (double)h[i];
-        const double per = (double)ntiles / grid * grid * FF_NW;      // (tiles per workgroup) x waves
-        fprintf(stderr, "[vc ff dbg] %d tiles on %d workgroups; us per tile and wave: patch %.2f stem %.2f conv %.2f\n", ntiles, grid, a[0] / per / 100.0, a[1] / per / 100.0, a[3] / per / 100.0);
-    }
+    if (dbg)
+        stamps.report(s, [](const long long* h, int grid, int nt) {
+            double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            for (size_t i = 0; i < (size_t)grid * FF_NW * 8; ++i) a[i & 7] += (double)h[i];
+            const double per = (double)nt * FF_NW;                   // (tiles per workgroup) x workgroups x waves
+            fprintf(stderr, "[vc ff dbg]   us per tile and wave: patch %.2f stem %.2f conv %.2f\n", a[0] / per / 100.0, a[1] / per / 100.0, a[3] / per / 100.0);
+        });
     return VC_OK;
 }
 

@@ -178,7 +178,25 @@ struct ConvP {
                          // VC_CONV_SLOTS -- the launchers themselves never read the environment
     int ablate;          // diagnostics only (VC_CONV_ABLATE, timing experiments with wrong results): 1 = no staging DMA after the first tiles,
                          // 2 = no output stores, 3 = both, 6 = return at once (launch floor of the grid); per-phase times come from dbg
+    unsigned* tile_ctr;  // front_fused_kernel: this launch's counter pair {next, done} (zero; engine.h: tile_ctr_next), null = the fixed-stride loop
 };
+
+// Claimed tiles of a persistent kernel.  Workgroup b starts with tile b; every later tile is gridDim.x + (what `next` held), so a workgroup that
+// starts late takes what is left.  A workgroup makes claims until one returns a tile >= ntiles -- exactly one such claim each -- and then
+// calls tile_claims_done; the last of the gridDim.x callers zeroes the pair for the launch that gets it next from the ring.  Every other
+// workgroup's last claim precedes its own `done` increment (the claim's result decided that it leaves), so nothing touches `next` after
+// the reset.  Nobody waits for anybody.  One lane per workgroup calls these; agent scope: the workgroups sit on all XCDs.
+#if defined(__HIPCC__)
+__device__ __forceinline__ int tile_claim(unsigned* ctr) {
+    return (int)gridDim.x + (int)__hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void tile_claims_done(unsigned* ctr) {
+    if (__hip_atomic_fetch_add(ctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
+        __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(ctr + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+#endif
 
 // launch, optionally with the dispatch's own start/stop timestamps written to p.ev_start / p.ev_stop (what rocprofv3 reports as the
 // kernel duration; a hipEventRecord pair around a launch also counts the time the dispatch waits behind other queues)
