@@ -441,6 +441,30 @@ typedef struct vc_conv_desc {
 } vc_conv_desc;
 /* x NHWC f32, w OIHW f32, bias f32[cout], res NHWC f32 or NULL, y NHWC f32 (bf16 mode rounds x, w, res, y). */
 int vc_conv2d_host(const vc_conv_desc* d, const float* x, const float* w, const float* bias, const float* res, float* y);
+/* The launch views of a convolution (what the engine's ConvP carries besides the plain problem), on whole host buffers at full channel
+ * stride.  Element type E = d->precision; a channel slice is (cs, co) as below. */
+typedef struct vc_conv_view {
+    int in_cs, in_co;                /* input channels [in_co, in_co + cin) of x */
+    int out_cs, out_co;              /* the concat-slice store into y */
+    int res_cs, res_co;              /* the residual as a slice of res (res != NULL) */
+    int split, out2_cs, out2_co;     /* split > 0: output channels >= split go to y2 at out2_co + (channel - split) */
+    int out_f32;                     /* bf16 arithmetic, f32 store */
+    int out_bf16;                    /* fp8 arithmetic, bf16 store */
+    int m_valid;                     /* -1: none; otherwise the number of valid output pixels, put in device memory (ConvP::m_dev) */
+    int up_c, up_cs, up_co;          /* up_c > 0: input channels [0, up_c) are the 2 x nearest upsampling of channels [up_co, up_co + up_c) of x_up */
+} vc_conv_view;
+/* vc_conv2d_host's launch with these views: the same launch_conv call, the same environment (VC_CONV_CFG, VC_CONV_SLOTS, VC_CONV_STRICT).
+ * x [b][h][w][in_cs], x_up [b][h/2][w/2][up_cs] (up_c > 0), res [b][ho][wo][res_cs] (or NULL): converted element by element to E, NaN
+ * stays NaN.  y [b][ho][wo][out_cs] and y2 [b][ho][wo][out2_cs] (split > 0) are in AND out: uploaded as the store type (f32 / bf16 / e4m3),
+ * launched into between guard blocks and read back whole, so elements no launch may touch can be compared by value.  d->cin must be a
+ * multiple of the chunk (8 bf16, 4 f32, 16 fp8).  A refused launch is VC_ERR_ARG and leaves y / y2 as they were. */
+int vc_conv2d_view_host(const vc_conv_desc* d, const vc_conv_view* v, const float* x, const float* x_up, const float* w, const float* bias,
+                        const float* res, float* y, float* y2);
+/* launch_s2halo_pw on host arrays (bf16): the 3x3 / s2 / p1 convolution d (SiLU, cout 128, weights w, bias) over channels [in_co, in_co + cin)
+ * of x [b][h][w][in_cs], and on the tile the pointwise 128 -> 128 conv (SiLU, w_pw, bias_pw) that alone reads it, stored through v's
+ * out_cs / out_co / split / out2_*: y, y2 as above.  The 3x3's own output is never written and not returned. */
+int vc_conv_s2_pw_host(const vc_conv_desc* d, const vc_conv_view* v, const float* x, const float* w, const float* bias, const float* w_pw,
+                       const float* bias_pw, float* y, float* y2);
 int vc_kalman_initiate_host(const double* xyah, int n, double* mean8, double* cov64);
 int vc_kalman_predict_host(double* mean8, double* cov64, int n);
 int vc_kalman_update_host(double* mean8, double* cov64, const double* z4, int n);

@@ -49,6 +49,13 @@ class ConvDesc(C.Structure):
                 ("precision", C.c_int)]
 
 
+class ConvView(C.Structure):
+    """vc_conv_view: the launch views of vc_conv2d_view_host / vc_conv_s2_pw_host."""
+    _fields_ = [("in_cs", C.c_int), ("in_co", C.c_int), ("out_cs", C.c_int), ("out_co", C.c_int), ("res_cs", C.c_int), ("res_co", C.c_int),
+                ("split", C.c_int), ("out2_cs", C.c_int), ("out2_co", C.c_int), ("out_f32", C.c_int), ("out_bf16", C.c_int),
+                ("m_valid", C.c_int), ("up_c", C.c_int), ("up_cs", C.c_int), ("up_co", C.c_int)]
+
+
 class YuvDesc(C.Structure):
     """vc_yuv_desc: byte geometry of 4:2:0 frames, 0 = tightly packed."""
     _fields_ = [("format", C.c_int), ("matrix", C.c_int), ("full_range", C.c_int), ("pitch_y", C.c_int), ("pitch_c", C.c_int),
@@ -175,6 +182,8 @@ SIGNATURES = {
     "vc_profile_reset": [_vp],
     "vc_profile_ops": [_vp, C.c_char_p, C.c_size_t],
     "vc_conv2d_host": [_P(ConvDesc), _pf, _pf, _pf, _pf, _pf],
+    "vc_conv2d_view_host": [_P(ConvDesc), _P(ConvView), _pf, _pf, _pf, _pf, _pf, _pf, _pf],
+    "vc_conv_s2_pw_host": [_P(ConvDesc), _P(ConvView), _pf, _pf, _pf, _pf, _pf, _pf, _pf],
     "vc_kalman_initiate_host": [_pd, _i, _pd, _pd],
     "vc_kalman_predict_host": [_pd, _pd, _i],
     "vc_kalman_update_host": [_pd, _pd, _pd, _i],

@@ -362,7 +362,7 @@ static inline int halo_patch_pixels(const ConvP& p, int bp) {
 }
 static inline bool halo_applicable(const ConvP& p, int bp) {
     if (p.prec != PREC_BF16 || p.kh != 3 || p.kw != 3 || p.sh != 1 || p.sw != 1 || p.ph != 1 || p.pw != 1) return false;
-    if (p.Cin % 32 != 0 || p.in_cs % 8 != 0 || p.in_co % 8 != 0 || p.Ho != p.H || p.Wo != p.W) return false;
+    if (p.Cin % 32 != 0 || p.in_cs % 8 != 0 || p.in_co % 8 != 0 || p.Ho != p.H || p.Wo != p.W || p.m_dev) return false;
     return halo_patch_pixels(p, bp) <= 11 * 64 - 1;
 }
 

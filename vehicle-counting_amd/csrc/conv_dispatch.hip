@@ -67,6 +67,7 @@ int conv_check(const ConvP& p) {
     VC_CHECK(p.out_cs % 4 == 0 && p.out_co % 4 == 0, VC_ERR_ARG, "conv: output stride/offset must be multiples of 4");
     VC_CHECK(p.split == 0 || (p.split % 4 == 0 && p.out2 && p.out2_cs % 4 == 0 && p.out2_co % 4 == 0 && p.res_mode == RES_NONE), VC_ERR_ARG,
              "conv: bad split destination");
+    VC_CHECK(!(p.prec == PREC_FP8 && p.out_bf16 && p.split != 0), VC_ERR_ARG, "conv fp8: the bf16 store has one destination (conv_epilogue_fp8 would put channels >= split behind the first slice)");
     VC_CHECK(p.res_mode == RES_NONE || (p.res_cs % 4 == 0 && p.res_co % 4 == 0), VC_ERR_ARG, "conv: residual alignment");
     VC_CHECK(p.Kp % conv_k_tile(p.prec) == 0 && p.Kp >= p.K, VC_ERR_ARG, "conv: bad K padding %d/%d", p.K, p.Kp);
     VC_CHECK(p.M > 0 && p.Cout > 0, VC_ERR_ARG, "conv: empty problem");

@@ -696,45 +696,94 @@ int vc_profile_conv_busy(vc_engine* e, double* union_ms, double* span_ms) {
 }
 
 // ---- single-function entry points --------------------------------------------------------------------------
-int vc_conv2d_host(const vc_conv_desc* d, const float* x, const float* w, const float* bias, const float* res, float* y) {
-    VC_CHECK(d && x && w && bias && y, VC_ERR_ARG, "null argument");
-    const int prec = d->precision, es = elem_size(prec), ch = prec == PREC_F32 ? 4 : prec == PREC_FP8 ? 16 : 8;
+// n floats -> elements of `prec` (exact for values the type represents; NaN stays NaN) and back
+static std::vector<uint8_t> to_elems(const float* src, size_t n, int prec) {
+    const int es = elem_size(prec);
+    std::vector<uint8_t> buf(n * es);
+    for (size_t i = 0; i < n; ++i) {
+        if (es == 4) ((float*)buf.data())[i] = src[i];
+        else if (es == 2) ((uint16_t*)buf.data())[i] = f32_to_bf16(src[i]);
+        else buf[i] = f32_to_e4m3(src[i]);
+    }
+    return buf;
+}
+static void from_elems(const std::vector<uint8_t>& buf, size_t n, int prec, float* dst) {
+    const int es = elem_size(prec);
+    for (size_t i = 0; i < n; ++i)
+        dst[i] = es == 4 ? ((const float*)buf.data())[i] : es == 2 ? bf16_to_f32(((const uint16_t*)buf.data())[i]) : e4m3_to_f32(buf[i]);
+}
+static int upload_elems(DevScratch& mem, const float* src, size_t n, int prec, void** dst) {
+    const std::vector<uint8_t> buf = to_elems(src, n, prec);
+    VC_TRY(mem.alloc(dst, buf.size()));
+    VC_HIP(hipMemcpy(*dst, buf.data(), buf.size(), hipMemcpyHostToDevice));
+    return VC_OK;
+}
+// the caller's float array as the guarded device buffer a kernel writes into, and back
+static int guarded_elems(DevScratch& mem, GuardedOut& g, const float* init, size_t n, int prec) {
+    const std::vector<uint8_t> buf = to_elems(init, n, prec);
+    return g.alloc(mem, buf.size(), buf.data());
+}
+static int read_elems(const GuardedOut& g, size_t n, int prec, float* dst, const char* kernel) {
+    std::vector<uint8_t> buf(g.bytes);
+    VC_TRY(g.read_back(buf.data(), kernel));
+    from_elems(buf, n, prec, dst);
+    return VC_OK;
+}
+
+// One convolution launch on host arrays under the views of `v` (include/vcount_hip.h: vc_conv2d_view_host); vc_conv2d_host is its dense
+// case.  d->cin may be short of the chunk here (the weights are packed for round_up(cin, chunk) channels, x holds that many).
+static int conv_view_run(const vc_conv_desc* d, const vc_conv_view* v, const float* x, const float* x_up, const float* w, const float* bias,
+                         const float* res, float* y, float* y2) {
+    const int prec = d->precision, ch = prec == PREC_F32 ? 4 : prec == PREC_FP8 ? 16 : 8;
+    set_error("%s", "");                               // a launcher refuses a shape without a message: the caller must not read an older one
+    VC_CHECK(prec == PREC_F32 || prec == PREC_BF16 || prec == PREC_FP8, VC_ERR_ARG, "conv: bad precision");
+    VC_CHECK(d->b >= 1 && d->h >= 1 && d->w >= 1 && d->cin >= 1 && d->cout >= 1 && d->kh >= 1 && d->kw >= 1 && d->stride >= 1 && d->pad >= 0, VC_ERR_ARG, "conv: bad shape");
+    const int cin_eff = round_up(d->cin, ch);
+    const int Ho = (d->h + 2 * d->pad - d->kh) / d->stride + 1, Wo = (d->w + 2 * d->pad - d->kw) / d->stride + 1;
+    VC_CHECK(Ho >= 1 && Wo >= 1, VC_ERR_ARG, "conv: empty output");
+    const size_t npix_in = (size_t)d->b * d->h * d->w, npix_out = (size_t)d->b * Ho * Wo;
+    const int cout_l = prec == PREC_FP8 ? round_up(d->cout, 8) : d->cout;   // the fp8 epilogue stores 8 channels at a time (weight / bias / scale rows are zero-padded)
+    const bool with_res = res && d->res_mode != RES_NONE, up = v->up_c > 0;
+    // every slice inside its buffer: the kernels address by (stride, offset) alone
+    VC_CHECK(v->in_co >= 0 && v->in_cs >= v->in_co + cin_eff, VC_ERR_ARG, "conv view: input slice [%d, %d) outside stride %d", v->in_co, v->in_co + cin_eff, v->in_cs);
+    VC_CHECK(v->split >= 0 && v->split < cout_l && (v->split == 0 || y2), VC_ERR_ARG, "conv view: split %d of %d channels", v->split, cout_l);
+    VC_CHECK(v->out_co >= 0 && v->out_cs >= v->out_co + (v->split > 0 ? v->split : cout_l), VC_ERR_ARG, "conv view: output slice outside stride %d", v->out_cs);
+    VC_CHECK(v->split == 0 || (v->out2_co >= 0 && v->out2_cs >= v->out2_co + cout_l - v->split), VC_ERR_ARG, "conv view: second output slice outside stride %d", v->out2_cs);
+    VC_CHECK(!with_res || (v->res_co >= 0 && v->res_cs >= v->res_co + round_up(cout_l, 4)), VC_ERR_ARG, "conv view: residual slice outside stride %d", v->res_cs);
+    VC_CHECK(!up || (x_up && v->up_c <= cin_eff && v->up_co >= 0 && v->up_cs >= v->up_co + v->up_c), VC_ERR_ARG, "conv view: upsampled slice outside stride %d", v->up_cs);
+    VC_CHECK((!v->out_f32 || prec == PREC_BF16) && (!v->out_bf16 || prec == PREC_FP8), VC_ERR_ARG, "conv view: out_f32 belongs to bf16, out_bf16 to fp8");
+    const int oprec = (prec == PREC_F32 || v->out_f32) ? (int)PREC_F32 : (prec == PREC_BF16 || v->out_bf16) ? (int)PREC_BF16 : (int)PREC_FP8;   // element type of the stores
     DevScratch mem;
     ConvParam p;
     p.name = "host"; p.O = d->cout; p.I = d->cin; p.kh = d->kh; p.kw = d->kw; p.set = true;
     p.w.assign(w, w + (size_t)d->cout * d->cin * d->kh * d->kw);
     p.b.assign(bias, bias + d->cout);
     VC_TRY(pack_and_upload(mem.allocs, p, prec));
-    const int cin_eff = p.cin_eff;
-    const int Ho = (d->h + 2 * d->pad - d->kh) / d->stride + 1, Wo = (d->w + 2 * d->pad - d->kw) / d->stride + 1;
-    const size_t npix_in = (size_t)d->b * d->h * d->w, npix_out = (size_t)d->b * Ho * Wo;
-    const int cout_s = round_up(d->cout, prec == PREC_FP8 ? 8 : 4);
-    void *dx = nullptr, *dy = nullptr, *dr = nullptr;
-    auto upload = [&](const float* src, size_t npix, int C, int Cs, void** dst) -> int {
-        std::vector<uint8_t> buf(npix * Cs * es, 0);
-        for (size_t i = 0; i < npix; ++i)
-            for (int c = 0; c < C; ++c) {
-                if (es == 4) ((float*)buf.data())[i * Cs + c] = src[i * C + c];
-                else if (es == 2) ((uint16_t*)buf.data())[i * Cs + c] = f32_to_bf16(src[i * C + c]);
-                else buf[i * Cs + c] = f32_to_e4m3(src[i * C + c]);                 // activation scale 1
-            }
-        VC_TRY(mem.alloc(dst, buf.size()));
-        VC_HIP(hipMemcpy(*dst, buf.data(), buf.size(), hipMemcpyHostToDevice));
-        return VC_OK;
-    };
-    VC_TRY(upload(x, npix_in, d->cin, cin_eff, &dx));
-    if (res) VC_TRY(upload(res, npix_out, d->cout, cout_s, &dr));
-    VC_TRY(mem.alloc(&dy, npix_out * cout_s * es));
+    void *dx = nullptr, *dxu = nullptr, *dr = nullptr;
+    int* dm = nullptr;
+    VC_TRY(upload_elems(mem, x, npix_in * v->in_cs, prec, &dx));                 // activation scale 1
+    if (up) VC_TRY(upload_elems(mem, x_up, (size_t)d->b * (d->h / 2) * (d->w / 2) * v->up_cs, prec, &dxu));
+    if (with_res) VC_TRY(upload_elems(mem, res, npix_out * v->res_cs, prec, &dr));
+    if (v->m_valid >= 0) {
+        VC_TRY(mem.alloc(&dm, sizeof(int)));
+        VC_HIP(hipMemcpy(dm, &v->m_valid, sizeof(int), hipMemcpyHostToDevice));
+    }
+    GuardedOut gy, gy2;
+    const size_t ny = npix_out * v->out_cs, ny2 = npix_out * (size_t)v->out2_cs;
+    VC_TRY(guarded_elems(mem, gy, y, ny, oprec));
+    if (v->split > 0) VC_TRY(guarded_elems(mem, gy2, y2, ny2, oprec));
     int st = VC_OK;
     {
         ConvP c{};
-        c.in = dx; c.w = p.d_w; c.bias = p.d_b; c.res = dr; c.out = dy;
-        c.B = d->b; c.H = d->h; c.W = d->w; c.Cin = cin_eff; c.in_cs = cin_eff; c.in_co = 0;
-        c.Ho = Ho; c.Wo = Wo; c.Cout = d->cout; c.out_cs = cout_s; c.out_co = 0; c.res_cs = cout_s; c.res_co = 0;
+        c.in = dx; c.w = p.d_w; c.bias = p.d_b; c.res = dr; c.out = gy.out();
+        c.B = d->b; c.H = d->h; c.W = d->w; c.Cin = cin_eff; c.in_cs = v->in_cs; c.in_co = v->in_co;
+        c.Ho = Ho; c.Wo = Wo; c.Cout = cout_l; c.out_cs = v->out_cs; c.out_co = v->out_co; c.res_cs = v->res_cs; c.res_co = v->res_co;
         c.kh = d->kh; c.kw = d->kw; c.sh = c.sw = d->stride; c.ph = c.pw = d->pad;
-        c.K = p.K; c.Kp = p.Kp; c.act = d->act; c.res_mode = res ? d->res_mode : RES_NONE; c.out_f32 = 0; c.prec = prec;
-        c.scale = p.d_scale; c.act_scale = 1.0f; c.inv_act_scale = 1.0f; c.out_bf16 = 0;
-        if (prec == PREC_FP8) c.Cout = round_up(d->cout, 8);      // the fp8 epilogue stores 8 channels at a time (weight / bias / scale rows are zero-padded)
+        c.K = p.K; c.Kp = p.Kp; c.act = d->act; c.res_mode = with_res ? d->res_mode : RES_NONE; c.out_f32 = v->out_f32; c.prec = prec;
+        c.scale = p.d_scale; c.act_scale = 1.0f; c.inv_act_scale = 1.0f; c.out_bf16 = v->out_bf16;
+        if (v->split > 0) { c.split = v->split; c.out2 = gy2.out(); c.out2_cs = v->out2_cs; c.out2_co = v->out2_co; }
+        c.m_dev = dm;
+        if (up) { c.in_up = dxu; c.up_C = v->up_c; c.up_cs = v->up_cs; c.up_co = v->up_co; }
         c.M = d->b * Ho * Wo;
         c.cfg = getenv("VC_CONV_CFG") ? atoi(getenv("VC_CONV_CFG")) : -1;
         c.ablate = getenv("VC_CONV_ABLATE") ? atoi(getenv("VC_CONV_ABLATE")) : 0;
@@ -791,14 +840,103 @@ int vc_conv2d_host(const vc_conv_desc* d, const float* x, const float* w, const 
             hipFree(dbg);
         }
     }
-    if (st == VC_OK) {
-        std::vector<uint8_t> buf(npix_out * cout_s * es);
-        if (hipMemcpy(buf.data(), dy, buf.size(), hipMemcpyDeviceToHost) != hipSuccess) { set_error("copy back failed"); st = VC_ERR_HIP; }
-        for (size_t i = 0; i < npix_out && st == VC_OK; ++i)
-            for (int c = 0; c < d->cout; ++c)
-                y[i * d->cout + c] = es == 4 ? ((const float*)buf.data())[i * cout_s + c] : es == 2 ? bf16_to_f32(((const uint16_t*)buf.data())[i * cout_s + c]) : e4m3_to_f32(buf[i * cout_s + c]);
+    VC_TRY(st);                                         // a refused launch leaves y / y2 as the caller passed them
+    VC_TRY(read_elems(gy, ny, oprec, y, "the conv kernel"));
+    if (v->split > 0) VC_TRY(read_elems(gy2, ny2, oprec, y2, "the conv kernel (second destination)"));
+    return VC_OK;
+}
+
+int vc_conv2d_host(const vc_conv_desc* d, const float* x, const float* w, const float* bias, const float* res, float* y) {
+    VC_CHECK(d && x && w && bias && y, VC_ERR_ARG, "null argument");
+    const int prec = d->precision;
+    VC_CHECK(d->b >= 1 && d->h >= 1 && d->w >= 1 && d->cin >= 1 && d->cout >= 1 && d->kh >= 1 && d->kw >= 1 && d->stride >= 1 && d->pad >= 0, VC_ERR_ARG, "conv: bad shape");
+    // the dense case of conv_view_run: input channels padded with zeros to the chunk (the 3 -> 8 stem padding), output rows to 4 (fp8: 8)
+    const int cin_eff = round_up(d->cin, prec == PREC_F32 ? 4 : prec == PREC_FP8 ? 16 : 8), cout_s = round_up(d->cout, prec == PREC_FP8 ? 8 : 4);
+    const int Ho = (d->h + 2 * d->pad - d->kh) / d->stride + 1, Wo = (d->w + 2 * d->pad - d->kw) / d->stride + 1;
+    VC_CHECK(Ho >= 1 && Wo >= 1, VC_ERR_ARG, "conv: empty output");
+    const size_t npix_in = (size_t)d->b * d->h * d->w, npix_out = (size_t)d->b * Ho * Wo;
+    auto padded = [](const float* src, size_t npix, int C, int Cs) {
+        std::vector<float> buf(npix * Cs, 0.f);
+        for (size_t i = 0; i < npix; ++i)
+            for (int c = 0; c < C; ++c) buf[i * Cs + c] = src[i * C + c];
+        return buf;
+    };
+    const std::vector<float> xs = padded(x, npix_in, d->cin, cin_eff);
+    const std::vector<float> rs = res ? padded(res, npix_out, d->cout, cout_s) : std::vector<float>();
+    std::vector<float> ys(npix_out * cout_s, 0.f);
+    vc_conv_view v{};
+    v.in_cs = cin_eff; v.out_cs = cout_s; v.res_cs = cout_s; v.m_valid = -1;
+    VC_TRY(conv_view_run(d, &v, xs.data(), nullptr, w, bias, res ? rs.data() : nullptr, ys.data(), nullptr));
+    for (size_t i = 0; i < npix_out; ++i)
+        for (int c = 0; c < d->cout; ++c) y[i * d->cout + c] = ys[i * cout_s + c];
+    return VC_OK;
+}
+
+int vc_conv2d_view_host(const vc_conv_desc* d, const vc_conv_view* v, const float* x, const float* x_up, const float* w, const float* bias,
+                        const float* res, float* y, float* y2) {
+    VC_CHECK(d && v && x && w && bias && y, VC_ERR_ARG, "null argument");
+    const int ch = d->precision == PREC_F32 ? 4 : d->precision == PREC_FP8 ? 16 : 8;
+    VC_CHECK(d->cin > 0 && d->cin % ch == 0, VC_ERR_ARG, "conv view: cin %d must be a multiple of %d (vc_conv2d_host pads the stem)", d->cin, ch);
+    return conv_view_run(d, v, x, x_up, w, bias, res, y, y2);
+}
+
+int vc_conv_s2_pw_host(const vc_conv_desc* d, const vc_conv_view* v, const float* x, const float* w, const float* bias, const float* w_pw,
+                       const float* bias_pw, float* y, float* y2) {
+    VC_CHECK(d && v && x && w && bias && w_pw && bias_pw && y, VC_ERR_ARG, "null argument");
+    constexpr int CO = 128;
+    VC_CHECK(d->precision == PREC_BF16 && d->kh == 3 && d->kw == 3 && d->stride == 2 && d->pad == 1 && d->cout == CO && d->act == ACT_SILU && d->res_mode == RES_NONE,
+             VC_ERR_ARG, "s2 + pointwise: a bf16 3x3 / s2 / p1 conv with SiLU to 128 channels");
+    VC_CHECK(d->b >= 1 && d->h >= 2 && d->w >= 2 && d->cin >= 8 && d->cin % 8 == 0, VC_ERR_ARG, "s2 + pointwise: bad shape");
+    const int Ho = (d->h + 2 - 3) / 2 + 1, Wo = (d->w + 2 - 3) / 2 + 1;
+    const size_t npix_in = (size_t)d->b * d->h * d->w, npix_out = (size_t)d->b * Ho * Wo;
+    VC_CHECK(v->in_co >= 0 && v->in_cs >= v->in_co + d->cin, VC_ERR_ARG, "s2 + pointwise: input slice outside stride %d", v->in_cs);
+    VC_CHECK(v->split >= 0 && v->split < CO && (v->split == 0 || y2), VC_ERR_ARG, "s2 + pointwise: split %d of %d channels", v->split, CO);
+    VC_CHECK(v->out_co >= 0 && v->out_cs >= v->out_co + (v->split > 0 ? v->split : CO), VC_ERR_ARG, "s2 + pointwise: output slice outside stride %d", v->out_cs);
+    VC_CHECK(v->split == 0 || (v->out2_co >= 0 && v->out2_cs >= v->out2_co + CO - v->split), VC_ERR_ARG, "s2 + pointwise: second output slice outside stride %d", v->out2_cs);
+    DevScratch mem;
+    ConvParam p3, p1;
+    p3.name = "host 3x3"; p3.O = CO; p3.I = d->cin; p3.kh = 3; p3.kw = 3; p3.set = true;
+    p3.w.assign(w, w + (size_t)CO * d->cin * 9);
+    p3.b.assign(bias, bias + CO);
+    p1.name = "host 1x1"; p1.O = CO; p1.I = CO; p1.kh = 1; p1.kw = 1; p1.set = true;
+    p1.w.assign(w_pw, w_pw + (size_t)CO * CO);
+    p1.b.assign(bias_pw, bias_pw + CO);
+    VC_TRY(pack_and_upload(mem.allocs, p3, PREC_BF16));
+    VC_TRY(pack_and_upload(mem.allocs, p1, PREC_BF16));
+    void* dx = nullptr;
+    VC_TRY(upload_elems(mem, x, npix_in * v->in_cs, PREC_BF16, &dx));
+    GuardedOut gmid, gy, gy2;                          // gmid: the 3x3's own output, which the fused kernel keeps on chip
+    VC_TRY(gmid.alloc(mem, npix_out * CO * 2));
+    const size_t ny = npix_out * v->out_cs, ny2 = npix_out * (size_t)v->out2_cs;
+    VC_TRY(guarded_elems(mem, gy, y, ny, PREC_BF16));
+    if (v->split > 0) VC_TRY(guarded_elems(mem, gy2, y2, ny2, PREC_BF16));
+    ConvP c{}, q{};
+    c.in = dx; c.w = p3.d_w; c.bias = p3.d_b; c.out = gmid.out();
+    c.B = d->b; c.H = d->h; c.W = d->w; c.Cin = p3.cin_eff; c.in_cs = v->in_cs; c.in_co = v->in_co;
+    c.Ho = Ho; c.Wo = Wo; c.Cout = CO; c.out_cs = CO; c.out_co = 0;
+    c.kh = c.kw = 3; c.sh = c.sw = 2; c.ph = c.pw = 1;
+    c.K = p3.K; c.Kp = p3.Kp; c.act = ACT_SILU; c.res_mode = RES_NONE; c.prec = PREC_BF16;
+    c.act_scale = c.inv_act_scale = 1.0f; c.M = d->b * Ho * Wo; c.cfg = -1;
+    q.in = gmid.out(); q.w = p1.d_w; q.bias = p1.d_b; q.out = gy.out();
+    q.B = d->b; q.H = Ho; q.W = Wo; q.Cin = CO; q.in_cs = CO; q.in_co = 0;
+    q.Ho = Ho; q.Wo = Wo; q.Cout = CO; q.out_cs = v->out_cs; q.out_co = v->out_co;
+    q.kh = q.kw = 1; q.sh = q.sw = 1; q.ph = q.pw = 0;
+    q.K = p1.K; q.Kp = p1.Kp; q.act = ACT_SILU; q.res_mode = RES_NONE; q.prec = PREC_BF16;
+    q.act_scale = q.inv_act_scale = 1.0f; q.M = c.M; q.cfg = -1;
+    if (v->split > 0) { q.split = v->split; q.out2 = gy2.out(); q.out2_cs = v->out2_cs; q.out2_co = v->out2_co; }
+    VC_CHECK(s2halo_pw_applicable(c, q), VC_ERR_ARG, "s2 + pointwise: the fused kernel does not take this pair");
+    VC_TRY(launch_s2halo_pw(c, q, nullptr));
+    VC_CHECK(hipDeviceSynchronize() == hipSuccess, VC_ERR_HIP, "conv3x3s2_halo_kernel failed: %s", hipGetErrorString(hipGetLastError()));
+    {   // the 3x3's own output stays on chip: its buffer still holds the fill (unless the diagnostic VC_S2PW_STORE asks for the store)
+        std::vector<uint8_t> mid(gmid.bytes);
+        VC_TRY(gmid.read_back(mid.data(), "conv3x3s2_halo_kernel (the 3x3's own output)"));
+        const bool also_store = getenv("VC_S2PW_STORE") && atoi(getenv("VC_S2PW_STORE")) != 0;
+        for (size_t i = 0; i < mid.size() && !also_store; ++i)
+            VC_CHECK(mid[i] == 0xA5, VC_ERR_HIP, "conv3x3s2_halo_kernel wrote the 3x3's own output (byte %zu)", i);
     }
-    return st;
+    VC_TRY(read_elems(gy, ny, PREC_BF16, y, "conv3x3s2_halo_kernel"));
+    if (v->split > 0) VC_TRY(read_elems(gy2, ny2, PREC_BF16, y2, "conv3x3s2_halo_kernel (second destination)"));
+    return VC_OK;
 }
 
 int vc_letterbox_host(const uint8_t* rgb, int h, int w, int net_h, int net_w, int precision, float* out) {
@@ -820,39 +958,7 @@ int vc_letterbox_host(const uint8_t* rgb, int h, int w, int net_h, int net_w, in
 }
 
 // ---- the pool, resample, layout and cast kernels on host arrays (include/vcount_hip.h) ------------------------------------------------
-// n floats -> elements of `prec` (exact for values the type represents) and back
-static std::vector<uint8_t> to_elems(const float* src, size_t n, int prec) {
-    const int es = elem_size(prec);
-    std::vector<uint8_t> buf(n * es);
-    for (size_t i = 0; i < n; ++i) {
-        if (es == 4) ((float*)buf.data())[i] = src[i];
-        else if (es == 2) ((uint16_t*)buf.data())[i] = f32_to_bf16(src[i]);
-        else buf[i] = f32_to_e4m3(src[i]);
-    }
-    return buf;
-}
-static void from_elems(const std::vector<uint8_t>& buf, size_t n, int prec, float* dst) {
-    const int es = elem_size(prec);
-    for (size_t i = 0; i < n; ++i)
-        dst[i] = es == 4 ? ((const float*)buf.data())[i] : es == 2 ? bf16_to_f32(((const uint16_t*)buf.data())[i]) : e4m3_to_f32(buf[i]);
-}
-static int upload_elems(DevScratch& mem, const float* src, size_t n, int prec, void** dst) {
-    const std::vector<uint8_t> buf = to_elems(src, n, prec);
-    VC_TRY(mem.alloc(dst, buf.size()));
-    VC_HIP(hipMemcpy(*dst, buf.data(), buf.size(), hipMemcpyHostToDevice));
-    return VC_OK;
-}
-// the caller's float array as the guarded device buffer a kernel writes into, and back
-static int guarded_elems(DevScratch& mem, GuardedOut& g, const float* init, size_t n, int prec) {
-    const std::vector<uint8_t> buf = to_elems(init, n, prec);
-    return g.alloc(mem, buf.size(), buf.data());
-}
-static int read_elems(const GuardedOut& g, size_t n, int prec, float* dst, const char* kernel) {
-    std::vector<uint8_t> buf(g.bytes);
-    VC_TRY(g.read_back(buf.data(), kernel));
-    from_elems(buf, n, prec, dst);
-    return VC_OK;
-}
+// (to_elems / upload_elems / guarded_elems / read_elems: above, with the convolution entry points)
 static bool prec_known(int prec, bool fp8_too) { return prec == PREC_F32 || prec == PREC_BF16 || (fp8_too && prec == PREC_FP8); }
 
 int vc_sppf_pool_host(float* buf, int b, int h, int w, int cs, int co, int c, int precision, int form, int* ran_kernel, int* ran_ws) {

@@ -163,7 +163,7 @@ struct ConvP {
     int split, out2_cs, out2_co;
     const int* m_dev;    // optional: the number of valid output pixels lives on the DEVICE (a compacted batch whose size the host does not
                          // know, e.g. the sparse Detect head): the kernel processes min(M, *m_dev) pixels; M bounds the launch.  Only the
-                         // implicit-GEMM family (conv_igemm_kernel) honours it
+                         // implicit-GEMM family (conv_igemm_kernel, without split-K) honours it; the other families refuse it
     // optional (bf16 pointwise convs, conv_igemm_kernel<..., UP>): input channels [0, up_C) are the nearest-neighbour 2 x upsampling of this
     // [B][H/2][W/2] tensor (channel stride up_cs, offset up_co) instead of channels [in_co, in_co + up_C) of `in` (Upsample + Concat folded in)
     const void* in_up;

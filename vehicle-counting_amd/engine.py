@@ -467,6 +467,60 @@ def conv2d(x_nhwc, w_oihw, bias, *, stride=1, pad=0, act=0, res=None, res_mode=0
     return y
 
 
+def _conv_view(view, *, in_cs, out_cs):
+    v = L.ConvView(in_cs=in_cs, in_co=0, out_cs=out_cs, out_co=0, m_valid=-1)
+    for k, val in view.items():
+        if not hasattr(v, k):
+            raise KeyError(k)
+        setattr(v, k, int(val))
+    return v
+
+
+def conv2d_view(x, w_oihw, bias, y, *, view, x_up=None, res=None, y2=None, stride=1, pad=0, act=0, res_mode=0, precision="bf16"):
+    """launch_conv under the views of `view` (a dict of vc_conv_view fields) on WHOLE buffers: x (B, H, W, in_cs), x_up (B, H/2, W/2, up_cs),
+    res (B, Ho, Wo, res_cs); y (B, Ho, Wo, out_cs) and y2 (B, Ho, Wo, out2_cs) are uploaded, launched into and returned as copies.
+    The input channel count is the weights'.  Returns y, or (y, y2) under a split."""
+    x, w, b = L.f32(x), L.f32(w_oihw), L.f32(bias)
+    B, H, W, in_cs = x.shape
+    Co, Ci, kh, kw = w.shape
+    y = L.f32(y).copy()
+    v = _conv_view(view, in_cs=in_cs, out_cs=y.shape[3])
+    d = L.ConvDesc(B, H, W, Ci, Co, kh, kw, stride, pad, act, res_mode if res is not None else 0, L.PREC_ID[precision])
+    xu = L.f32(x_up) if x_up is not None else None
+    r = L.f32(res) if res is not None else None
+    y2 = L.f32(y2).copy() if y2 is not None else None
+    if xu is not None:
+        assert xu.shape == (B, H // 2, W // 2, v.up_cs)
+    if r is not None:
+        assert r.shape == y.shape[:3] + (v.res_cs,)
+    if y2 is not None:
+        assert y2.shape == y.shape[:3] + (v.out2_cs,)
+    try:
+        L.check(L.lib().vc_conv2d_view_host(C.byref(d), C.byref(v), L.ptr(x, C.c_float), L.ptr(xu, C.c_float), L.ptr(w, C.c_float), L.ptr(b, C.c_float),
+                                            L.ptr(r, C.c_float), L.ptr(y, C.c_float), L.ptr(y2, C.c_float)))
+    except L.VcError as err:
+        err.outputs = (y, y2)              # what the refused call left in the output arrays
+        raise
+    return y if y2 is None else (y, y2)
+
+
+def conv_s2_pw(x, w3, b3, w1, b1, y, *, view, y2=None):
+    """launch_s2halo_pw on whole buffers (bf16): 3x3 / s2 / p1 + SiLU to 128 channels over the slice (in_cs, in_co) of x, then on the tile the
+    pointwise 128 -> 128 + SiLU, stored through view's out_* / split / out2_*.  Returns y, or (y, y2) under a split."""
+    x, w3, b3, w1, b1 = L.f32(x), L.f32(w3), L.f32(b3), L.f32(w1), L.f32(b1)
+    B, H, W, in_cs = x.shape
+    Co, Ci, kh, kw = w3.shape
+    y = L.f32(y).copy()
+    v = _conv_view(view, in_cs=in_cs, out_cs=y.shape[3])
+    d = L.ConvDesc(B, H, W, Ci, Co, kh, kw, 2, 1, 1, 0, L.PREC_BF16)
+    y2 = L.f32(y2).copy() if y2 is not None else None
+    if y2 is not None:
+        assert y2.shape == y.shape[:3] + (v.out2_cs,)
+    L.check(L.lib().vc_conv_s2_pw_host(C.byref(d), C.byref(v), L.ptr(x, C.c_float), L.ptr(w3, C.c_float), L.ptr(b3, C.c_float), L.ptr(w1, C.c_float),
+                                       L.ptr(b1, C.c_float), L.ptr(y, C.c_float), L.ptr(y2, C.c_float)))
+    return y if y2 is None else (y, y2)
+
+
 def kalman_initiate(xyah):
     z = L.f64(xyah).reshape(-1, 4)
     m, c = np.zeros((len(z), 8)), np.zeros((len(z), 8, 8))
