@@ -101,6 +101,23 @@ int vc_engine_finalize(vc_engine* e); /* packs + uploads weights; detector/ReID 
  * (conf > min_confidence, then DeepSORT's NMS per class, deep_sort.py:31-37).  The reference embeds every box first and drops the rest
  * afterwards; a dropped box never becomes a Detection, so its feature is never read and the rows are the same.  0 embeds every box. */
 int vc_engine_set_option(vc_engine* e, const char* name, int value);
+/* Class filter and label map of the detector.  networks/yolo.py:20,64: get_model hands the keys of args.mapping_dict to
+ * YoloBackbone as filter_classes -> model.classes, which non_max_suppression applies behind the conf tests and in front of the max_nms trim,
+ * the NMS and the max_det cut; modules/detect.py:41-46: ImageDetect.run relabels what is left.  label_of_class[c] = -1
+ * drops every detection whose best class over ALL classes is c (nothing is reassigned), l >= 0 is the label the detection leaves the engine
+ * with, on every detect path (vc_detect, the stream path, vc_stream_embed).  Labels need not be dense (n_labels = largest + 1) and classes
+ * may share one; the NMS separates ORIGINAL classes, so overlapping boxes of two classes with one label both survive, as they do in the
+ * reference's relabel after the NMS.  max_candidates is judged on the unfiltered candidates; vc_stream_inject rows are taken as given;
+ * vc_detect_debug_pred / _layer are unchanged.  NULL clears the map.  n != num_classes, an entry outside [-1, n) or no entry >= 0:
+ * VC_ERR_ARG before any device call; an engine without a (finalized) detector, or a stream path that holds a pending submission or an
+ * outstanding batch: VC_ERR_STATE.  The table is copied on the detector stream from a pinned copy the engine owns. */
+int vc_engine_set_class_map(vc_engine* e, const int* label_of_class, int n);
+/* The map in force -- model.classes (networks/yolo.py:64) and the relabel (modules/detect.py:41-46) as one table; the identity and
+ * n_labels = num_classes when none is set.  n must be num_classes. */
+int vc_engine_class_map(const vc_engine* e, int* label_of_class, int n, int* n_labels);
+/* The rules of such a table alone (what vc_engine_set_class_map checks of filter_classes, networks/yolo.py:20), pure host code:
+ * n_labels = largest label + 1, n_kept = classes with a label (both nullable). */
+int vc_class_map_check_host(const int* label_of_class, int n, int* n_labels, int* n_kept);
 
 /* ---- detect: ImageDetect.run ------------------------------------------------------------------ */
 /* rgb[i]: H[i] x W[i] x 3 uint8 RGB.  out_det: n * max_det * 6 floats [x1,y1,x2,y2,conf,cls] in source pixels
@@ -510,6 +527,14 @@ int vc_nms_host(const float* boxes4, const float* conf, const int* cls, int n, f
  * geom4 == NULL or net_h <= 0: network pixels, no rescale and no clamp, like vc_nms_host).  out6: [b][max_det][6], out_n: [b]. */
 int vc_nms_batch_host(const float* boxes4, const float* conf, const int* cls, const int* counts, int b, float iou, int max_det, int max_cand,
                       const int* geom4, float* out6, int* out_n);
+/* vc_nms_batch_host with the class filter in front and the relabel behind, the order of non_max_suppression(classes=...) under
+ * networks/yolo.py:64 and of modules/detect.py:41-46 (vc_engine_set_class_map: cand_class_filter_kernel, the three
+ * NMS kernels on the ORIGINAL classes, det_relabel_kernel), on the same device buffers; validated before any device call.  The class column
+ * of out6 holds labels.  kept_count[f] = candidates of frame f the filter kept, kept_idx + f * max_cand (nullable) their positions in
+ * ascending order (the filter is stable).  Rows and positions lie between guard blocks: a write outside them is VC_ERR_HIP. */
+int vc_class_filter_nms_host(const float* boxes4, const float* conf, const int* cls, const int* counts, int b, const int* label_of_class,
+                             int n_classes, float iou, int max_det, int max_cand, const int* geom4, float* out6, int* out_n, int* kept_count,
+                             int* kept_idx /* b * max_cand, nullable */);
 /* The detector's tail on explicit logits, without an engine or a network: decode_kernel<f32 | bf16>, or head_compact_kernel +
  * decode_sparse_kernel wired as the bf16 engine wires them (objectness plane = channels a * (nc + 5) + 4 of the logits, the head conv's
  * input rows = the dense logits themselves, cap = every pixel of the batch).  The bf16 and the sparse mode round the logits to bf16. */

@@ -103,6 +103,9 @@ SIGNATURES = {
     "vc_engine_set_anchors": [_vp, _pf],
     "vc_engine_finalize": [_vp],
     "vc_engine_set_option": [_vp, C.c_char_p, _i],
+    "vc_engine_set_class_map": [_vp, _pi, _i],
+    "vc_engine_class_map": [_vp, _pi, _i, _pi],
+    "vc_class_map_check_host": [_pi, _i, _pi, _pi],
     "vc_engine_sync": [_vp],
     "vc_detect": [_vp, _P(_vp), _pi, _pi, _i, _pf, _pi],
     "vc_detect_debug_shape": [_vp, _pi, _pi, _pi],
@@ -196,6 +199,7 @@ SIGNATURES = {
     "vc_zone_filter_host": [_pd, _i, _pl, _i, _pu8],
     "vc_nms_host": [_pf, _pf, _pi, _i, _f, _i, _i, _pf, _pi],
     "vc_nms_batch_host": [_pf, _pf, _pi, _pi, _i, _f, _i, _i, _pi, _pf, _pi],
+    "vc_class_filter_nms_host": [_pf, _pf, _pi, _pi, _i, _pi, _i, _f, _i, _i, _pi, _pf, _pi, _pi, _pi],
     "vc_decode_host": [_P(DecodeDesc), _P(_pf), _pi, _pi, _pf, _pf, _pi, _pi, _pi, _P(_pi), _f, _i, _pi, _pf, _pi],
     "vc_sppf_pool_host": [_pf, _i, _i, _i, _i, _i, _i, _i, _i, _pi, _pi],
     "vc_upsample2x_host": [_pf, _i, _i, _i, _i, _pf, _i, _i, _i],

@@ -181,6 +181,12 @@ struct vc_engine {
     float* d_geom = nullptr;                     // [max_batch][5] gain, padw, padh, src_w, src_h
     float* d_pred_debug = nullptr;
     bool want_pred_debug = false;
+    // class filter and label map (class_filter.hip): empty = no map, and yolo_forward launches what it always did; the pinned and the
+    // device table are allocated by the first vc_engine_set_class_map
+    std::vector<int> class_map;                  // [num_classes] label of each class, -1 = dropped
+    int n_labels = 0;
+    int* h_class_map = nullptr;
+    int* d_class_map = nullptr;
     int last_B = 0, last_nh = 0, last_nw = 0, last_ntotal = 0;
     // letterbox folded into the stem (stem_direct.hip, U8): source of the running / last detector pass; the letterboxed tensor
     // ybuf["in"] is then only produced on demand (vc_detect_debug_layer(-1))
@@ -391,6 +397,8 @@ int sized_dims_resolve(const vc_frame_dims* dims, int b, int img_size, SizedDims
 size_t yuv_batch_bytes(const YuvGeom& g, int b);
 int launch_yuv_to_bgr(const YuvGeom& g, const uint8_t* src, uint8_t* dst, int b, hipStream_t s);
 int launch_bgr_to_yuv(const YuvGeom& g, const uint8_t* src_bgr, uint8_t* dst_yuv, int b, hipStream_t s);
+// class_filter.hip: the rules of a class map (pure host code): n entries in [-1, n), at least one >= 0; n_labels = largest label + 1
+int class_map_check(const int* label_of_class, int n, int* n_labels, int* n_kept);
 // overlay.hip: the checks of vc_overlay on the host lists, and overlay_kernel over device-resident lists on `s` (no host wait)
 int overlay_check_lists(int b, const int32_t* prims12, const int32_t* frame_first);
 int launch_overlay(uint8_t* frames_dev, int b, int h, int w, const void* d_prims, const int* d_first, hipStream_t s);

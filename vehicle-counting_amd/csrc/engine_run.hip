@@ -393,7 +393,13 @@ int yolo_forward(vc_engine* e, int B, int nh, int nw) {
         ProfScope ps(e, VC_PROF_DETECT_AUX, 0, 0, ds);
         VC_TRY(launch_decode(lv, 3, B, nc, e->cfg.conf_thres, e->cfg.max_candidates, e->post, dbg, base, ds));
     }
+    // class map set: the dropped classes leave the candidates here, where non_max_suppression applies `classes` -- behind the conf tests, in
+    // front of the sort, the NMS and the max_det cut.  The three decodes fill the same buffers; overflow was judged on the unfiltered count.
+    const bool mapped = !e->class_map.empty();
+    if (mapped) { ProfScope ps(e, VC_PROF_DETECT_AUX, 0, 0, ds); VC_TRY(launch_cand_class_filter(B, nc, e->cfg.max_candidates, e->d_class_map, e->post, ds)); }
     { ProfScope ps(e, VC_PROF_DETECT_AUX, 0, 0, ds); VC_TRY(launch_nms(B, e->cfg.max_candidates, e->cfg.max_det, e->cfg.iou_thres, e->d_geom, e->post, ds)); }
+    // (the NMS offset its boxes by the ORIGINAL class; the rows leave with the label, modules/detect.py:41-46)
+    if (mapped) { ProfScope ps(e, VC_PROF_DETECT_AUX, 0, 0, ds); VC_TRY(launch_det_relabel(B, nc, e->cfg.max_det, e->d_class_map, e->post, ds)); }
     return VC_OK;
 }
 

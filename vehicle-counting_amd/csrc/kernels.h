@@ -78,6 +78,12 @@ struct ScaleGeom { int net_h, net_w, src_h, src_w; };
 void scale_geom_host(const ScaleGeom& g, float out5[5]);   // gain, padw, padh, src_w, src_h as float32
 // geom_dev: device [B][5] from scale_geom_host
 int launch_nms(int B, int max_cand, int max_det, float iou, const float* geom_dev, DetectPostBuffers& pb, hipStream_t s);
+// Class filter and label map (class_filter.hip).  label_of_dev: device int[nc], -1 = the class is dropped, l >= 0 = its label.
+// launch_cand_class_filter compacts cand_* of every frame in place (stable; cand_count becomes the kept count, overflow stays) between the
+// decode and launch_nms; launch_det_relabel replaces the class column of the rows launch_nms wrote by the label.
+#define VC_CLASS_MAP_MAX 4096     // classes a map may have: the filter keeps the table in LDS
+int launch_cand_class_filter(int B, int nc, int max_cand, const int* label_of_dev, DetectPostBuffers& pb, hipStream_t s);
+int launch_det_relabel(int B, int nc, int max_det, const int* label_of_dev, DetectPostBuffers& pb, hipStream_t s);
 
 // ---- ReID side -------------------------------------------------------------------------------------
 // frames: F x H x W x 3 u8 BGR.  crop[i] = (frame, x1, y1, x2, y2) end-exclusive int corners.

@@ -734,8 +734,8 @@ int post_alloc(DevScratch& mem, DetectPostBuffers& pb, float** geom, int B, int 
     return VC_OK;
 }
 
-// launch_nms over filled candidate buffers + download.  out_n[f] is the device's count: -1 for a frame whose overflow flag is set.
-int post_nms(DetectPostBuffers& pb, float* geom, int B, int max_cand, int max_det, float iou, const int* geom4, float* out6, int* out_n) {
+// the scale_coords scalars of every frame (geom4[f] = {net_h, net_w, src_h, src_w}; null or net_h <= 0: network pixels, no rescale, no clamp)
+int post_geom(float* geom, int B, const int* geom4) {
     std::vector<float> hg((size_t)B * 5);
     for (int f = 0; f < B; ++f) {
         float* g = &hg[(size_t)f * 5];
@@ -743,6 +743,12 @@ int post_nms(DetectPostBuffers& pb, float* geom, int B, int max_cand, int max_de
         else { g[0] = 1.f; g[1] = 0.f; g[2] = 0.f; g[3] = 1e30f; g[4] = 1e30f; }
     }
     VC_HIP(hipMemcpy(geom, hg.data(), hg.size() * 4, hipMemcpyHostToDevice));
+    return VC_OK;
+}
+
+// launch_nms over filled candidate buffers + download.  out_n[f] is the device's count: -1 for a frame whose overflow flag is set.
+int post_nms(DetectPostBuffers& pb, float* geom, int B, int max_cand, int max_det, float iou, const int* geom4, float* out6, int* out_n) {
+    VC_TRY(post_geom(geom, B, geom4));
     VC_TRY(launch_nms(B, max_cand, max_det, iou, geom, pb, nullptr));
     VC_CHECK(hipDeviceSynchronize() == hipSuccess, VC_ERR_HIP, "nms kernels failed: %s", hipGetErrorString(hipGetLastError()));
     VC_HIP(hipMemcpy(out_n, pb.det_count, (size_t)B * 4, hipMemcpyDeviceToHost));
@@ -771,6 +777,52 @@ int vc_nms_batch_host(const float* boxes4, const float* conf, const int* cls, co
     VC_HIP(hipMemcpy(pb.cand_idx, idx.data(), mc * 4, hipMemcpyHostToDevice));
     VC_HIP(hipMemcpy(pb.cand_count, counts, (size_t)b * 4, hipMemcpyHostToDevice));
     return post_nms(pb, geom, b, max_cand, max_det, iou, geom4, out6, out_n);
+}
+
+// vc_nms_batch_host with cand_class_filter_kernel in front of the three NMS kernels and det_relabel_kernel behind them, on the same device
+// buffers (class_filter.hip).  The rows and the compacted cand_idx (= the kept candidates' positions) lie between guard blocks.
+int vc_class_filter_nms_host(const float* boxes4, const float* conf, const int* cls, const int* counts, int b, const int* label_of_class, int n_classes,
+                             float iou, int max_det, int max_cand, const int* geom4, float* out6, int* out_n, int* kept_count, int* kept_idx) {
+    VC_CHECK(boxes4 && conf && cls && counts && out6 && out_n && kept_count && b >= 1, VC_ERR_ARG, "bad argument");
+    VC_TRY(class_map_check(label_of_class, n_classes, nullptr, nullptr));
+    VC_CHECK(nms_capacity_ok(max_cand, max_det), VC_ERR_ARG, "max_cand must be a multiple of 64 in [64,8192], max_det >= 1");
+    for (int f = 0; f < b; ++f) {
+        VC_CHECK(counts[f] >= 0 && counts[f] <= max_cand, VC_ERR_ARG, "frame %d: count %d outside [0, max_cand]", f, counts[f]);
+        for (int i = 0; i < counts[f]; ++i) {
+            const int c = cls[(size_t)f * max_cand + i];
+            VC_CHECK(c >= 0 && c < n_classes, VC_ERR_ARG, "frame %d candidate %d: class %d outside [0, %d)", f, i, c, n_classes);
+        }
+    }
+    DevScratch mem;
+    DetectPostBuffers pb{};
+    float* geom = nullptr;
+    int* d_map = nullptr;
+    VC_TRY(post_alloc(mem, pb, &geom, b, max_cand, max_det, true));
+    const size_t mc = (size_t)b * max_cand;
+    std::vector<int> idx(mc);
+    for (size_t i = 0; i < mc; ++i) idx[i] = (int)(i % max_cand);
+    GuardedOut gdet, gidx;
+    VC_TRY(gdet.alloc(mem, (size_t)b * max_det * 24));
+    VC_TRY(gidx.alloc(mem, mc * 4, (const uint8_t*)idx.data()));
+    pb.det = (float*)gdet.out();
+    pb.cand_idx = (int*)gidx.out();
+    VC_TRY(mem.alloc(&d_map, (size_t)n_classes * 4));
+    VC_HIP(hipMemcpy(d_map, label_of_class, (size_t)n_classes * 4, hipMemcpyHostToDevice));
+    VC_HIP(hipMemcpy(pb.cand_box, boxes4, mc * 16, hipMemcpyHostToDevice));
+    VC_HIP(hipMemcpy(pb.cand_conf, conf, mc * 4, hipMemcpyHostToDevice));
+    VC_HIP(hipMemcpy(pb.cand_cls, cls, mc * 4, hipMemcpyHostToDevice));
+    VC_HIP(hipMemcpy(pb.cand_count, counts, (size_t)b * 4, hipMemcpyHostToDevice));
+    VC_TRY(post_geom(geom, b, geom4));
+    VC_TRY(launch_cand_class_filter(b, n_classes, max_cand, d_map, pb, nullptr));
+    VC_TRY(launch_nms(b, max_cand, max_det, iou, geom, pb, nullptr));
+    VC_TRY(launch_det_relabel(b, n_classes, max_det, d_map, pb, nullptr));
+    VC_CHECK(hipDeviceSynchronize() == hipSuccess, VC_ERR_HIP, "class filter / nms kernels failed: %s", hipGetErrorString(hipGetLastError()));
+    VC_HIP(hipMemcpy(out_n, pb.det_count, (size_t)b * 4, hipMemcpyDeviceToHost));
+    VC_HIP(hipMemcpy(kept_count, pb.cand_count, (size_t)b * 4, hipMemcpyDeviceToHost));
+    VC_TRY(gdet.read_back((uint8_t*)out6, "nms_scan_kernel / det_relabel_kernel"));
+    VC_TRY(gidx.read_back((uint8_t*)idx.data(), "cand_class_filter_kernel"));
+    if (kept_idx) memcpy(kept_idx, idx.data(), mc * 4);
+    return VC_OK;
 }
 
 // Greedy class-offset NMS on an explicit candidate list (reference order), through the same three kernels the

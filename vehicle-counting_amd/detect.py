@@ -90,6 +90,11 @@ class ImageDetect:
             self.included_classes = list(self.mapping_dict.keys())
             ids = sorted(np.unique(list(self.mapping_dict.values())))
             self.class_names = [self.class_names[i] for i in ids]
+            # networks/yolo.py:20,64: get_model hands the keys to the detector as filter_classes -> model.classes, so the other classes
+            # leave in front of the NMS and the max_det cut.  Identity labels: run() below still sees class ids and relabels as before.
+            if isinstance(self.mapping_dict, dict) and self.included_classes and \
+                    all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) for k in self.included_classes):
+                engine.set_class_map({int(k): int(k) for k in self.included_classes})
 
     @staticmethod
     def _marshal(det):

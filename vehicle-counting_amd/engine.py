@@ -92,6 +92,33 @@ class Engine:
         L.check(L.lib().vc_stream_crop_stats(self._h, C.byref(boxes), C.byref(crops)))
         return boxes.value, crops.value
 
+    # ---------------------------------------------------------------- class filter and label map
+    def set_class_map(self, classes):
+        """Restrict the detector to some classes and relabel them, on every detect path (`vc_engine_set_class_map`: the filter runs on
+        the device in front of the NMS, where upstream's `classes` argument applies; the relabel behind it).  `classes`: a list of
+        class ids (list order gives labels 0..), a dict {class: label} (labels may repeat and need not be dense), or None to clear."""
+        if classes is None:
+            L.check(L.lib().vc_engine_set_class_map(self._h, None, 0))
+            return
+        t = class_table(self.cfg.num_classes, classes)
+        L.check(L.lib().vc_engine_set_class_map(self._h, L.ptr(t, C.c_int), len(t)))
+
+    def _class_map(self):
+        nc = self.cfg.num_classes
+        t, n = np.zeros(nc, np.int32), C.c_int()
+        L.check(L.lib().vc_engine_class_map(self._h, L.ptr(t, C.c_int), nc, C.byref(n)))
+        return t, n.value
+
+    @property
+    def class_map(self):
+        """label_of_class [num_classes] int32 (-1 = dropped); the identity when no map is set."""
+        return self._class_map()[0]
+
+    @property
+    def num_labels(self):
+        """Labels a detection can leave the engine with (largest label + 1; num_classes when no map is set): the tracker fan-out."""
+        return self._class_map()[1]
+
     # ---------------------------------------------------------------- detect (AutoShape forward)
     def detect(self, imgs_rgb):
         """list of HxWx3 uint8 RGB -> list of (n,6) float32 [x1,y1,x2,y2,conf,cls] in source pixels."""
@@ -921,6 +948,54 @@ def nms_batch(boxes, conf, cls, counts, iou=0.45, max_det=300, max_cand=4096, ge
     L.check(L.lib().vc_nms_batch_host(L.ptr(bx, C.c_float), L.ptr(cf, C.c_float), L.ptr(cl, C.c_int), L.ptr(cnt, C.c_int), b, iou, max_det, max_cand,
                                       L.ptr(g, C.c_int), L.ptr(out, C.c_float), L.ptr(n_out, C.c_int)))
     return out, n_out
+
+
+def class_table(nc, classes):
+    """label_of_class [nc] int32 for `vc_engine_set_class_map`: -1 = dropped.  `classes`: a list of class ids (list order gives labels
+    0, 1, ...) or a dict {class: label}.  A class outside [0, nc), a class named twice, a label outside [0, nc) or an empty selection
+    raises ValueError."""
+    pairs = list(classes.items()) if isinstance(classes, dict) else [(c, l) for l, c in enumerate(classes)]
+    t = np.full(int(nc), -1, np.int32)
+    for c, l in pairs:
+        if isinstance(c, bool) or isinstance(l, bool) or int(c) != c or int(l) != l:
+            raise ValueError(f"class map: class {c!r} -> label {l!r}: ids must be integers")
+        c, l = int(c), int(l)
+        if not 0 <= c < nc:
+            raise ValueError(f"class map: class {c} outside [0, {nc})")
+        if not 0 <= l < nc:
+            raise ValueError(f"class map: label {l} of class {c} outside [0, {nc})")
+        if t[c] >= 0:
+            raise ValueError(f"class map: class {c} named twice")
+        t[c] = l
+    if not len(pairs):
+        raise ValueError("class map: no class selected (None clears the map)")
+    return t
+
+
+def class_map_check(table):
+    """vc_class_map_check_host: (n_labels, n_kept) of a label_of_class table, VcError(VC_ERR_ARG) for a bad one.  Pure host code."""
+    t = np.ascontiguousarray(table, dtype=np.int32).reshape(-1)
+    nl, nk = C.c_int(), C.c_int()
+    L.check(L.lib().vc_class_map_check_host(L.ptr(t, C.c_int), len(t), C.byref(nl), C.byref(nk)))
+    return nl.value, nk.value
+
+
+def class_filter_nms(boxes, conf, cls, counts, table, iou=0.45, max_det=300, max_cand=4096, geoms=None):
+    """vc_class_filter_nms_host: `nms_batch` with cand_class_filter_kernel in front and det_relabel_kernel behind, `table` = label_of_class.
+    Returns ([b][max_det][6] rows with labels in the class column, [b] counts, [b] kept candidates, [b][max_cand] their positions)."""
+    b = len(counts)
+    bx, cf, cl = np.zeros((b, max_cand, 4), np.float32), np.zeros((b, max_cand), np.float32), np.zeros((b, max_cand), np.int32)
+    for f, n in enumerate(counts):
+        bx[f, :n], cf[f, :n], cl[f, :n] = np.reshape(boxes[f], (-1, 4))[:n], np.reshape(conf[f], -1)[:n], np.reshape(cls[f], -1)[:n]
+    cnt = np.ascontiguousarray(counts, dtype=np.int32)
+    t = np.ascontiguousarray(table, dtype=np.int32).reshape(-1)
+    g = _geom_array(geoms, b)
+    out, n_out = np.zeros((b, max_det, 6), np.float32), np.zeros(b, np.int32)
+    kept, kept_idx = np.zeros(b, np.int32), np.zeros((b, max_cand), np.int32)
+    L.check(L.lib().vc_class_filter_nms_host(L.ptr(bx, C.c_float), L.ptr(cf, C.c_float), L.ptr(cl, C.c_int), L.ptr(cnt, C.c_int), b, L.ptr(t, C.c_int), len(t),
+                                             iou, max_det, max_cand, L.ptr(g, C.c_int), L.ptr(out, C.c_float), L.ptr(n_out, C.c_int), L.ptr(kept, C.c_int),
+                                             L.ptr(kept_idx, C.c_int)))
+    return out, n_out, kept, kept_idx
 
 
 def decode(logits, nc, strides, anchors, conf=0.25, max_cand=4096, mode="f32", nms=None):

@@ -138,13 +138,24 @@ class YuvFrameSink:
 
 
 class CountingPipeline:
-    def __init__(self, args, config, cam_config, engine=None, class_names=None, synthetic=False):
+    def __init__(self, args, config, cam_config, engine=None, class_names=None, synthetic=False, classes=None):
+        """classes: the detector's class filter and label map (`Engine.set_class_map`: a list of class ids, labelled 0.. in list order,
+        or a dict {class: label}).  Every driver then runs one tracker per LABEL and counts per label; `class_names` becomes one name
+        per label, that of the lowest class mapped to it."""
         # the ReID checkpoint of the reference's cam_configs.yaml (`checkpoint: .../ckpt.t7`, handed to every DeepSort at
         # modules/__init__.py:36) becomes the engine's ReID parameters -- one engine owns both networks
         ck = cam_config.get("checkpoint") if isinstance(cam_config, dict) else getattr(cam_config, "checkpoint", None)
         self.detector = ImageDetect(args, config, engine=engine, class_names=class_names, synthetic=synthetic, reid_checkpoint=ck)
         self.engine = self.detector.engine
         self.class_names = self.detector.class_names
+        if classes is not None:
+            self.engine.set_class_map(classes)
+            table, n_labels = self.engine.class_map, self.engine.num_labels
+            names = [f"label{l}" for l in range(n_labels)]                # a label no class maps to keeps a placeholder: it never occurs
+            for c in range(len(table) - 1, -1, -1):
+                if table[c] >= 0:
+                    names[table[c]] = self.class_names[c]
+            self.class_names = names
         self.saved_path = getattr(args, "output_path", None)
         self.cam_config = cam_config
         self.config = config
