@@ -482,6 +482,35 @@ int vc_conv2d_view_host(const vc_conv_desc* d, const vc_conv_view* v, const floa
  * out_cs / out_co / split / out2_*: y, y2 as above.  The 3x3's own output is never written and not returned. */
 int vc_conv_s2_pw_host(const vc_conv_desc* d, const vc_conv_view* v, const float* x, const float* w, const float* bias, const float* w_pw,
                        const float* bias_pw, float* y, float* y2);
+/* The fused block kernels (c3_fused_kernel, bneck_fused_kernel<false / true>, reid_block_fused_kernel; bf16) as ONE launch on host arrays,
+ * without an engine.  Each entry point builds the ConvP chain the engine's plan builds for the block and calls the block's launcher, so
+ * the launcher's own applicability function decides; its quiet refusal comes back as VC_ERR_ARG with an empty message and leaves every
+ * array as passed.  A channel slice is (cs, co) as above; arrays are whole buffers at full channel stride, converted element by element
+ * to bf16 (NaN stays NaN), in AND out: x too is launched on between guard blocks and read back, so that elements no launch may touch
+ * can be compared by value.  Tensors the fused kernel keeps on chip (C3: y1, b1, [m | y2]; Bottleneck: b1, and m under cv3; ReID: t)
+ * live in buffers of the entry point's own; a fused launch that writes one of them, or a guard block, is VC_ERR_HIP. */
+typedef struct vc_fused_view {
+    int in_cs, in_co;                /* the block's input: channels [in_co, in_co + 64) of x */
+    int out_cs, out_co;              /* C3: out; ReID: y; Bottleneck: m -- under cv3 y is the concat buffer [m | y2]: m is NOT written
+                                        and channels [out_co + 64, out_co + 128) hold y2 */
+    int z_cs, z_co;                  /* Bottleneck under cv3: cv3's output, channels [z_co, z_co + 128) of z */
+    int out_buf;                     /* 0: y is a buffer of its own; 1: the (out_cs = in_cs, out_co) slice lies in x's buffer, y is not used */
+    int z_buf;                       /* 0: z is a buffer of its own; 1: cv3 stores into x's buffer, 2: into y's (z_cs = that buffer's stride) */
+    int res;                         /* Bottleneck: with the shortcut */
+    int cv3;                         /* Bottleneck: the CV3 instance (w3 [128][128], b3, z) */
+    int split;                       /* C3: the channel split of the cv1 | cv2 launch; 0 = 32, what the block has (anything else breaks the chain) */
+    int unfused;                     /* 1: the SAME chain through launch_conv, one launch per convolution (VC_CONV_CFG, VC_CONV_STRICT as for
+                                        vc_conv2d_host); the intermediates are then written, m under cv3 included */
+    int grid;                        /* > 0: at most this many workgroups, which then walk all tiles or crops; 0 = the product's grid */
+} vc_fused_view;
+/* C3(64 -> 64, n = 1, shortcut): x [b][h][w][in_cs], w12 [64][64] = cv1 over cv2, wm1 [32][32], wm2 [32][32][3][3], w3 [64][64], y [b][h][w][out_cs] */
+int vc_c3_fused_host(int b, int h, int w, const vc_fused_view* v, float* x, const float* w12, const float* b12, const float* wm1, const float* bm1,
+                     const float* wm2, const float* bm2, const float* w3, const float* b3, float* y);
+/* Bottleneck(64 -> 64, e = 1): w1 [64][64], w2 [64][64][3][3]; w3 / b3 / z may be NULL without cv3 */
+int vc_bneck_fused_host(int b, int h, int w, const vc_fused_view* v, float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                        const float* w3, const float* b3, float* y, float* z);
+/* ReID BasicBlock(64 -> 64) on k maps of h x w (the kernel takes 25 x 25): w1, w2 [64][64][3][3] */
+int vc_reid_block_fused_host(int k, int h, int w, const vc_fused_view* v, float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* y);
 int vc_kalman_initiate_host(const double* xyah, int n, double* mean8, double* cov64);
 int vc_kalman_predict_host(double* mean8, double* cov64, int n);
 int vc_kalman_update_host(double* mean8, double* cov64, const double* z4, int n);

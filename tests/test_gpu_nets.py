@@ -137,7 +137,9 @@ def test_embed_crops(frames, precision):
 @pytest.mark.parametrize("hw", [(640, 640), (360, 640), (416, 352)])
 def test_c3_fused_bit_identical(hw):
     """c3_fused.hip (the first C3 block in one kernel: y1, y2, b1, m in LDS) against the four launches it replaces: the block's output
-    (layer 2) identical bit for bit, also where tiles hang over the right / bottom edge (H/4 not a multiple of 8, W/4 not of 16)."""
+    (layer 2) identical bit for bit, also where tiles hang over the right edge (88 columns: W/4 not a multiple of 16).  Through the
+    engine H/4 is always a multiple of 8 (160, 96, 104 rows here): tiles over the bottom edge, maps below one tile and other slices are
+    tests/test_gpu_fused_blocks.py's, one launch at a time."""
     H, W = hw
     nc = 8
     sd = synth_yolo("yolov5s", nc=nc, seed=1702, det_scale=4.0, obj_shift=0.0)

@@ -56,6 +56,13 @@ class ConvView(C.Structure):
                 ("m_valid", C.c_int), ("up_c", C.c_int), ("up_cs", C.c_int), ("up_co", C.c_int)]
 
 
+class FusedView(C.Structure):
+    """vc_fused_view: slices, buffer sharing and switches of vc_c3_fused_host / vc_bneck_fused_host / vc_reid_block_fused_host."""
+    _fields_ = [("in_cs", C.c_int), ("in_co", C.c_int), ("out_cs", C.c_int), ("out_co", C.c_int), ("z_cs", C.c_int), ("z_co", C.c_int),
+                ("out_buf", C.c_int), ("z_buf", C.c_int), ("res", C.c_int), ("cv3", C.c_int), ("split", C.c_int), ("unfused", C.c_int),
+                ("grid", C.c_int)]
+
+
 class YuvDesc(C.Structure):
     """vc_yuv_desc: byte geometry of 4:2:0 frames, 0 = tightly packed."""
     _fields_ = [("format", C.c_int), ("matrix", C.c_int), ("full_range", C.c_int), ("pitch_y", C.c_int), ("pitch_c", C.c_int),
@@ -187,6 +194,9 @@ SIGNATURES = {
     "vc_conv2d_host": [_P(ConvDesc), _pf, _pf, _pf, _pf, _pf],
     "vc_conv2d_view_host": [_P(ConvDesc), _P(ConvView), _pf, _pf, _pf, _pf, _pf, _pf, _pf],
     "vc_conv_s2_pw_host": [_P(ConvDesc), _P(ConvView), _pf, _pf, _pf, _pf, _pf, _pf, _pf],
+    "vc_c3_fused_host": [_i, _i, _i, _P(FusedView), _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf],
+    "vc_bneck_fused_host": [_i, _i, _i, _P(FusedView), _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf],
+    "vc_reid_block_fused_host": [_i, _i, _i, _P(FusedView), _pf, _pf, _pf, _pf, _pf, _pf],
     "vc_kalman_initiate_host": [_pd, _i, _pd, _pd],
     "vc_kalman_predict_host": [_pd, _pd, _i],
     "vc_kalman_update_host": [_pd, _pd, _pd, _i],

@@ -387,7 +387,8 @@ static int bneck_grid_cap(int cus) {
     return forced > 0 ? forced : cus - cus / 8;
 }
 
-int launch_bneck_cv3_fused(const ConvP& pm1, const ConvP& pm2, const ConvP& p3, hipStream_t s) {
+// grid_cap > 0 (tests, vc_bneck_fused_host): at most that many workgroups; 0 = bneck_grid_cap alone
+int launch_bneck_cv3_fused(const ConvP& pm1, const ConvP& pm2, const ConvP& p3, hipStream_t s, int grid_cap) {
     if (!bneck_cv3_fused_applicable(pm1, pm2, p3)) return VC_ERR_ARG;
     BnArgs a{};
     a.w1 = (const uint4*)pm1.w; a.w2 = (const uint4*)pm2.w; a.b1 = pm1.bias; a.b2 = pm2.bias;
@@ -404,7 +405,8 @@ int launch_bneck_cv3_fused(const ConvP& pm1, const ConvP& pm2, const ConvP& p3, 
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
     a.res = pm2.res_mode == RES_AFTER_ACT ? 1 : 0;
-    const int grid = std::min(ntiles, bneck_grid_cap(cus));
+    int grid = std::min(ntiles, bneck_grid_cap(cus));
+    if (grid_cap > 0) grid = std::min(grid, grid_cap);
     static WgStamps stamps("VC_BN_DBG", "bneck cv3", 1024, 2, 0, 1);
     a.dbg = stamps.next(grid, ntiles, s);
     launch_timed(pm1, bneck_fused_kernel<true>, dim3(grid), dim3(BN_NW * 64), 0, s, a);
@@ -413,7 +415,7 @@ int launch_bneck_cv3_fused(const ConvP& pm1, const ConvP& pm2, const ConvP& p3, 
     return VC_OK;
 }
 
-int launch_bneck_fused(const ConvP& pm1, const ConvP& pm2, hipStream_t s) {
+int launch_bneck_fused(const ConvP& pm1, const ConvP& pm2, hipStream_t s, int grid_cap) {
     if (!bneck_fused_applicable(pm1, pm2)) return VC_ERR_ARG;
     BnArgs a{};
     a.w1 = (const uint4*)pm1.w; a.w2 = (const uint4*)pm2.w; a.b1 = pm1.bias; a.b2 = pm2.bias;
@@ -429,7 +431,8 @@ int launch_bneck_fused(const ConvP& pm1, const ConvP& pm2, hipStream_t s) {
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
         return n;
     }();
-    const int grid = std::min(ntiles, bneck_grid_cap(cus));                // persistent, one workgroup per CU (128 KB of LDS)
+    int grid = std::min(ntiles, bneck_grid_cap(cus));                      // persistent, one workgroup per CU (128 KB of LDS)
+    if (grid_cap > 0) grid = std::min(grid, grid_cap);
     a.res = pm2.res_mode == RES_AFTER_ACT ? 1 : 0;
     static WgStamps stamps("VC_BN_DBG", "bneck", 1024, 2, 0, 1);
     a.dbg = stamps.next(grid, ntiles, s);

@@ -278,7 +278,8 @@ bool c3_fused_applicable(const ConvP& p12, const ConvP& pm1, const ConvP& pm2, c
     return chain && shape && p12.in_cs % 8 == 0 && p12.in_co % 8 == 0 && p3.out_cs % 8 == 0 && p3.out_co % 8 == 0 && p12.Kp >= 64 && pm1.Kp >= 32 && pm2.Kp >= 288 && p3.Kp >= 64;
 }
 
-int launch_c3_fused(const ConvP& p12, const ConvP& pm1, const ConvP& pm2, const ConvP& p3, hipStream_t s) {
+// grid_cap > 0 (tests, vc_c3_fused_host): at most that many workgroups, which then walk all tiles; 0 = the product's grid
+int launch_c3_fused(const ConvP& p12, const ConvP& pm1, const ConvP& pm2, const ConvP& p3, hipStream_t s, int grid_cap) {
     if (!c3_fused_applicable(p12, pm1, pm2, p3)) return VC_ERR_ARG;
     C3Args a{};
     a.w12 = (const uint4*)p12.w; a.wm1 = (const uint4*)pm1.w; a.wm2 = (const uint4*)pm2.w; a.w3 = (const uint4*)p3.w;
@@ -290,7 +291,8 @@ int launch_c3_fused(const ConvP& p12, const ConvP& pm1, const ConvP& pm2, const 
     a.tiles_x = (a.W + C3_TW - 1) / C3_TW; a.tiles_y = (a.H + C3_TH - 1) / C3_TH;
     const int ntiles = a.B * a.tiles_x * a.tiles_y;
     static const int slots_hw = resident_workgroups(c3_fused_kernel<false>, C3_NW * 64);
-    const int grid = std::min(ntiles, std::max(256, slots_hw - conv_slots_reserve() / 2));   // persistent; two workgroups per CU: half the usual number of slots stays free
+    int grid = std::min(ntiles, std::max(256, slots_hw - conv_slots_reserve() / 2));         // persistent; two workgroups per CU: half the usual number of slots stays free
+    if (grid_cap > 0) grid = std::min(grid, grid_cap);
     a.abl = p12.ablate;                                                              // diagnostics only (engine option "c3_ablate", tools/ff_ablate.py)
     static WgStamps stamps("VC_C3_DBG", "c3", 1024, 2, 0, 1);
     a.dbg = stamps.next(grid, ntiles, s);

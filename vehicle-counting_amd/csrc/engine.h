@@ -349,10 +349,11 @@ struct DevScratch {
 struct GuardedOut {
     static constexpr size_t kGuard = 256;
     uint8_t* base = nullptr;
-    size_t bytes = 0;
-    // out_bytes + 2 guard blocks, all 0xA5; with `preload` the output starts as the caller's array
-    int alloc(DevScratch& mem, size_t out_bytes, const uint8_t* preload = nullptr);
-    uint8_t* out() const { return base + kGuard; }
+    size_t bytes = 0, guard = kGuard;
+    // out_bytes + 2 guard blocks, all 0xA5; with `preload` the output starts as the caller's array.  guard_bytes (a multiple of 256): a
+    // caller that knows how far a kernel without its bounds tests would stray (a tile's overhang) asks for blocks that hold all of it
+    int alloc(DevScratch& mem, size_t out_bytes, const uint8_t* preload = nullptr, size_t guard_bytes = kGuard);
+    uint8_t* out() const { return base + guard; }
     int read_back(uint8_t* host_out, const char* kernel) const;      // waits for the null stream; `kernel` names the culprit
 };
 int dev_realloc(vc_engine* e, void** p, size_t bytes);            // frees *p (if it belongs to the engine) and allocates anew

@@ -25,21 +25,22 @@ int dev_alloc(std::vector<void*>& allocs, void** p, size_t bytes) {
     allocs.push_back(*p);
     return VC_OK;
 }
-int GuardedOut::alloc(DevScratch& mem, size_t out_bytes, const uint8_t* preload) {
+int GuardedOut::alloc(DevScratch& mem, size_t out_bytes, const uint8_t* preload, size_t guard_bytes) {
     bytes = out_bytes;
-    VC_TRY(mem.alloc(&base, bytes + 2 * kGuard));
-    VC_HIP(hipMemset(base, 0xA5, bytes + 2 * kGuard));
+    guard = guard_bytes;
+    VC_TRY(mem.alloc(&base, bytes + 2 * guard));
+    VC_HIP(hipMemset(base, 0xA5, bytes + 2 * guard));
     if (preload) VC_HIP(hipMemcpy(out(), preload, bytes, hipMemcpyHostToDevice));
     return VC_OK;
 }
 int GuardedOut::read_back(uint8_t* host_out, const char* kernel) const {
-    uint8_t edge[2 * kGuard];
-    if (hipMemcpy(host_out, out(), bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(edge, base, kGuard, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(edge + kGuard, out() + bytes, kGuard, hipMemcpyDeviceToHost) != hipSuccess) {
+    std::vector<uint8_t> edge(2 * guard);
+    if (hipMemcpy(host_out, out(), bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(edge.data(), base, guard, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(edge.data() + guard, out() + bytes, guard, hipMemcpyDeviceToHost) != hipSuccess) {
         set_error("%s failed: %s", kernel, hipGetErrorString(hipGetLastError()));
         return VC_ERR_HIP;
     }
-    for (size_t i = 0; i < 2 * kGuard; ++i) VC_CHECK(edge[i] == 0xA5, VC_ERR_HIP, "%s wrote outside its output (guard byte %zu)", kernel, i);
+    for (size_t i = 0; i < 2 * guard; ++i) VC_CHECK(edge[i] == 0xA5, VC_ERR_HIP, "%s wrote outside its output (guard byte %zu)", kernel, i);
     return VC_OK;
 }
 // Replace *p (an allocation of this engine, or null) by a fresh block of `bytes`; the old block is freed.  The caller makes sure no
@@ -719,9 +720,9 @@ static int upload_elems(DevScratch& mem, const float* src, size_t n, int prec, v
     return VC_OK;
 }
 // the caller's float array as the guarded device buffer a kernel writes into, and back
-static int guarded_elems(DevScratch& mem, GuardedOut& g, const float* init, size_t n, int prec) {
+static int guarded_elems(DevScratch& mem, GuardedOut& g, const float* init, size_t n, int prec, size_t guard = GuardedOut::kGuard) {
     const std::vector<uint8_t> buf = to_elems(init, n, prec);
-    return g.alloc(mem, buf.size(), buf.data());
+    return g.alloc(mem, buf.size(), buf.data(), guard);
 }
 static int read_elems(const GuardedOut& g, size_t n, int prec, float* dst, const char* kernel) {
     std::vector<uint8_t> buf(g.bytes);
@@ -936,6 +937,171 @@ int vc_conv_s2_pw_host(const vc_conv_desc* d, const vc_conv_view* v, const float
     }
     VC_TRY(read_elems(gy, ny, PREC_BF16, y, "conv3x3s2_halo_kernel"));
     if (v->split > 0) VC_TRY(read_elems(gy2, ny2, PREC_BF16, y2, "conv3x3s2_halo_kernel (second destination)"));
+    return VC_OK;
+}
+
+// ---- the fused block kernels on host arrays (include/vcount_hip.h: vc_fused_view) ------------------------------------------------------
+// Each entry point builds the ConvP chain the engine's plan builds (engine_plan.hip::yolo_c3, reid_build_ops) over buffers of its own and
+// hands it to the block's launcher, whose *_applicable decides as it does in the engine, or -- v->unfused -- to launch_conv one
+// convolution at a time.
+static int host_param(DevScratch& mem, ConvParam& p, const char* name, int O, int I, int k, const float* w, const float* b) {
+    p.name = name; p.O = O; p.I = I; p.kh = p.kw = k; p.set = true;
+    p.w.assign(w, w + (size_t)O * I * k * k);
+    p.b.assign(b, b + O);
+    return pack_and_upload(mem.allocs, p, PREC_BF16);
+}
+// one bf16 convolution (1x1, or 3x3 / pad 1) of a chain, filled as PlanBuilder::conv fills it
+static ConvP chain_conv(const ConvParam& p, const void* in, int in_cs, int in_co, void* out, int out_cs, int out_co, int B, int H, int W, int act) {
+    ConvP c{};
+    c.in = in; c.w = p.d_w; c.bias = p.d_b; c.out = out;
+    c.B = B; c.H = H; c.W = W; c.Cin = p.cin_eff; c.in_cs = in_cs; c.in_co = in_co;
+    c.kh = c.kw = p.kh; c.sh = c.sw = 1; c.ph = c.pw = p.kh / 2;
+    c.Ho = H; c.Wo = W; c.Cout = p.O; c.out_cs = out_cs; c.out_co = out_co;
+    c.K = p.K; c.Kp = p.Kp; c.act = act; c.res_mode = RES_NONE; c.prec = PREC_BF16;
+    c.act_scale = c.inv_act_scale = 1.0f; c.M = B * H * W;
+    c.cfg = getenv("VC_CONV_CFG") ? atoi(getenv("VC_CONV_CFG")) : -1;                // the unfused chain: the tile configuration of every launch
+    return c;
+}
+static int chain_unfused(std::initializer_list<ConvP> chain) {
+    for (const ConvP& c : chain) VC_TRY(launch_conv(c, nullptr));
+    return VC_OK;
+}
+static int chain_finish(int st, const char* kernel) {
+    if (st == VC_OK && hipDeviceSynchronize() != hipSuccess) { set_error("%s failed: %s", kernel, hipGetErrorString(hipGetLastError())); return VC_ERR_HIP; }
+    return st;
+}
+// an intermediate the fused kernel keeps on chip: its buffer (and the guards around it) still hold the fill
+static int still_filled(const GuardedOut& g, const char* kernel, const char* what) {
+    std::vector<uint8_t> h(g.bytes);
+    VC_TRY(g.read_back(h.data(), kernel));
+    for (size_t i = 0; i < h.size(); ++i) VC_CHECK(h[i] == 0xA5, VC_ERR_HIP, "%s wrote %s (byte %zu)", kernel, what, i);
+    return VC_OK;
+}
+static bool fused_shape_ok(int b, int h, int w) { return b >= 1 && h >= 1 && w >= 1 && (long long)b * h * w <= (1 << 22); }
+// Guard blocks that hold every store of an 8 x 16 tile that lost its `y < H` / `x < W` tests: past the last frame's last pixel such a tile
+// reaches less than 7 rows and 16 pixels further (bf16 pixels of cs channels)
+static size_t tile_guard(int w, int cs) { return ((size_t)(8 * w + 16) * cs * 2 + 255) / 256 * 256; }
+// channels [co, co + n) inside a pixel of cs channels
+static bool fused_slice_ok(int cs, int co, int n) { return co >= 0 && cs >= co + n && cs <= 4096; }
+
+int vc_c3_fused_host(int b, int h, int w, const vc_fused_view* v, float* x, const float* w12, const float* b12, const float* wm1, const float* bm1,
+                     const float* wm2, const float* bm2, const float* w3, const float* b3, float* y) {
+    VC_CHECK(v && x && w12 && b12 && wm1 && bm1 && wm2 && bm2 && w3 && b3 && (y || v->out_buf == 1), VC_ERR_ARG, "null argument");
+    set_error("%s", "");                               // the launcher refuses without a message: the caller must not read an older one
+    const int out_cs = v->out_buf == 1 ? v->in_cs : v->out_cs, split = v->split ? v->split : 32;
+    VC_CHECK(fused_shape_ok(b, h, w) && (v->out_buf == 0 || v->out_buf == 1) && v->grid >= 0, VC_ERR_ARG, "c3 fused: bad shape");
+    VC_CHECK(fused_slice_ok(v->in_cs, v->in_co, 64) && fused_slice_ok(out_cs, v->out_co, 64), VC_ERR_ARG, "c3 fused: a slice lies outside its stride");
+    VC_CHECK(split >= 4 && split <= 60 && split % 4 == 0 && (split == 32 || !v->unfused), VC_ERR_ARG, "c3 fused: split %d", split);
+    const size_t npix = (size_t)b * h * w, nx = npix * v->in_cs, ny = npix * out_cs;
+    DevScratch mem;
+    ConvParam P12, PM1, PM2, P3;
+    VC_TRY(host_param(mem, P12, "cv1 | cv2", 64, 64, 1, w12, b12));
+    VC_TRY(host_param(mem, PM1, "m.cv1", 32, 32, 1, wm1, bm1));
+    VC_TRY(host_param(mem, PM2, "m.cv2", 32, 32, 3, wm2, bm2));
+    VC_TRY(host_param(mem, P3, "cv3", 64, 64, 1, w3, b3));
+    GuardedOut gx, gy, gy1, gb1, gcat;                 // gy1 / gb1 / gcat: y1, b1 and [m | y2] of the unfused graph (c3_<idx>.a, .t, .cat)
+    VC_TRY(guarded_elems(mem, gx, x, nx, PREC_BF16, tile_guard(w, v->in_cs)));
+    if (!v->out_buf) VC_TRY(guarded_elems(mem, gy, y, ny, PREC_BF16, tile_guard(w, out_cs)));
+    VC_TRY(gy1.alloc(mem, npix * 32 * 2));
+    VC_TRY(gb1.alloc(mem, npix * 32 * 2));
+    VC_TRY(gcat.alloc(mem, npix * 64 * 2));
+    ConvP p12 = chain_conv(P12, gx.out(), v->in_cs, v->in_co, gy1.out(), 32, 0, b, h, w, ACT_SILU);
+    p12.split = split; p12.out2 = gcat.out(); p12.out2_cs = 64; p12.out2_co = 32;
+    const ConvP pm1 = chain_conv(PM1, gy1.out(), 32, 0, gb1.out(), 32, 0, b, h, w, ACT_SILU);
+    ConvP pm2 = chain_conv(PM2, gb1.out(), 32, 0, gcat.out(), 64, 0, b, h, w, ACT_SILU);
+    pm2.res = gy1.out(); pm2.res_cs = 32; pm2.res_co = 0; pm2.res_mode = RES_AFTER_ACT;
+    const ConvP p3 = chain_conv(P3, gcat.out(), 64, 0, v->out_buf ? gx.out() : gy.out(), out_cs, v->out_co, b, h, w, ACT_SILU);
+    VC_TRY(chain_finish(v->unfused ? chain_unfused({p12, pm1, pm2, p3}) : launch_c3_fused(p12, pm1, pm2, p3, nullptr, v->grid), "c3_fused_kernel"));   // refused: x / y as passed
+    if (!v->unfused) {
+        VC_TRY(still_filled(gy1, "c3_fused_kernel", "y1"));
+        VC_TRY(still_filled(gb1, "c3_fused_kernel", "b1"));
+        VC_TRY(still_filled(gcat, "c3_fused_kernel", "the concat buffer [m | y2]"));
+    }
+    VC_TRY(read_elems(gx, nx, PREC_BF16, x, "c3_fused_kernel (the input buffer)"));
+    if (!v->out_buf) VC_TRY(read_elems(gy, ny, PREC_BF16, y, "c3_fused_kernel"));
+    return VC_OK;
+}
+
+int vc_bneck_fused_host(int b, int h, int w, const vc_fused_view* v, float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                        const float* w3, const float* b3, float* y, float* z) {
+    VC_CHECK(v && x && w1 && b1 && w2 && b2 && (y || v->out_buf == 1), VC_ERR_ARG, "null argument");
+    VC_CHECK(!v->cv3 || (w3 && b3 && (z || v->z_buf != 0)), VC_ERR_ARG, "null argument (cv3)");
+    set_error("%s", "");
+    const char* kernel = v->cv3 ? "bneck_fused_kernel<true>" : "bneck_fused_kernel<false>";
+    const int out_cs = v->out_buf == 1 ? v->in_cs : v->out_cs, z_cs = v->z_buf == 1 ? v->in_cs : v->z_buf == 2 ? out_cs : v->z_cs;
+    VC_CHECK(fused_shape_ok(b, h, w) && (v->out_buf == 0 || v->out_buf == 1) && v->z_buf >= 0 && v->z_buf <= 2 && v->grid >= 0, VC_ERR_ARG, "bneck fused: bad shape");
+    VC_CHECK(fused_slice_ok(v->in_cs, v->in_co, 64) && fused_slice_ok(out_cs, v->out_co, v->cv3 ? 128 : 64) && (!v->cv3 || fused_slice_ok(z_cs, v->z_co, 128)), VC_ERR_ARG,
+             "bneck fused: a slice lies outside its stride");
+    const size_t npix = (size_t)b * h * w, nx = npix * v->in_cs, ny = npix * out_cs, nz = npix * (size_t)z_cs;
+    DevScratch mem;
+    ConvParam P1, P2, P3;
+    VC_TRY(host_param(mem, P1, "m.cv1", 64, 64, 1, w1, b1));
+    VC_TRY(host_param(mem, P2, "m.cv2", 64, 64, 3, w2, b2));
+    if (v->cv3) VC_TRY(host_param(mem, P3, "cv3", 128, 128, 1, w3, b3));
+    GuardedOut gx, gy, gz, gt;                         // gt: b1 of the unfused graph (c3_<idx>.t)
+    VC_TRY(guarded_elems(mem, gx, x, nx, PREC_BF16, tile_guard(w, v->in_cs)));
+    std::vector<uint8_t> y_before;                     // CV3 instance: the m slice of y must come back as it went in
+    if (!v->out_buf) {
+        y_before = to_elems(y, ny, PREC_BF16);
+        VC_TRY(gy.alloc(mem, y_before.size(), y_before.data(), tile_guard(w, out_cs)));
+    } else {
+        y_before = to_elems(x, nx, PREC_BF16);
+    }
+    const bool own_z = v->cv3 && v->z_buf == 0;
+    if (own_z) VC_TRY(guarded_elems(mem, gz, z, nz, PREC_BF16, tile_guard(w, z_cs)));
+    VC_TRY(gt.alloc(mem, npix * 64 * 2));
+    const GuardedOut& my = v->out_buf ? gx : gy;
+    const GuardedOut& zy = v->z_buf == 1 ? gx : v->z_buf == 2 ? my : gz;
+    const ConvP pm1 = chain_conv(P1, gx.out(), v->in_cs, v->in_co, gt.out(), 64, 0, b, h, w, ACT_SILU);
+    ConvP pm2 = chain_conv(P2, gt.out(), 64, 0, my.out(), out_cs, v->out_co, b, h, w, ACT_SILU);
+    if (v->res) { pm2.res = gx.out(); pm2.res_cs = v->in_cs; pm2.res_co = v->in_co; pm2.res_mode = RES_AFTER_ACT; }
+    int st;
+    if (v->cv3) {
+        const ConvP p3 = chain_conv(P3, my.out(), out_cs, v->out_co, zy.out(), z_cs, v->z_co, b, h, w, ACT_SILU);
+        st = v->unfused ? chain_unfused({pm1, pm2, p3}) : launch_bneck_cv3_fused(pm1, pm2, p3, nullptr, v->grid);
+    } else {
+        st = v->unfused ? chain_unfused({pm1, pm2}) : launch_bneck_fused(pm1, pm2, nullptr, v->grid);
+    }
+    VC_TRY(chain_finish(st, kernel));                  // refused: x / y / z as passed
+    if (!v->unfused) VC_TRY(still_filled(gt, kernel, "b1"));
+    if (v->cv3 && !v->unfused) {
+        std::vector<uint8_t> after(my.bytes);
+        VC_TRY(my.read_back(after.data(), kernel));
+        const uint16_t *a16 = (const uint16_t*)after.data(), *b16 = (const uint16_t*)y_before.data();
+        for (size_t p = 0; p < npix; ++p)
+            for (int c = 0; c < 64; ++c) {
+                const size_t i = p * out_cs + v->out_co + c;
+                VC_CHECK(a16[i] == b16[i], VC_ERR_HIP, "%s wrote m (pixel %zu, channel %d)", kernel, p, c);
+            }
+    }
+    VC_TRY(read_elems(gx, nx, PREC_BF16, x, v->cv3 ? "bneck_fused_kernel<true> (the input buffer)" : "bneck_fused_kernel<false> (the input buffer)"));
+    if (!v->out_buf) VC_TRY(read_elems(gy, ny, PREC_BF16, y, kernel));
+    if (own_z) VC_TRY(read_elems(gz, nz, PREC_BF16, z, kernel));
+    return VC_OK;
+}
+
+int vc_reid_block_fused_host(int k, int h, int w, const vc_fused_view* v, float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* y) {
+    VC_CHECK(v && x && w1 && b1 && w2 && b2 && (y || v->out_buf == 1), VC_ERR_ARG, "null argument");
+    set_error("%s", "");
+    const int out_cs = v->out_buf == 1 ? v->in_cs : v->out_cs;
+    VC_CHECK(fused_shape_ok(k, h, w) && (v->out_buf == 0 || v->out_buf == 1) && v->grid >= 0, VC_ERR_ARG, "reid block fused: bad shape");
+    VC_CHECK(fused_slice_ok(v->in_cs, v->in_co, 64) && fused_slice_ok(out_cs, v->out_co, 64), VC_ERR_ARG, "reid block fused: a slice lies outside its stride");
+    const size_t npix = (size_t)k * h * w, nx = npix * v->in_cs, ny = npix * out_cs;
+    DevScratch mem;
+    ConvParam P1, P2;
+    VC_TRY(host_param(mem, P1, "conv1", 64, 64, 3, w1, b1));
+    VC_TRY(host_param(mem, P2, "conv2", 64, 64, 3, w2, b2));
+    GuardedOut gx, gy, gt;                             // gt: t of the unfused graph
+    VC_TRY(guarded_elems(mem, gx, x, nx, PREC_BF16));
+    if (!v->out_buf) VC_TRY(guarded_elems(mem, gy, y, ny, PREC_BF16));
+    VC_TRY(gt.alloc(mem, npix * 64 * 2));
+    const ConvP p1 = chain_conv(P1, gx.out(), v->in_cs, v->in_co, gt.out(), 64, 0, k, h, w, ACT_RELU);
+    ConvP p2 = chain_conv(P2, gt.out(), 64, 0, v->out_buf ? gx.out() : gy.out(), out_cs, v->out_co, k, h, w, ACT_RELU);
+    p2.res = gx.out(); p2.res_cs = v->in_cs; p2.res_co = v->in_co; p2.res_mode = RES_BEFORE_ACT;
+    VC_TRY(chain_finish(v->unfused ? chain_unfused({p1, p2}) : launch_reid_block_fused(p1, p2, nullptr, v->grid), "reid_block_fused_kernel"));   // refused: x / y as passed
+    if (!v->unfused) VC_TRY(still_filled(gt, "reid_block_fused_kernel", "t"));
+    VC_TRY(read_elems(gx, nx, PREC_BF16, x, "reid_block_fused_kernel (the input buffer)"));
+    if (!v->out_buf) VC_TRY(read_elems(gy, ny, PREC_BF16, y, "reid_block_fused_kernel"));
     return VC_OK;
 }
 

@@ -208,7 +208,8 @@ bool reid_block_fused_applicable(const ConvP& p1, const ConvP& p2) {
     return p1.in_cs % 8 == 0 && p1.in_co % 8 == 0 && p2.out_cs % 4 == 0 && p2.out_co % 4 == 0;
 }
 
-int launch_reid_block_fused(const ConvP& p1, const ConvP& p2, hipStream_t s) {
+// grid_cap > 0 (tests, vc_reid_block_fused_host): at most that many workgroups, which then walk all crops; 0 = one per crop up to the CUs
+int launch_reid_block_fused(const ConvP& p1, const ConvP& p2, hipStream_t s, int grid_cap) {
     if (!reid_block_fused_applicable(p1, p2)) return VC_ERR_ARG;
     RbArgs a{};
     a.w1 = (const uint4*)p1.w; a.w2 = (const uint4*)p2.w; a.b1 = p1.bias; a.b2 = p2.bias;
@@ -222,7 +223,9 @@ int launch_reid_block_fused(const ConvP& p1, const ConvP& p2, hipStream_t s) {
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
         return n;
     }();
-    launch_timed(p1, reid_block_fused_kernel, dim3(std::min(a.k, cus)), dim3(RB_NW * 64), 0, s, a);
+    int grid = std::min(a.k, cus);
+    if (grid_cap > 0) grid = std::min(grid, grid_cap);
+    launch_timed(p1, reid_block_fused_kernel, dim3(grid), dim3(RB_NW * 64), 0, s, a);
     VC_HIP(hipGetLastError());
     return VC_OK;
 }

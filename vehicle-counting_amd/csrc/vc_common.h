@@ -227,16 +227,16 @@ bool stem_u8_applicable(const ConvP& p, const LetterboxGeom& g);
 int launch_stem_direct_u8(const ConvP& p, const uint8_t* frames, const LetterboxGeom& g, hipStream_t s, const View* q8 = nullptr, float q_inv_scale = 1.0f);
 // front_fused.hip: YOLO layers 0 + 1 (stem + 3x3 / s2) in one kernel, the stem's output never leaves the CU
 bool c3_fused_applicable(const ConvP& p12, const ConvP& pm1, const ConvP& pm2, const ConvP& p3);     // c3_fused.hip: the first C3 block (64 -> 64, n = 1) in one kernel
-int launch_c3_fused(const ConvP& p12, const ConvP& pm1, const ConvP& pm2, const ConvP& p3, hipStream_t s);
+int launch_c3_fused(const ConvP& p12, const ConvP& pm1, const ConvP& pm2, const ConvP& p3, hipStream_t s, int grid_cap = 0);    // grid_cap (all four block launchers): tests only, 0 = the product's grid
 bool bneck_fused_applicable(const ConvP& pm1, const ConvP& pm2);                                     // bneck_fused.hip: a 64-channel Bottleneck (1x1 + 3x3 [+ shortcut]) in one kernel
-int launch_bneck_fused(const ConvP& pm1, const ConvP& pm2, hipStream_t s);
+int launch_bneck_fused(const ConvP& pm1, const ConvP& pm2, hipStream_t s, int grid_cap = 0);
 bool bneck_cv3_fused_applicable(const ConvP& pm1, const ConvP& pm2, const ConvP& p3);                // the same + the C3's cv3 (1x1 over [m | y2], 128 -> 128) on the tile
-int launch_bneck_cv3_fused(const ConvP& pm1, const ConvP& pm2, const ConvP& p3, hipStream_t s);
+int launch_bneck_cv3_fused(const ConvP& pm1, const ConvP& pm2, const ConvP& p3, hipStream_t s, int grid_cap = 0);
 bool front_fused_applicable(const ConvP& p0, const ConvP& p1);
 int launch_front_fused(const ConvP& p0, const ConvP& p1, const uint8_t* frames_u8 /* nullable */, const LetterboxGeom& g, hipStream_t s);
 bool front_fused_resize_ok(const LetterboxGeom& g);            // u8 frames that need the letterbox RESIZE: does the tile's source footprint fit the kernel's staging area?
 bool reid_block_fused_applicable(const ConvP& p1, const ConvP& p2);          // reid_block_fused.hip: a 64-channel BasicBlock (two 3x3 + residual) on a 25 x 25 map in one kernel
-int launch_reid_block_fused(const ConvP& p1, const ConvP& p2, hipStream_t s);
+int launch_reid_block_fused(const ConvP& p1, const ConvP& p2, hipStream_t s, int grid_cap = 0);
 bool reid_stem_applicable(const ConvP& p, int out_cs, int out_co);          // reid_stem.hip: conv1 + ReLU + MaxPool fused (bf16)
 int launch_reid_stem_pool(const ConvP& p, void* pooled, hipStream_t s);
 int conv_k_tile(int prec);    // K elements per tile (weights are padded to a multiple of it)

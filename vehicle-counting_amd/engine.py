@@ -548,6 +548,40 @@ def conv_s2_pw(x, w3, b3, w1, b1, y, *, view, y2=None):
     return y if y2 is None else (y, y2)
 
 
+def fused_block(kind, x, weights, *, view, y=None, z=None):
+    """One launch of a fused block kernel on WHOLE buffers (bf16): kind "c3" (vc_c3_fused_host, weights = w12, b12, wm1, bm1, wm2, bm2, w3,
+    b3), "bneck" (vc_bneck_fused_host: w1, b1, w2, b2 and, with view["cv3"], w3, b3) or "reid" (vc_reid_block_fused_host: w1, b1, w2, b2).
+    x (B, H, W, in_cs), y (B, H, W, out_cs) and z (B, H, W, z_cs) are uploaded, launched on and returned as copies (x, y, z); y is None when
+    view["out_buf"] is 1, z when there is no cv3 or view["z_buf"] is not 0.  `view`: the other vc_fused_view fields.  A refusal raises VcError
+    with the arrays as the call left them in err.outputs."""
+    x = L.f32(x).copy()
+    B, H, W, in_cs = x.shape
+    y = L.f32(y).copy() if y is not None else None
+    z = L.f32(z).copy() if z is not None else None
+    v = L.FusedView(in_cs=in_cs, out_cs=y.shape[3] if y is not None else 0, z_cs=z.shape[3] if z is not None else 0)
+    for k, val in view.items():
+        if not hasattr(v, k):
+            raise KeyError(k)
+        setattr(v, k, int(val))
+    assert (y is None) == (v.out_buf == 1) and (y is None or y.shape[:3] == x.shape[:3])
+    assert (z is None) == (not v.cv3 or v.z_buf != 0) and (z is None or z.shape[:3] == x.shape[:3])
+    ws = [L.f32(a) for a in weights]
+    assert len(ws) == {"c3": 8, "bneck": 6 if v.cv3 else 4, "reid": 4}[kind]
+    pw = [L.ptr(a, C.c_float) for a in ws]
+    try:
+        if kind == "c3":
+            L.check(L.lib().vc_c3_fused_host(B, H, W, C.byref(v), L.ptr(x, C.c_float), *pw, L.ptr(y, C.c_float)))
+        elif kind == "bneck":
+            pw += [None] * (6 - len(pw))
+            L.check(L.lib().vc_bneck_fused_host(B, H, W, C.byref(v), L.ptr(x, C.c_float), *pw, L.ptr(y, C.c_float), L.ptr(z, C.c_float)))
+        else:
+            L.check(L.lib().vc_reid_block_fused_host(B, H, W, C.byref(v), L.ptr(x, C.c_float), *pw, L.ptr(y, C.c_float)))
+    except L.VcError as err:
+        err.outputs = (x, y, z)
+        raise
+    return x, y, z
+
+
 def kalman_initiate(xyah):
     z = L.f64(xyah).reshape(-1, 4)
     m, c = np.zeros((len(z), 8)), np.zeros((len(z), 8, 8))
