@@ -50,6 +50,16 @@ def test_no_silent_cpu_fallback():
 
     with pytest.raises(L.VcError):
         E.lap(np.ones((2, 2)))
+    # one entry point of every host_*.hip: the staging harness returns at its first allocation
+    with pytest.raises(L.VcError):
+        E.iou_matrix(np.ones((1, 4)), np.ones((1, 4)))
+    with pytest.raises(L.VcError):
+        E.nms(np.ones((1, 4), np.float32), np.ones(1, np.float32), np.zeros(1, np.int32), max_cand=64)
+    with pytest.raises(L.VcError):
+        E.upsample2x(np.zeros((1, 2, 2, 8), np.float32), np.zeros((1, 4, 4, 8), np.float32), 0)
+    with pytest.raises(L.VcError):
+        w, b = np.zeros((64, 64, 3, 3), np.float32), np.zeros(64, np.float32)
+        E.fused_block("reid", np.zeros((1, 8, 8, 64), np.float32), (w, b, w, b), view={}, y=np.zeros((1, 8, 8, 64), np.float32))
 
 
 @pytest.mark.gpu

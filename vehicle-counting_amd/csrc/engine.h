@@ -1,4 +1,5 @@
-// Engine internals shared between engine.hip / engine_plan.hip / engine_run.hip (networks), tracker.hip (DeepSORT) and stream.hip (fused path).
+// Engine internals shared between engine.hip / engine_plan.hip / engine_run.hip (networks), tracker.hip (DeepSORT) and stream.hip (fused path),
+// and the engine routines that the host-array entry points (host_*.hip, on the staging harness of host_stage.h) share with the engine.
 #pragma once
 #include <chrono>
 #include <condition_variable>
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "host_stage.h"   // dev_alloc, and DevScratch for the entry points that stage host arrays beside their kernels (yuv_ingest.hip, yuv_egress.hip)
 
 namespace vc {
 
@@ -327,35 +329,14 @@ struct vc_engine {
 
 namespace vc {
 // engine.hip
-int dev_alloc(std::vector<void*>& allocs, void** p, size_t bytes);   // the one allocation routine: hipMalloc, recorded in `allocs`
+int pack_and_upload(std::vector<void*>& allocs, ConvParam& p, int prec, float act_scale = 1.0f);   // p.w / p.b -> packed device weights, bias, fp8 scales
+void crop_corners(const double* b, int W, int H, int out[4]);     // deep_sort.py:89-95 _xywh_to_xyxy
 inline int dev_alloc(vc_engine* e, void** p, size_t bytes) { return dev_alloc(e->allocs, p, bytes); }
 // the counter pair of the next fused launch; null (option "dyn_tiles" 0) = the fixed stride
 inline unsigned* tile_ctr_next(vc_engine* e) {
     if (!e->d_tile_ctr || !e->opt.dyn_tiles) return nullptr;
     return e->d_tile_ctr + (size_t)(e->tile_ctr_seq++ % e->tile_ctr_ring) * 16;
 }
-// Device scratch memory of the stateless host-array entry points (vc_*_host): freed when the owner goes out of scope, so every early
-// VC_TRY / VC_HIP / VC_CHECK return releases it.
-struct DevScratch {
-    std::vector<void*> allocs;
-    DevScratch() = default;
-    DevScratch(const DevScratch&) = delete;
-    DevScratch& operator=(const DevScratch&) = delete;
-    ~DevScratch() { for (void* q : allocs) (void)hipFree(q); }
-    template <class T> int alloc(T** p, size_t bytes) { return dev_alloc(allocs, (void**)p, bytes); }
-};
-// The device output of a parity entry point between two guard blocks that read_back checks: a kernel that wrote outside its output is
-// reported instead of returning a plausible result.
-struct GuardedOut {
-    static constexpr size_t kGuard = 256;
-    uint8_t* base = nullptr;
-    size_t bytes = 0, guard = kGuard;
-    // out_bytes + 2 guard blocks, all 0xA5; with `preload` the output starts as the caller's array.  guard_bytes (a multiple of 256): a
-    // caller that knows how far a kernel without its bounds tests would stray (a tile's overhang) asks for blocks that hold all of it
-    int alloc(DevScratch& mem, size_t out_bytes, const uint8_t* preload = nullptr, size_t guard_bytes = kGuard);
-    uint8_t* out() const { return base + guard; }
-    int read_back(uint8_t* host_out, const char* kernel) const;      // waits for the null stream; `kernel` names the culprit
-};
 int dev_realloc(vc_engine* e, void** p, size_t bytes);            // frees *p (if it belongs to the engine) and allocates anew
 int host_alloc(vc_engine* e, void** p, size_t bytes);
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
@@ -369,6 +350,13 @@ int reid_alloc(vc_engine* e);
 int reid_build_ops(vc_engine* e, int k0, int k, ReidPlan& plan);
 int reid_cpad(int prec);                                          // channels of the ReID input buffer
 View mkview(const View& buf, int B, int H, int W, int C, int co);
+// The one place a ConvP is filled from a packed parameter: the plans (PlanBuilder::conv) and the entry points that launch one convolution
+// or a fused block on host arrays (host_conv.hip) both go through it, so a test launches what the engine would launch.  in / out: channel
+// slices of NHWC buffers; B x H x W: the logical input (a pair_stem parameter reads it as H x W/2 pixels of 8 channels).  Everything else
+// (residual, second destination, out_f32 / out_bf16, m_dev, in_up, cfg / ablate / slots) is the caller's to set on the result.
+struct ConvSlice { void* ptr; int cs, co; };
+ConvP conv_params(const ConvParam& p, ConvSlice in, ConvSlice out, int B, int H, int W, int kh, int kw, int stride, int pad, int act,
+                  float act_scale, float inv_act_scale);
 // engine_run.hip: running them
 void tune_cache_load(vc_engine* e);
 void tune_cache_save(vc_engine* e);
@@ -389,6 +377,7 @@ int run_reid_on(vc_engine* e, const uint8_t* d_frames, int H, int W, int k, cons
 int ingest_take_slot(vc_engine* e, int b, int h, int w, int* slot);
 size_t ingest_slot_bytes(const vc_engine* e);
 int ingest_publish(vc_engine* e, int slot, void** frames_dev_out);
+inline bool nms_capacity_ok(int max_cand, int max_det) { return max_cand % 64 == 0 && max_cand >= 64 && max_cand <= 8192 && max_det >= 1; }   // launch_nms's sizes
 // yuv_ingest.hip / yuv_egress.hip: descriptor validation (pure host code) and the two conversions, both enqueued on `s`
 int yuv_resolve(const vc_yuv_desc* d, int b, int h, int w, YuvGeom& g);
 // The rules of a sized batch (pure host code): every size in 1 .. 1 << 15, every frame's own network shape at img_size that of frame 0;

@@ -28,6 +28,28 @@ static int alloc_buf(vc_engine* e, std::map<std::string, View>& m, const std::st
     return VC_OK;
 }
 
+ConvP conv_params(const ConvParam& p, ConvSlice in, ConvSlice out, int B, int H, int W, int kh, int kw, int stride, int pad, int act,
+                  float act_scale, float inv_act_scale) {
+    ConvP c{};
+    c.in = in.ptr; c.w = p.d_w; c.bias = p.d_b; c.out = out.ptr;
+    c.B = B; c.H = H;
+    if (p.pair_stem) {
+        c.W = W / 2; c.Cin = 8; c.in_cs = 8; c.in_co = 0;
+        c.kh = p.kh; c.kw = p.kw / 2; c.sh = stride; c.sw = 1; c.ph = pad; c.pw = 1;
+    } else {
+        c.W = W; c.Cin = p.cin_eff; c.in_cs = in.cs; c.in_co = in.co;
+        c.kh = kh; c.kw = kw; c.sh = c.sw = stride; c.ph = c.pw = pad;
+    }
+    c.Ho = (H + 2 * pad - kh) / stride + 1; c.Wo = (W + 2 * pad - kw) / stride + 1;
+    c.Cout = p.O; c.out_cs = out.cs; c.out_co = out.co;
+    c.K = p.K; c.Kp = p.Kp;
+    c.act = act; c.res_mode = RES_NONE; c.prec = p.prec;
+    c.scale = p.d_scale; c.act_scale = act_scale; c.inv_act_scale = inv_act_scale;
+    c.M = B * c.Ho * c.Wo;
+    c.cfg = -1;
+    return c;
+}
+
 struct PlanBuilder {
     vc_engine* e;
     Net* net;
@@ -45,24 +67,9 @@ struct PlanBuilder {
         op.kind = Op::CONV;
         op.param = it->second;
         ConvP& c = op.conv;
-        c.in = in.ptr; c.w = cp.d_w; c.bias = cp.d_b; c.out = out.ptr;
-        c.B = in.B;
-        if (cp.pair_stem) {
-            c.H = in.H; c.W = in.W / 2; c.Cin = 8; c.in_cs = 8; c.in_co = 0;
-            c.kh = cp.kh; c.kw = cp.kw / 2; c.sh = s; c.sw = 1; c.ph = p; c.pw = 1;
-            c.Ho = (in.H + 2 * p - k) / s + 1; c.Wo = (in.W + 2 * p - k) / s + 1;
-        } else {
-            c.H = in.H; c.W = in.W; c.Cin = cp.cin_eff; c.in_cs = in.cs; c.in_co = in.co;
-            c.kh = k; c.kw = k; c.sh = s; c.sw = s; c.ph = p; c.pw = p;
-            c.Ho = (in.H + 2 * p - k) / s + 1; c.Wo = (in.W + 2 * p - k) / s + 1;
-        }
-        c.Cout = cp.O; c.out_cs = out.cs; c.out_co = out.co;
-        c.K = cp.K; c.Kp = cp.Kp;
-        c.act = act; c.res_mode = res_mode; c.out_f32 = out_f32 ? 1 : 0; c.prec = cp.prec;
-        c.scale = cp.d_scale; c.act_scale = e->act_scale; c.inv_act_scale = 1.0f / e->act_scale; c.out_bf16 = 0;
+        c = conv_params(cp, {in.ptr, in.cs, in.co}, {out.ptr, out.cs, out.co}, in.B, in.H, in.W, k, k, s, p, act, e->act_scale, 1.0f / e->act_scale);
+        c.res_mode = res_mode; c.out_f32 = out_f32 ? 1 : 0;
         if (res) { c.res = res->ptr; c.res_cs = res->cs; c.res_co = res->co; }
-        c.M = c.B * c.Ho * c.Wo;
-        c.cfg = -1;
         op.C = cp.I * cp.kh * cp.kw;          // logical K for algorithmic FLOPs
         ops->push_back(op);
         out.B = in.B; out.H = c.Ho; out.W = c.Wo; out.C = cp.O;

@@ -2,7 +2,8 @@
 // (track_kernels.hip); the host only prepares a batch's detections -- confidence filter and DeepSORT NMS, which do not depend
 // on tracker state -- packs them with the (frame, class) task list into one host-to-device copy, launches ONE kernel per batch
 // and reads the rows the kernel wrote into pinned memory.  One tracker per (camera, class) like the reference
-// (modules/track.py:16).
+// (modules/track.py:16).  (The single-function entry points -- vc_kalman_*_host, vc_iou_cost_host, vc_cosine_cost_host, vc_lap_host --
+// are host_track.hip.)
 //
 // Reference (paths relative to /root/reference/networks/deepsort/):
 //   deep_sort.py:25-59            DeepSort.update (confidence filter :31, tlwh :68-87, NMS :37-41, predict/update :44-45, rows :46-58)
@@ -421,11 +422,6 @@ static void xyxy_to_cxcywh(const double* b, double* o) {
     o[0] = b[0] + w / 2; o[1] = b[1] + h / 2; o[2] = w; o[3] = h;
 }
 
-static void crop_corners_i(const double* b, int W, int H, int* c) {  // deep_sort.py:89-95
-    c[0] = std::max((int)(b[0] - b[2] / 2), 0); c[2] = std::min((int)(b[0] + b[2] / 2), W - 1);
-    c[1] = std::max((int)(b[1] - b[3] / 2), 0); c[3] = std::min((int)(b[1] + b[3] / 2), H - 1);
-}
-
 // Shared by vc_deepsort_update / vc_videotracker_run: one frame already on the device, blocking.
 // groups: per tracker the indices (into xyxy/conf) of its boxes.  Output rows [x1,y1,x2,y2,id,label].
 // The trackers are known here, so DeepSort.update's own filter (prepare_dets: deep_sort.py:31-37) runs BEFORE the crops are cut and,
@@ -439,7 +435,7 @@ int frame_track(vc_engine* e, const uint8_t* d_frame_base, int frame_index, int 
     for (int i = 0; i < n; ++i) {
         double c[4]; int q[4];
         xyxy_to_cxcywh(xyxy + (size_t)i * 4, c);
-        crop_corners_i(c, W, H, q);
+        crop_corners(c, W, H, q);                       // deep_sort.py:89-95
         VC_CHECK(q[2] > q[0] && q[3] > q[1], VC_ERR_ARG, "box %d gives an empty crop (the reference's cv2.resize raises here)", i);
         int* h = &crops[(size_t)i * 5];
         h[0] = frame_index; h[1] = q[0]; h[2] = q[1]; h[3] = q[2]; h[4] = q[3];
@@ -832,121 +828,6 @@ int vc_videotracker_run(vc_engine* e, const int* trackers, int num_classes, cons
     return VC_OK;
 }
 
-// ---- single-function entry points (parity tests): the batch kernel's device functions on caller-supplied state --------------------
-static int with_pool(int n, TrackPool& tp, std::vector<void*>& allocs) {
-    tp.max_tracks = n; tp.budget_cap = 1;
-    VC_HIP(hipMalloc((void**)&tp.mean, (size_t)n * 8 * sizeof(double))); allocs.push_back(tp.mean);
-    VC_HIP(hipMalloc((void**)&tp.cov, (size_t)n * 64 * sizeof(double))); allocs.push_back(tp.cov);
-    tp.gallery = nullptr;
-    return VC_OK;
-}
-static void free_all(std::vector<void*>& a) { for (void* p : a) hipFree(p); a.clear(); }
-
-#define VC_HOST_FINISH(st)                                                                                              \
-    if ((st) == VC_OK && hipDeviceSynchronize() != hipSuccess) { set_error("kernel failed: %s", hipGetErrorString(hipGetLastError())); (st) = VC_ERR_HIP; }
-
-// which: 0 initiate (z -> mean, cov), 1 predict, 2 update (z)
-static int kalman_kat(double* mean8, double* cov64, const double* z4, int n, int which) {
-    VC_CHECK(mean8 && cov64 && n > 0, VC_ERR_ARG, "bad argument");
-    TrackPool tp{}; std::vector<void*> al; double* dz = nullptr;
-    int st = with_pool(n, tp, al);
-    if (st == VC_OK && which != 0) { hipMemcpy(tp.mean, mean8, (size_t)n * 64, hipMemcpyHostToDevice); hipMemcpy(tp.cov, cov64, (size_t)n * 512, hipMemcpyHostToDevice); }
-    if (st == VC_OK && z4) {
-        if (hipMalloc((void**)&dz, (size_t)n * 32) != hipSuccess) { set_error("alloc"); st = VC_ERR_HIP; } else { al.push_back(dz); hipMemcpy(dz, z4, (size_t)n * 32, hipMemcpyHostToDevice); }
-    }
-    if (st == VC_OK) st = launch_kat_kalman(tp, which, dz, n, nullptr);
-    VC_HOST_FINISH(st);
-    if (st == VC_OK) { hipMemcpy(mean8, tp.mean, (size_t)n * 64, hipMemcpyDeviceToHost); hipMemcpy(cov64, tp.cov, (size_t)n * 512, hipMemcpyDeviceToHost); }
-    free_all(al);
-    return st;
-}
-int vc_kalman_initiate_host(const double* xyah, int n, double* mean8, double* cov64) {
-    VC_CHECK(xyah, VC_ERR_ARG, "null measurement");
-    return kalman_kat(mean8, cov64, xyah, n, 0);
-}
-int vc_kalman_predict_host(double* mean8, double* cov64, int n) { return kalman_kat(mean8, cov64, nullptr, n, 1); }
-int vc_kalman_update_host(double* mean8, double* cov64, const double* z4, int n) {
-    VC_CHECK(z4, VC_ERR_ARG, "null measurement");
-    return kalman_kat(mean8, cov64, z4, n, 2);
-}
-
-// squared Mahalanobis distances of ONE track against n_meas measurements (the gate's project4 / chol4 / maha4)
-int vc_kalman_gating_host(const double* mean8, const double* cov64, const double* z4, int n_meas, double* out) {
-    VC_CHECK(mean8 && cov64 && z4 && out && n_meas > 0, VC_ERR_ARG, "bad argument");
-    TrackPool tp{}; std::vector<void*> al; double *dz = nullptr, *dout = nullptr;
-    int st = with_pool(1, tp, al);
-    if (st == VC_OK) { hipMemcpy(tp.mean, mean8, 64, hipMemcpyHostToDevice); hipMemcpy(tp.cov, cov64, 512, hipMemcpyHostToDevice); }
-    if (st == VC_OK && (hipMalloc((void**)&dz, (size_t)n_meas * 32) != hipSuccess || hipMalloc((void**)&dout, (size_t)n_meas * 8) != hipSuccess)) { set_error("alloc"); st = VC_ERR_HIP; }
-    if (dz) al.push_back(dz);
-    if (dout) al.push_back(dout);
-    if (st == VC_OK) { hipMemcpy(dz, z4, (size_t)n_meas * 32, hipMemcpyHostToDevice); st = launch_gating_values(tp, 0, dz, n_meas, dout, nullptr); }
-    VC_HOST_FINISH(st);
-    if (st == VC_OK) hipMemcpy(out, dout, (size_t)n_meas * 8, hipMemcpyDeviceToHost);
-    free_all(al);
-    return st;
-}
-
-int vc_iou_cost_host(const double* track_tlwh, int t, const double* det_tlwh, int d, double* out_iou) {
-    VC_CHECK(track_tlwh && det_tlwh && out_iou && t > 0 && d > 0, VC_ERR_ARG, "bad argument");
-    double *da = nullptr, *db = nullptr, *dout = nullptr;
-    std::vector<void*> al;
-    int st = VC_OK;
-    if (hipMalloc((void**)&da, (size_t)t * 32) != hipSuccess || hipMalloc((void**)&db, (size_t)d * 32) != hipSuccess ||
-        hipMalloc((void**)&dout, (size_t)t * d * 8) != hipSuccess) { set_error("alloc"); st = VC_ERR_HIP; }
-    if (da) al.push_back(da);
-    if (db) al.push_back(db);
-    if (dout) al.push_back(dout);
-    if (st == VC_OK) { hipMemcpy(da, track_tlwh, (size_t)t * 32, hipMemcpyHostToDevice); hipMemcpy(db, det_tlwh, (size_t)d * 32, hipMemcpyHostToDevice);
-                       st = launch_iou_boxes(da, t, db, d, dout, nullptr); }
-    VC_HOST_FINISH(st);
-    if (st == VC_OK) hipMemcpy(out_iou, dout, (size_t)t * d * 8, hipMemcpyDeviceToHost);
-    free_all(al);
-    return st;
-}
-
-int vc_cosine_cost_host(const float* gallery, const int* gal_count, int t, int s_cap, const float* feat, int d, double* out) {
-    VC_CHECK(gallery && gal_count && feat && out && t > 0 && d > 0 && s_cap > 0, VC_ERR_ARG, "bad argument");
-    TrackPool tp{}; std::vector<void*> al;
-    int st = with_pool(t, tp, al);
-    tp.budget_cap = s_cap;
-    float* dfeat = nullptr; double *dz = nullptr, *dout = nullptr; CostJob* dj = nullptr; int* drow = nullptr;
-    if (st == VC_OK && (hipMalloc((void**)&tp.gallery, (size_t)t * s_cap * VC_FEAT_DIM * 4) != hipSuccess || hipMalloc((void**)&dfeat, (size_t)d * VC_FEAT_DIM * 4) != hipSuccess ||
-                        hipMalloc((void**)&dz, (size_t)d * 32) != hipSuccess || hipMalloc((void**)&dout, (size_t)t * d * 8) != hipSuccess ||
-                        hipMalloc((void**)&dj, (size_t)t * sizeof(CostJob)) != hipSuccess || hipMalloc((void**)&drow, (size_t)d * 4) != hipSuccess)) { set_error("alloc"); st = VC_ERR_HIP; }
-    for (void* p : {(void*)tp.gallery, (void*)dfeat, (void*)dz, (void*)dout, (void*)dj, (void*)drow}) if (p) al.push_back(p);
-    if (st == VC_OK) {
-        // a wide-open gate: identity covariance scaled up, measurement = mean
-        std::vector<double> mean((size_t)t * 8, 0.0), cov((size_t)t * 64, 0.0), z((size_t)d * 4, 0.0);
-        for (int i = 0; i < t; ++i) { mean[i * 8 + 3] = 100.0; for (int k = 0; k < 8; ++k) cov[(size_t)i * 64 + k * 9] = 1e6; }
-        for (int i = 0; i < d; ++i) z[i * 4 + 3] = 100.0;
-        std::vector<CostJob> jobs(t);
-        std::vector<int> rows(d);
-        std::iota(rows.begin(), rows.end(), 0);
-        for (int i = 0; i < t; ++i) jobs[i] = CostJob{i, gal_count[i], 0, d, i * d, 1};
-        hipMemcpy(tp.mean, mean.data(), mean.size() * 8, hipMemcpyHostToDevice); hipMemcpy(tp.cov, cov.data(), cov.size() * 8, hipMemcpyHostToDevice);
-        hipMemcpy(dfeat, feat, (size_t)d * VC_FEAT_DIM * 4, hipMemcpyHostToDevice);
-        {   // samples enter the device gallery the way the tracker stores them (normalised rows)
-            float* draw = nullptr; int* dsps = nullptr;
-            std::vector<int> sps;
-            for (int i = 0; i < t; ++i) for (int q = 0; q < gal_count[i]; ++q) { sps.push_back(i); sps.push_back(q); sps.push_back(i * s_cap + q); }
-            if (hipMalloc((void**)&draw, (size_t)t * s_cap * VC_FEAT_DIM * 4) == hipSuccess && hipMalloc((void**)&dsps, sps.size() * 4 + 16) == hipSuccess) {
-                al.push_back(draw); al.push_back(dsps);
-                hipMemcpy(draw, gallery, (size_t)t * s_cap * VC_FEAT_DIM * 4, hipMemcpyHostToDevice);
-                hipMemcpy(dsps, sps.data(), sps.size() * 4, hipMemcpyHostToDevice);
-                st = launch_gallery_write(tp, dsps, (int)sps.size() / 3, draw, nullptr);
-            } else { set_error("alloc"); st = VC_ERR_HIP; }
-        }
-        hipMemcpy(dz, z.data(), z.size() * 8, hipMemcpyHostToDevice);
-        hipMemcpy(dj, jobs.data(), jobs.size() * sizeof(CostJob), hipMemcpyHostToDevice);
-        hipMemcpy(drow, rows.data(), rows.size() * 4, hipMemcpyHostToDevice);
-        if (st == VC_OK) st = launch_appearance_cost(tp, dj, t, dfeat, drow, dz, dout, nullptr);
-    }
-    VC_HOST_FINISH(st);
-    if (st == VC_OK) hipMemcpy(out, dout, (size_t)t * d * 8, hipMemcpyDeviceToHost);
-    free_all(al);
-    return st;
-}
-
 int vc_dsort_nms_host(const double* tlwh, const double* scores, int n, double max_overlap, int* keep, int* n_keep) {
     VC_CHECK(n_keep && (n == 0 || (tlwh && scores && keep)), VC_ERR_ARG, "null argument");
     std::vector<int> k;
@@ -954,31 +835,6 @@ int vc_dsort_nms_host(const double* tlwh, const double* scores, int n, double ma
     for (size_t i = 0; i < k.size(); ++i) keep[i] = k[i];
     *n_keep = (int)k.size();
     return VC_OK;
-}
-
-// scipy.optimize.linear_sum_assignment through the tracker kernel's own solver (track_core.h lap_solve, one wave on the device)
-int vc_lap_host(const double* cost, int nr, int nc, int* rows, int* cols, int* n_assigned) {
-    VC_CHECK(cost && rows && cols && n_assigned && nr >= 0 && nc >= 0, VC_ERR_ARG, "bad argument");
-    *n_assigned = 0;
-    if (nr == 0 || nc == 0) return VC_OK;
-    VC_CHECK(nr <= 512 && nc <= 512, VC_ERR_CAPACITY, "lap: at most 512 rows / columns");
-    std::vector<void*> al;
-    double *dc = nullptr, *dt = nullptr; int *dr = nullptr, *dq = nullptr, *dn = nullptr;
-    const int k = std::min(nr, nc);
-    int st = VC_OK;
-    if (hipMalloc((void**)&dc, (size_t)nr * nc * 8) != hipSuccess || hipMalloc((void**)&dt, (size_t)nr * nc * 8) != hipSuccess ||
-        hipMalloc((void**)&dr, (size_t)k * 4) != hipSuccess || hipMalloc((void**)&dq, (size_t)k * 4) != hipSuccess || hipMalloc((void**)&dn, 4) != hipSuccess) { set_error("alloc"); st = VC_ERR_HIP; }
-    for (void* p : {(void*)dc, (void*)dt, (void*)dr, (void*)dq, (void*)dn}) if (p) al.push_back(p);
-    if (st == VC_OK) { hipMemcpy(dc, cost, (size_t)nr * nc * 8, hipMemcpyHostToDevice); st = launch_kat_lap(dc, nr, nc, dt, dr, dq, dn, nullptr); }
-    VC_HOST_FINISH(st);
-    if (st == VC_OK) {
-        int n = 0;
-        hipMemcpy(&n, dn, 4, hipMemcpyDeviceToHost);
-        if (n < 0) { set_error("lap: infeasible cost matrix"); st = VC_ERR_ARG; }
-        else { hipMemcpy(rows, dr, (size_t)n * 4, hipMemcpyDeviceToHost); hipMemcpy(cols, dq, (size_t)n * 4, hipMemcpyDeviceToHost); *n_assigned = n; }
-    }
-    free_all(al);
-    return st;
 }
 
 }  // extern "C"
