@@ -12,27 +12,13 @@ import vehicle_counting_amd.engine as E  # noqa: E402
 from oracle import deepsort as od  # noqa: E402
 from oracle import reid as orr  # noqa: E402
 from oracle import yolov5 as oy  # noqa: E402
+from det_prep_cases import BOXES, DROPPED, KEPT_PER_FRAME, kept_indices  # noqa: E402
 from vehicle_counting_amd.synth import synth_frames  # noqa: E402
 from vehicle_counting_amd.weights import synth_reid, synth_yolo  # noqa: E402
 
 TRACK_CFG = dict(MAX_DIST=0.2, MIN_CONFIDENCE=0.25, NMS_MAX_OVERLAP=0.5, MAX_IOU_DISTANCE=0.6, MAX_AGE=30, N_INIT=3, NN_BUDGET=60)
 TRACK_KW = dict(max_dist=0.2, min_confidence=0.25, nms_max_overlap=0.5, max_iou_distance=0.6, max_age=30, n_init=3, nn_budget=60)
 T, B, H, W, NC = 12, 4, 160, 160, 3
-
-# [x1, y1, x2, y2, conf, class] in frame 0; every box moves (+2, +1) pixels per frame, so the overlaps below hold in every frame.
-# DeepSORT's overlap is intersection / area of the LOWER-scoring box with the +1 pixel convention, threshold '>' 0.5 (Q6).
-BOXES = [
-    (5, 5, 75, 95, 0.9, 0),        # 0 A: large, kept
-    (20, 20, 50, 60, 0.8, 0),      # 1 B: nested in A, same class: overlap 1 -> dropped
-    (20, 20, 50, 60, 0.8, 1),      # 2 B in another class: kept
-    (10, 40, 110, 140, 0.5, 2),    # 3 low-confidence large box ...
-    (40, 70, 70, 110, 0.95, 2),    # 4 ... around a high-confidence small one: 31 * 41 / (101 * 101) = 0.12 of the large box -> both kept
-    (55, 30, 105, 70, 0.7, 0),     # 5 21 * 41 of its 51 * 41 pixels (41 %) inside A -> kept
-    (100, 100, 130, 140, 0.25, 1),  # 6 conf == min_confidence: '>' fails -> dropped
-    (85, 5, 135, 50, 0.6, 1),      # 7 equal confidence, different geometry, each suppresses the other (1.0 of box 8, 0.72 of box 7):
-    (90, 8, 135, 48, 0.6, 1),      # 8 the stable ascending sort picks the later one; box 7 is dropped
-]
-DROPPED, KEPT_PER_FRAME = {1, 6, 7}, 6
 
 
 def scene():
@@ -42,19 +28,6 @@ def scene():
         det[f, :, [0, 2]] += 2.0 * f
         det[f, :, [1, 3]] += 1.0 * f
     return det, np.full(T, len(BOXES), np.int32)
-
-
-def kept_indices(det_f, min_conf, nms_overlap):
-    """Box indices of one frame that DeepSort.update turns into Detections: the reference's filter, per class, on the rows
-    marshalled like networks/yolo.py:72-97 (oracle.deepsort.DeepSortOracle.update lines :31-37)."""
-    m = oy.marshal_like_reference(det_f)
-    xywh, labels, scores = np.asarray(m["bboxes"], np.float64), np.asarray(m["classes"]), np.asarray(m["scores"], np.float64)
-    kept = []
-    for c in range(NC):
-        idx = [i for i in np.flatnonzero(labels == c) if scores[i] > min_conf]
-        keep = od.dsort_nms(xywh[idx], nms_overlap, scores[idx]) if idx else []      # xywh here is top-left + size = tlwh
-        kept += [int(idx[k]) for k in keep]
-    return sorted(kept)
 
 
 @pytest.fixture(scope="module")

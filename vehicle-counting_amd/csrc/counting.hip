@@ -48,9 +48,54 @@ static int best_direction(const vc_counter* c, const int64_t* fbox, const int64_
     return bi;
 }
 
+// Zone filter of VideoCounting.run (/root/reference/modules/track.py:102-104 -> utilities/counting/bb_polygon.py:14-114):
+// inside[i] = any corner of boxes[i] = (x1,y1,x2,y2) lies in the polygon (ray cast to y = 1e9, exact double compares).
+// Host-only (the post-pass runs once per video on a few thousand rows); same arithmetic as counting.py.
+namespace {
+struct P2 { double x, y; };
+inline int orient(P2 p, P2 q, P2 r) {
+    const double v = (q.y - p.y) * (r.x - q.x) - (q.x - p.x) * (r.y - q.y);
+    return v == 0 ? 0 : (v > 0 ? 1 : 2);
+}
+inline bool on_segment(P2 p, P2 q, P2 r) {
+    return q.x <= std::max(p.x, r.x) && q.x >= std::min(p.x, r.x) && q.y <= std::max(p.y, r.y) && q.y >= std::min(p.y, r.y);
+}
+inline bool intersect(P2 p1, P2 q1, P2 p2, P2 q2) {
+    const int o1 = orient(p1, q1, p2), o2 = orient(p1, q1, q2), o3 = orient(p2, q2, p1), o4 = orient(p2, q2, q1);
+    if (o1 != o2 && o3 != o4) return true;
+    if (o1 == 0 && on_segment(p1, p2, q1)) return true;
+    if (o2 == 0 && on_segment(p1, q2, q1)) return true;
+    if (o3 == 0 && on_segment(p2, p1, q2)) return true;
+    return o4 == 0 && on_segment(p2, q1, q2);
+}
+bool point_in_polygon(const P2* poly, int n, P2 pt) {
+    const P2 far{pt.x, 1e9};
+    int count = 0;
+    for (int i = 0; i < n; ++i) {
+        const P2 a = poly[i], b = poly[(i + 1) % n];
+        if (intersect(a, b, pt, far)) {
+            if (orient(a, pt, b) == 0) return on_segment(a, pt, b);
+            ++count;
+        }
+    }
+    return count % 2 == 1;
+}
+}  // namespace
+
 using namespace vc;
 
 extern "C" {
+
+int vc_zone_filter_host(const double* polygon_xy, int n_points, const int64_t* boxes_xyxy, int n, uint8_t* inside) {
+    VC_CHECK(polygon_xy && n_points >= 1 && (n == 0 || (boxes_xyxy && inside)), VC_ERR_ARG, "bad argument");
+    const P2* poly = (const P2*)polygon_xy;
+    for (int i = 0; i < n; ++i) {
+        const double x1 = (double)boxes_xyxy[i * 4], y1 = (double)boxes_xyxy[i * 4 + 1], x2 = (double)boxes_xyxy[i * 4 + 2], y2 = (double)boxes_xyxy[i * 4 + 3];
+        inside[i] = point_in_polygon(poly, n_points, P2{x1, y1}) || point_in_polygon(poly, n_points, P2{x2, y1}) ||
+                    point_in_polygon(poly, n_points, P2{x2, y2}) || point_in_polygon(poly, n_points, P2{x1, y2});
+    }
+    return VC_OK;
+}
 
 int vc_counter_create(const double* polygon_xy, int n_points, const double* dir_lines, int n_dir, int num_classes, vc_counter** out) {
     VC_CHECK(polygon_xy && n_points >= 1 && dir_lines && n_dir >= 1 && num_classes >= 1 && out, VC_ERR_ARG, "bad argument");

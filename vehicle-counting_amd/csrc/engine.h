@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "det_prep.h"     // FrameDets, Prepared, FramePrepared: the detection hand-over that needs no engine
 #include "host_stage.h"   // dev_alloc, and DevScratch for the entry points that stage host arrays beside their kernels (yuv_ingest.hip, yuv_egress.hip)
 
 namespace vc {
@@ -121,10 +122,6 @@ struct YuvGeom {
 
 }  // namespace vc
 
-namespace vc {
-struct Prepared { std::vector<double> tlwh, conf; std::vector<int> feat_rows; };   // filtered + NMS'ed detections of one tracker (tracker.hip)
-}
-
 struct vc_render;
 
 struct vc_engine {
@@ -230,7 +227,6 @@ struct vc_engine {
     int* h_crops2[3] = {nullptr, nullptr, nullptr};
     unsigned reid_seq = 0;
     std::vector<int> crop_scratch;               // crop list of the batch being validated (stream.hip::issue_reid)
-    struct FrameDets { std::vector<double> xyxy, conf; std::vector<int> label; };
     // DeepSort.update's own detection filter (deep_sort.py:31-37): the two tracker parameters prepare_dets reads.  `stream_flt` is the
     // one every tracker of the most recent vc_stream_run_async* call agreed on (valid = false: no such call yet, or they disagreed)
     struct EmbedFilter { bool valid = false; double min_confidence = 0, nms_max_overlap = 0; };
@@ -244,13 +240,13 @@ struct vc_engine {
         int stage = 0;                   // 0: detector enqueued, 1: ReID enqueued as well
         bool embed_refused = false;      // a look-ahead attempt to embed this batch failed; the call that consumes it reports why (stream.hip)
         int fslot = 0;                   // feature / crop buffer of this batch
-        std::vector<FrameDets> fd;       // per frame, as VideoTracker.run sees them
+        std::vector<vc::FrameDets> fd;   // per frame, as VideoTracker.run sees them
         std::vector<int> row0;           // first feature row of each frame when every box is embedded
         // embed_kept_only: the batch was embedded under `flt` -- only the boxes prepare_dets keeps own a feature row, and prep[f] holds
-        // frame f's prepare_dets results per label (ascending), feat_rows indexing those compact rows (stream.hip::issue_reid)
+        // frame f's prepare_frame results (det_prep.h), feat_rows indexing those compact rows (stream.hip::issue_reid)
         bool filtered = false;
         EmbedFilter flt;
-        std::vector<std::vector<std::pair<int, vc::Prepared>>> prep;
+        std::vector<vc::FramePrepared> prep;
         std::vector<float> inj_det; std::vector<int> inj_cnt; int inj_b = 0, inj_n = 0;   // detection injection captured at submit time
     };
     std::vector<Pending> pending;
@@ -330,7 +326,6 @@ struct vc_engine {
 namespace vc {
 // engine.hip
 int pack_and_upload(std::vector<void*>& allocs, ConvParam& p, int prec, float act_scale = 1.0f);   // p.w / p.b -> packed device weights, bias, fp8 scales
-void crop_corners(const double* b, int W, int H, int out[4]);     // deep_sort.py:89-95 _xywh_to_xyxy
 inline int dev_alloc(vc_engine* e, void** p, size_t bytes) { return dev_alloc(e->allocs, p, bytes); }
 // the counter pair of the next fused launch; null (option "dyn_tiles" 0) = the fixed stride
 inline unsigned* tile_ctr_next(vc_engine* e) {
@@ -402,9 +397,6 @@ struct ProfScope {
 };
 // tracker.hip
 int tracker_init_pool(vc_engine* e);
-void prepare_dets(const double* xyxy, const double* conf, const int* rows, int k, const vc_tracker_params& p, Prepared& out);
-void prepare_dets(const double* xyxy, const double* conf, const int* rows, int k, double min_confidence, double nms_max_overlap, Prepared& out);
-void dsort_nms(const double* tlwh, const double* scores, int n, double max_overlap, std::vector<int>& keep);
 // Build + enqueue one tracker batch on the tracker stream (after `wait`, if given, has fired on the GPU).  frame_groups[f] lists
 // (class label, tracker id, prepared detections) of frame f in class order.  Rows land in stage `st`; track_collect waits for them.
 struct FrameClassDets { int label, tracker; Prepared dets; };
@@ -415,7 +407,10 @@ int track_enqueue(vc_engine* e, int st, const std::vector<std::vector<FrameClass
 int track_collect(vc_engine* e, int st, int64_t* out_rows6, int cap_rows_per_frame, int* out_m);
 int track_idle(vc_engine* e);              // wait until no tracker batch is in flight (stream path included)
 int async_wait_all(vc_engine* e);          // stream.hip: the same, named as the blocking entry points call it
-int frame_track(vc_engine* e, const uint8_t* d_frame_base, int frame_index, int H, int W, const std::vector<int>& tracker_ids,
-                const std::vector<int>& labels, const std::vector<std::vector<int>>& groups, const double* xyxy, const double* conf,
-                int n, std::vector<int64_t>& rows6);
+// det_prep.h's prepare_frame under each in-range class's own tracker parameters (handle trackers[c]), and a prepared frame -> its tasks
+void prepare_for_trackers(vc_engine* e, const int* trackers, int num_classes, const FrameDets& d, int row_base, PrepScratch& scratch, FramePrepared& out);
+int frame_tasks(vc_engine* e, const int* trackers, int num_classes, FramePrepared& prep, std::vector<FrameClassDets>& out);
+// one frame already on the device, blocking: the boxes of label c (all in [0, num_classes)) go to the tracker with handle trackers[c]
+int frame_track(vc_engine* e, const uint8_t* d_frame_base, int frame_index, int H, int W, const int* trackers, int num_classes, const FrameDets& d,
+                std::vector<int64_t>& rows6);
 }  // namespace vc

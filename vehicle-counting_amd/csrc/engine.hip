@@ -120,15 +120,6 @@ int pack_and_upload(std::vector<void*>& allocs, ConvParam& p, int prec, float ac
     return VC_OK;
 }
 
-// deep_sort.py:89-95 _xywh_to_xyxy: int() truncation toward zero, clamp to [0, W-1] / [0, H-1]
-void crop_corners(const double* b, int W, int H, int out[4]) {
-    const double x = b[0], y = b[1], w = b[2], h = b[3];
-    out[0] = std::max((int)(x - w / 2), 0);
-    out[2] = std::min((int)(x + w / 2), W - 1);
-    out[1] = std::max((int)(y - h / 2), 0);
-    out[3] = std::min((int)(y + h / 2), H - 1);
-}
-
 }  // namespace vc
 
 // ================================================================================================ C ABI
@@ -570,12 +561,10 @@ int vc_embed(vc_engine* e, const uint8_t* bgr, int h, int w, const double* boxes
     VC_HIP(hipSetDevice(e->cfg.device));
     const size_t bytes = (size_t)h * w * 3;
     VC_CHECK(bytes <= e->d_frames_bytes, VC_ERR_CAPACITY, "frame exceeds the staging buffer");
-    for (int i = 0; i < k; ++i) {
-        int c[4];
-        crop_corners(boxes + (size_t)i * 4, w, h, c);
-        VC_CHECK(c[2] > c[0] && c[3] > c[1], VC_ERR_ARG, "box %d gives an empty crop (the reference's cv2.resize raises here)", i);
-        e->h_crops[i * 5 + 0] = 0; e->h_crops[i * 5 + 1] = c[0]; e->h_crops[i * 5 + 2] = c[1]; e->h_crops[i * 5 + 3] = c[2]; e->h_crops[i * 5 + 4] = c[3];
-    }
+    std::vector<int> crops;
+    const int empty = append_crops_cxcywh(0, w, h, boxes, k, crops);
+    VC_CHECK(empty < 0, VC_ERR_ARG, "box %d gives an empty crop (the reference's cv2.resize raises here)", empty);
+    memcpy(e->h_crops, crops.data(), crops.size() * sizeof(int));
     VC_HIP(hipMemcpyAsync(e->d_frames, bgr, bytes, hipMemcpyHostToDevice, e->stream));
     VC_HIP(hipMemcpyAsync(e->d_crops, e->h_crops, (size_t)k * 5 * sizeof(int), hipMemcpyHostToDevice, e->stream));
     VC_TRY(run_reid_dev(e, e->d_frames, h, w, k));

@@ -164,15 +164,12 @@ int vc_letterbox_dev(const void* frames_dev, int b, int h, int w, int net_h, int
 
 int vc_crop_resize_frames_host(const uint8_t* const* bgr, const vc_frame_dims* dims, int b, const int* frame_of_box, const double* boxes, int k, float* out) {
     VC_CHECK(frame_of_box && boxes && out && k >= 1, VC_ERR_ARG, "bad argument");
-    std::vector<int> crops((size_t)k * 5);
+    std::vector<int> crops;
     for (int i = 0; i < k; ++i) {
         const int f = frame_of_box[i];
         VC_CHECK(dims && f >= 0 && f < b, VC_ERR_ARG, "box %d: frame %d outside [0, %d)", i, f, b);
-        int c[4];
-        crop_corners(boxes + (size_t)i * 4, dims[f].w, dims[f].h, c);                 // the frame's own W - 1, H - 1
-        VC_CHECK(c[2] > c[0] && c[3] > c[1], VC_ERR_ARG, "box %d gives an empty crop (the reference's cv2.resize raises here)", i);
-        crops[(size_t)i * 5] = f;
-        memcpy(&crops[(size_t)i * 5 + 1], c, sizeof(c));
+        const int empty = append_crops_cxcywh(f, dims[f].w, dims[f].h, boxes + (size_t)i * 4, 1, crops);   // the frame's own W - 1, H - 1
+        VC_CHECK(empty < 0, VC_ERR_ARG, "box %d gives an empty crop (the reference's cv2.resize raises here)", i);
     }
     DevScratch mem;
     GuardedOut dd;

@@ -2,12 +2,9 @@
 // batch of device-resident frames of one camera: detect (batched) -> marshal like networks/yolo.py:72-97 ->
 // skip empty frames (quirk Q1) -> crops + ReID for every box of the batch in one launch -> per frame, in order,
 // one batched tracker step over the classes that have boxes (modules/track.py:50-59).
+// What is here is the queueing: submissions, staging slots, the three feature buffers, events and error reporting.  The hand-over itself
+// (marshal, crop list, grouping by class, DeepSort.update's filter, the embed_kept_only compaction) is det_prep.h.
 // (The detect tail on host arrays -- vc_nms_host, vc_decode_host and their kin -- is host_detect.hip.)
-#include <algorithm>
-#include <cmath>
-#include <map>
-#include <numeric>
-
 #include <chrono>
 #include <cstdlib>
 #include <thread>
@@ -37,28 +34,6 @@ struct Tm {
         for (double& a : acc) a = 0;                   // windowed: the last 10 calls
     }
 } g_tm;
-}  // namespace
-
-namespace {
-
-// DataFrame.to_json(double_precision=10) -> json.loads (quirk Q9), same rounding as oracle/yolov5.py::marshal_like_reference
-inline double round10(double v) { return std::nearbyint(v * 1e10) / 1e10; }
-
-typedef vc_engine::FrameDets FrameDets;     // boxes as VideoTracker.run sees them (xywh -> xyxy round trip included)
-
-void marshal(const float* det6, int n, FrameDets& out) {
-    out.xyxy.clear(); out.conf.clear(); out.label.clear();
-    for (int i = 0; i < n; ++i) {
-        const float* d = det6 + (size_t)i * 6;
-        const double x1 = round10((double)d[0]), y1 = round10((double)d[1]), x2 = round10((double)d[2]), y2 = round10((double)d[3]);
-        const double w = x2 - x1, h = y2 - y1;                         // networks/yolo.py:82
-        out.xyxy.push_back(x1); out.xyxy.push_back(y1);
-        out.xyxy.push_back(w + x1); out.xyxy.push_back(h + y1);        // modules/track.py:39-41
-        out.conf.push_back(round10((double)d[4]));
-        out.label.push_back((int)d[5]);
-    }
-}
-
 }  // namespace
 
 namespace vc {
@@ -197,26 +172,13 @@ int all_crops(vc_engine* e, vc_engine::Pending& pd, std::vector<int>& crops) {
     const int b = pd.b;
     crops.clear();
     pd.row0.assign(b, 0);
-    int k = 0;
     for (int f = 0; f < b; ++f) {
+        const int k = (int)(crops.size() / 5), n = (int)pd.fd[f].conf.size();
         pd.row0[f] = k;
-        FrameDets& d = pd.fd[f];
-        const int h = pd.frame_dims(f).h, w = pd.frame_dims(f).w;
-        VC_CHECK(k + (int)d.conf.size() <= e->cfg.max_crops, VC_ERR_CAPACITY,
+        VC_CHECK(k + n <= e->cfg.max_crops, VC_ERR_CAPACITY,
                  "the batch has more boxes than max_crops (%d): raise vc_engine_config.max_crops", e->cfg.max_crops);
-        for (size_t i = 0; i < d.conf.size(); ++i) {
-            const double* bx = &d.xyxy[i * 4];
-            const double bw = bx[2] - bx[0], bh = bx[3] - bx[1];                 // deep_sort.py:78-87
-            const double cx = bx[0] + bw / 2, cy = bx[1] + bh / 2;
-            int c[5];
-            c[0] = f;
-            c[1] = std::max((int)(cx - bw / 2), 0); c[3] = std::min((int)(cx + bw / 2), w - 1);    // deep_sort.py:89-95
-            c[2] = std::max((int)(cy - bh / 2), 0); c[4] = std::min((int)(cy + bh / 2), h - 1);
-            VC_CHECK(c[3] > c[1] && c[4] > c[2], VC_ERR_ARG,
-                     "frame %d box %zu gives an empty crop (the reference's cv2.resize raises here)", f, i);
-            crops.insert(crops.end(), c, c + 5);
-            ++k;
-        }
+        const int empty = append_crops_xyxy(f, pd.frame_dims(f).w, pd.frame_dims(f).h, pd.fd[f].xyxy.data(), n, crops);   // the frame's own size
+        VC_CHECK(empty < 0, VC_ERR_ARG, "frame %d box %d gives an empty crop (the reference's cv2.resize raises here)", f, empty);
     }
     return VC_OK;
 }
@@ -277,38 +239,15 @@ int issue_reid(vc_engine* e, vc_engine::Pending& pd, const vc_engine::EmbedFilte
     pd.flt = flt;
     pd.prep.clear();
     if (pd.filtered) {
+        // every label that occurs: num_classes is not known at look-ahead time, enqueue_batch_tracking skips the labels outside it
         pd.prep.resize(b);
-        std::map<int, std::vector<int>> by_label;
-        std::vector<int> row_of;
-        std::vector<double> bx, cf;
-        int kept = 0;
-        for (int f = 0; f < b; ++f) {
-            const FrameDets& d = pd.fd[f];
-            const int nf = (int)d.conf.size();
-            by_label.clear();
-            for (int i = 0; i < nf; ++i) by_label[d.label[i]].push_back(i);
-            row_of.assign(nf, -1);
-            for (auto& lg : by_label) {
-                const std::vector<int>& g = lg.second;
-                bx.resize(g.size() * 4); cf.resize(g.size());
-                for (size_t i = 0; i < g.size(); ++i) {
-                    memcpy(&bx[i * 4], &d.xyxy[(size_t)g[i] * 4], 4 * sizeof(double));
-                    cf[i] = d.conf[g[i]];
-                }
-                pd.prep[f].emplace_back(lg.first, Prepared{});
-                Prepared& pr = pd.prep[f].back().second;
-                prepare_dets(bx.data(), cf.data(), g.data(), (int)g.size(), flt.min_confidence, flt.nms_max_overlap, pr);   // feat_rows: box index in the frame
-                for (int r : pr.feat_rows) row_of[r] = 0;
-            }
-            for (int i = 0; i < nf; ++i)
-                if (row_of[i] == 0) {
-                    memmove(&crops[(size_t)kept * 5], &crops[(size_t)(pd.row0[f] + i) * 5], 5 * sizeof(int));
-                    row_of[i] = kept++;
-                }
-            for (auto& lp : pd.prep[f])
-                for (int& r : lp.second.feat_rows) r = row_of[r];
-        }
-        k = kept;
+        PrepScratch scratch;
+        const auto one_filter = [&flt](int, double& min_confidence, double& nms_max_overlap) {
+            min_confidence = flt.min_confidence; nms_max_overlap = flt.nms_max_overlap;
+            return true;
+        };
+        for (int f = 0; f < b; ++f) prepare_frame(pd.fd[f], pd.row0[f], one_filter, scratch, pd.prep[f]);
+        k = compact_kept(crops, pd.prep.data(), b);
     }
     pd.fslot = (int)(e->reid_seq++ % 3);
     VC_TRY(enqueue_reid(e, pd, crops.data(), k));
@@ -395,42 +334,14 @@ static int enqueue_batch_tracking(vc_engine* e, vc_engine::Pending& pd, const in
         if (!same) VC_TRY(reembed_unfiltered(e, pd));
     }
     std::vector<std::vector<FrameClassDets>> frames(b);
-    std::vector<std::vector<int>> by_class(num_classes);
+    PrepScratch scratch;
+    FramePrepared own;
     for (int f = 0; f < b; ++f) {
-        const int cam = cam_of_frame ? cam_of_frame[f] : 0;
-        const int* trackers = all_trackers + (size_t)cam * num_classes;
-        FrameDets& d = pd.fd[f];
-        ndet[f] = (int)d.conf.size();
-        if (d.conf.empty()) continue;                                                // Q1
-        if (pd.filtered) {                                                           // prepared before the crops were cut (issue_reid)
-            for (auto& lp : pd.prep[f]) {
-                const int c = lp.first;
-                if (c < 0 || c >= num_classes) continue;
-                const int ts = tracker_slot(e->trackers, trackers[c]);
-                VC_CHECK(ts >= 0, VC_ERR_NOTFOUND, "bad or stale tracker handle %d for class %d", trackers[c], c);
-                frames[f].push_back(FrameClassDets{c, ts, std::move(lp.second)});
-            }
-            continue;
-        }
-        for (size_t i = 0; i < d.label.size(); ++i)
-            if (d.label[i] >= 0 && d.label[i] < num_classes) by_class[d.label[i]].push_back((int)i);
-        for (int c = 0; c < num_classes; ++c) {
-            std::vector<int>& g = by_class[c];
-            if (g.empty()) continue;
-            const int ts = tracker_slot(e->trackers, trackers[c]);
-            VC_CHECK(ts >= 0, VC_ERR_NOTFOUND, "bad or stale tracker handle %d for class %d", trackers[c], c);
-            std::vector<double> bx(g.size() * 4), cf(g.size());
-            std::vector<int> rows(g.size());
-            for (size_t i = 0; i < g.size(); ++i) {
-                memcpy(&bx[i * 4], &d.xyxy[(size_t)g[i] * 4], 4 * sizeof(double));
-                cf[i] = d.conf[g[i]];
-                rows[i] = pd.row0[f] + g[i];
-            }
-            FrameClassDets fc{c, ts, {}};
-            prepare_dets(bx.data(), cf.data(), rows.data(), (int)g.size(), e->trackers[ts]->p, fc.dets);
-            frames[f].push_back(std::move(fc));
-            g.clear();
-        }
+        const int* trackers = all_trackers + (size_t)(cam_of_frame ? cam_of_frame[f] : 0) * num_classes;
+        ndet[f] = (int)pd.fd[f].conf.size();                                         // a frame without boxes gives no task: Q1
+        // filtered: prepared before the crops were cut (issue_reid); else here, box i of the frame on feature row row0[f] + i
+        if (!pd.filtered) prepare_for_trackers(e, trackers, num_classes, pd.fd[f], pd.row0[f], scratch, own);
+        VC_TRY(frame_tasks(e, trackers, num_classes, pd.filtered ? pd.prep[f] : own, frames[f]));
     }
     g_tm.lap(1);
     VC_TRY(track_enqueue(e, stage, frames, e->d_feat2[pd.fslot], pd.w, pd.h, b * cap_rows_per_frame, e->ev_reid[pd.fslot], pd.dims.empty() ? nullptr : pd.dims.data()));
@@ -605,33 +516,22 @@ int vc_videotracker_run_features(vc_engine* e, const int* trackers, int num_clas
     VC_TRY(async_wait_all(e));
     std::vector<std::vector<FrameClassDets>> frames;
     std::vector<int64_t> keys;
-    std::vector<std::vector<int>> by_class(num_classes);
+    PrepScratch scratch;
+    FramePrepared prep;
+    FrameDets d;
     for (int i0 = 0; i0 < n;) {
         const double key = rows7[(size_t)i0 * 7];
-        int i1 = i0;
-        while (i1 < n && rows7[(size_t)i1 * 7] == key) ++i1;
         VC_CHECK(keys.empty() || (int64_t)key > keys.back(), VC_ERR_ARG, "rows must be sorted by frame key");
         keys.push_back((int64_t)key);
         frames.emplace_back();
-        for (int i = i0; i < i1; ++i) {
-            const int lb = (int)rows7[(size_t)i * 7 + 6];
-            if (lb >= 0 && lb < num_classes) by_class[lb].push_back(i);
+        d.xyxy.clear(); d.conf.clear(); d.label.clear();
+        int i1 = i0;
+        for (; i1 < n && rows7[(size_t)i1 * 7] == key; ++i1) {
+            const double* r = rows7 + (size_t)i1 * 7;
+            d.xyxy.insert(d.xyxy.end(), r + 1, r + 5); d.conf.push_back(r[5]); d.label.push_back((int)r[6]);
         }
-        for (int c = 0; c < num_classes; ++c) {                                        // modules/track.py:50-59
-            std::vector<int>& g = by_class[c];
-            if (g.empty()) continue;
-            const int ts = tracker_slot(e->trackers, trackers[c]);
-            VC_CHECK(ts >= 0, VC_ERR_NOTFOUND, "bad or stale tracker handle %d for class %d", trackers[c], c);
-            std::vector<double> bx(g.size() * 4), cf(g.size());
-            for (size_t k = 0; k < g.size(); ++k) {
-                memcpy(&bx[k * 4], rows7 + (size_t)g[k] * 7 + 1, 4 * sizeof(double));
-                cf[k] = rows7[(size_t)g[k] * 7 + 5];
-            }
-            FrameClassDets fc{c, ts, {}};
-            prepare_dets(bx.data(), cf.data(), g.data(), (int)g.size(), e->trackers[ts]->p, fc.dets);
-            frames.back().push_back(std::move(fc));
-            g.clear();
-        }
+        prepare_for_trackers(e, trackers, num_classes, d, i0, scratch, prep);        // modules/track.py:50-59; row i's embedding is feat_dev[i]
+        VC_TRY(frame_tasks(e, trackers, num_classes, prep, frames.back()));
         i0 = i1;
     }
     const int nf = (int)frames.size();
@@ -672,51 +572,6 @@ int vc_stream_crop_stats(vc_engine* e, int64_t* boxes_detected, int64_t* crops_e
     VC_CHECK(e && boxes_detected && crops_embedded, VC_ERR_ARG, "null argument");
     *boxes_detected = e->boxes_detected;
     *crops_embedded = e->crops_embedded;
-    return VC_OK;
-}
-
-// Zone filter of VideoCounting.run (/root/reference/modules/track.py:102-104 -> utilities/counting/bb_polygon.py:14-114):
-// inside[i] = any corner of boxes[i] = (x1,y1,x2,y2) lies in the polygon (ray cast to y = 1e9, exact double compares).
-// Host-only (the post-pass runs once per video on a few thousand rows); same arithmetic as counting.py.
-namespace {
-struct P2 { double x, y; };
-inline int orient(P2 p, P2 q, P2 r) {
-    const double v = (q.y - p.y) * (r.x - q.x) - (q.x - p.x) * (r.y - q.y);
-    return v == 0 ? 0 : (v > 0 ? 1 : 2);
-}
-inline bool on_segment(P2 p, P2 q, P2 r) {
-    return q.x <= std::max(p.x, r.x) && q.x >= std::min(p.x, r.x) && q.y <= std::max(p.y, r.y) && q.y >= std::min(p.y, r.y);
-}
-inline bool intersect(P2 p1, P2 q1, P2 p2, P2 q2) {
-    const int o1 = orient(p1, q1, p2), o2 = orient(p1, q1, q2), o3 = orient(p2, q2, p1), o4 = orient(p2, q2, q1);
-    if (o1 != o2 && o3 != o4) return true;
-    if (o1 == 0 && on_segment(p1, p2, q1)) return true;
-    if (o2 == 0 && on_segment(p1, q2, q1)) return true;
-    if (o3 == 0 && on_segment(p2, p1, q2)) return true;
-    return o4 == 0 && on_segment(p2, q1, q2);
-}
-bool point_in_polygon(const P2* poly, int n, P2 pt) {
-    const P2 far{pt.x, 1e9};
-    int count = 0;
-    for (int i = 0; i < n; ++i) {
-        const P2 a = poly[i], b = poly[(i + 1) % n];
-        if (intersect(a, b, pt, far)) {
-            if (orient(a, pt, b) == 0) return on_segment(a, pt, b);
-            ++count;
-        }
-    }
-    return count % 2 == 1;
-}
-}  // namespace
-
-int vc_zone_filter_host(const double* polygon_xy, int n_points, const int64_t* boxes_xyxy, int n, uint8_t* inside) {
-    VC_CHECK(polygon_xy && n_points >= 1 && (n == 0 || (boxes_xyxy && inside)), VC_ERR_ARG, "bad argument");
-    const P2* poly = (const P2*)polygon_xy;
-    for (int i = 0; i < n; ++i) {
-        const double x1 = (double)boxes_xyxy[i * 4], y1 = (double)boxes_xyxy[i * 4 + 1], x2 = (double)boxes_xyxy[i * 4 + 2], y2 = (double)boxes_xyxy[i * 4 + 3];
-        inside[i] = point_in_polygon(poly, n_points, P2{x1, y1}) || point_in_polygon(poly, n_points, P2{x2, y1}) ||
-                    point_in_polygon(poly, n_points, P2{x2, y2}) || point_in_polygon(poly, n_points, P2{x1, y2});
-    }
     return VC_OK;
 }
 

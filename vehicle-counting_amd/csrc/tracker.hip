@@ -1,13 +1,13 @@
 // DeepSORT tracker, host side: the tracker state is device-resident and every step runs inside track_batch_kernel
 // (track_kernels.hip); the host only prepares a batch's detections -- confidence filter and DeepSORT NMS, which do not depend
-// on tracker state -- packs them with the (frame, class) task list into one host-to-device copy, launches ONE kernel per batch
-// and reads the rows the kernel wrote into pinned memory.  One tracker per (camera, class) like the reference
+// on tracker state (det_prep.h) -- packs them with the (frame, class) task list into one host-to-device copy, launches ONE kernel
+// per batch and reads the rows the kernel wrote into pinned memory.  One tracker per (camera, class) like the reference
 // (modules/track.py:16).  (The single-function entry points -- vc_kalman_*_host, vc_iou_cost_host, vc_cosine_cost_host, vc_lap_host --
 // are host_track.hip.)
 //
 // Reference (paths relative to /root/reference/networks/deepsort/):
-//   deep_sort.py:25-59            DeepSort.update (confidence filter :31, tlwh :68-87, NMS :37-41, predict/update :44-45, rows :46-58)
-//   sort/preprocessing.py:6-73    non_max_suppression (quirk Q6)                      -> dsort_nms (host: state-independent)
+//   deep_sort.py:25-59            DeepSort.update (confidence filter :31, tlwh :68-87, NMS :37-41 -> det_prep.h; predict/update :44-45, rows :46-58)
+//   sort/preprocessing.py:6-73    non_max_suppression (quirk Q6)                      -> det_prep.h: dsort_nms (host: state-independent)
 //   sort/tracker.py, sort/track.py, sort/linear_assignment.py, sort/nn_matching.py, sort/kalman_filter.py, sort/iou_matching.py
 //                                 -> track_core.h + track_kernels.hip (device)
 //   modules/track.py:30-70        VideoTracker.run (one DeepSORT per class, classes without boxes are not stepped)
@@ -25,62 +25,6 @@
 namespace vc {
 
 using namespace tc;
-
-// sort/preprocessing.py:6-73 (overlap = inter / area(other), +1 pixel, '>' threshold; quirk Q6)
-void dsort_nms(const double* tlwh, const double* scores, int n, double max_overlap, std::vector<int>& keep) {
-    keep.clear();
-    if (n == 0) return;
-    std::vector<double> x1(n), y1(n), x2(n), y2(n), area(n);
-    for (int i = 0; i < n; ++i) {
-        x1[i] = tlwh[i * 4]; y1[i] = tlwh[i * 4 + 1]; x2[i] = tlwh[i * 4 + 2] + tlwh[i * 4]; y2[i] = tlwh[i * 4 + 3] + tlwh[i * 4 + 1];
-        area[i] = (x2[i] - x1[i] + 1) * (y2[i] - y1[i] + 1);
-    }
-    std::vector<int> idx(n);
-    std::iota(idx.begin(), idx.end(), 0);
-    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return scores[a] < scores[b]; });
-    while (!idx.empty()) {
-        const int i = idx.back();
-        idx.pop_back();
-        keep.push_back(i);
-        std::vector<int> rest;
-        for (int j : idx) {
-            const double w = std::max(0.0, std::min(x2[i], x2[j]) - std::max(x1[i], x1[j]) + 1);
-            const double h = std::max(0.0, std::min(y2[i], y2[j]) - std::max(y1[i], y1[j]) + 1);
-            if (!((w * h) / area[j] > max_overlap)) rest.push_back(j);
-        }
-        idx.swap(rest);
-    }
-}
-
-// DeepSort.update minus the embedding: confidence filter, tlwh, DeepSORT NMS -> detections in pick order
-void prepare_dets(const double* xyxy, const double* conf, const int* rows, int k, const vc_tracker_params& p, Prepared& out) {
-    prepare_dets(xyxy, conf, rows, k, p.min_confidence, p.nms_max_overlap, out);
-}
-
-// The same on the two parameters it reads: the result depends on the boxes, the confidences and these alone, never on tracker state, so
-// it can run before the crops are cut (embed_kept_only: a box dropped here never becomes a Detection, deep_sort.py:31-37, and its
-// feature row is never read)
-void prepare_dets(const double* xyxy, const double* conf, const int* rows, int k, double min_confidence, double nms_max_overlap, Prepared& out) {
-    std::vector<double> tl, cf;
-    std::vector<int> fr;
-    for (int i = 0; i < k; ++i) {
-        if (!(conf[i] > min_confidence)) continue;                   // deep_sort.py:31 (the reference computed features for all, Q5)
-        const double* b = xyxy + (size_t)i * 4;
-        const double w = b[2] - b[0], h = b[3] - b[1];               // _xyxy_to_xywh :78-87
-        const double cx = b[0] + w / 2, cy = b[1] + h / 2;
-        tl.push_back(cx - w / 2.); tl.push_back(cy - h / 2.); tl.push_back(w); tl.push_back(h);   // _xywh_to_tlwh :68-75
-        cf.push_back(conf[i]);
-        fr.push_back(rows[i]);
-    }
-    std::vector<int> keep;
-    dsort_nms(tl.data(), cf.data(), (int)cf.size(), nms_max_overlap, keep);
-    out.tlwh.clear(); out.conf.clear(); out.feat_rows.clear();
-    for (int i : keep) {
-        for (int c = 0; c < 4; ++c) out.tlwh.push_back(tl[(size_t)i * 4 + c]);
-        out.conf.push_back(cf[i]);
-        out.feat_rows.push_back(fr[i]);
-    }
-}
 
 // ------------------------------------------------------------------------------------------------ pool
 static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
@@ -417,58 +361,52 @@ int track_collect(vc_engine* e, int st, int64_t* out_rows6, int cap_rows_per_fra
     return VC_OK;
 }
 
-static void xyxy_to_cxcywh(const double* b, double* o) {
-    const double w = b[2] - b[0], h = b[3] - b[1];
-    o[0] = b[0] + w / 2; o[1] = b[1] + h / 2; o[2] = w; o[3] = h;
+// DeepSort.update's filter for a frame whose trackers are known: every class of [0, num_classes) that has boxes, under the parameters
+// of its own tracker (handle trackers[c]); box i of the frame owns feature row row_base + i.  Boxes of other labels are ignored like
+// the reference's mask loop ignores them.  A class with a bad handle is prepared too (under zeros): frame_tasks refuses it.
+void prepare_for_trackers(vc_engine* e, const int* trackers, int num_classes, const FrameDets& d, int row_base, PrepScratch& scratch, FramePrepared& out) {
+    prepare_frame(d, row_base, [&](int c, double& min_confidence, double& nms_max_overlap) {
+        if (c < 0 || c >= num_classes) return false;
+        const int ts = tracker_slot(e->trackers, trackers[c]);
+        if (ts >= 0) { min_confidence = e->trackers[ts]->p.min_confidence; nms_max_overlap = e->trackers[ts]->p.nms_max_overlap; }
+        return true;
+    }, scratch, out);
 }
 
-// Shared by vc_deepsort_update / vc_videotracker_run: one frame already on the device, blocking.
-// groups: per tracker the indices (into xyxy/conf) of its boxes.  Output rows [x1,y1,x2,y2,id,label].
-// The trackers are known here, so DeepSort.update's own filter (prepare_dets: deep_sort.py:31-37) runs BEFORE the crops are cut and,
+// A prepared frame -> its tracker tasks, appended in class order (modules/track.py:50-59: a class without boxes is not stepped; one whose
+// boxes were all dropped is, with zero detections).  A frame prepared at look-ahead time (stream.hip::issue_reid) holds every label that
+// occurred: those outside [0, num_classes) are skipped.  The detections are moved out of `prep`.
+int frame_tasks(vc_engine* e, const int* trackers, int num_classes, FramePrepared& prep, std::vector<FrameClassDets>& out) {
+    for (auto& lp : prep) {
+        const int c = lp.first;
+        if (c < 0 || c >= num_classes) continue;
+        const int ts = tracker_slot(e->trackers, trackers[c]);
+        VC_CHECK(ts >= 0, VC_ERR_NOTFOUND, "bad or stale tracker handle %d for class %d", trackers[c], c);
+        out.push_back(FrameClassDets{c, ts, std::move(lp.second)});
+    }
+    return VC_OK;
+}
+
+// Shared by vc_deepsort_update / vc_videotracker_run: one frame already on the device, blocking.  Every label of `d` lies in
+// [0, num_classes); the boxes of class c go to the tracker with handle trackers[c].  Output rows [x1,y1,x2,y2,id,label].
+// The trackers are known here, so DeepSort.update's own filter (prepare_dets: deep_sort.py:31-37) runs BEFORE the crops are uploaded and,
 // with the engine option embed_kept_only, only the boxes it keeps are embedded: a dropped box never becomes a Detection, so the
 // feature row the reference computes for it (Q5) is never read.  The capacity and empty-crop checks still cover every box.
-int frame_track(vc_engine* e, const uint8_t* d_frame_base, int frame_index, int H, int W, const std::vector<int>& tracker_ids,
-                const std::vector<int>& labels, const std::vector<std::vector<int>>& groups, const double* xyxy, const double* conf,
-                int n, std::vector<int64_t>& rows6) {
+int frame_track(vc_engine* e, const uint8_t* d_frame_base, int frame_index, int H, int W, const int* trackers, int num_classes, const FrameDets& d,
+                std::vector<int64_t>& rows6) {
+    const int n = (int)d.conf.size();
     VC_CHECK(n <= e->cfg.max_crops, VC_ERR_CAPACITY, "%d crops exceed max_crops %d", n, e->cfg.max_crops);
-    std::vector<int> crops((size_t)n * 5);
-    for (int i = 0; i < n; ++i) {
-        double c[4]; int q[4];
-        xyxy_to_cxcywh(xyxy + (size_t)i * 4, c);
-        crop_corners(c, W, H, q);                       // deep_sort.py:89-95
-        VC_CHECK(q[2] > q[0] && q[3] > q[1], VC_ERR_ARG, "box %d gives an empty crop (the reference's cv2.resize raises here)", i);
-        int* h = &crops[(size_t)i * 5];
-        h[0] = frame_index; h[1] = q[0]; h[2] = q[1]; h[3] = q[2]; h[4] = q[3];
-    }
+    std::vector<int> crops;
+    const int empty = append_crops_xyxy(frame_index, W, H, d.xyxy.data(), n, crops);         // deep_sort.py:78-95
+    VC_CHECK(empty < 0, VC_ERR_ARG, "box %d gives an empty crop (the reference's cv2.resize raises here)", empty);
+    PrepScratch scratch;
+    FramePrepared prep;
+    prepare_for_trackers(e, trackers, num_classes, d, 0, scratch, prep);
+    const int k = e->opt.embed_kept_only ? compact_kept(crops, &prep, 1) : n;                // kept boxes get consecutive feature rows, in box order
     std::vector<std::vector<FrameClassDets>> frames(1);
+    VC_TRY(frame_tasks(e, trackers, num_classes, prep, frames[0]));
     int total_tracks = 0;
-    for (size_t j = 0; j < tracker_ids.size(); ++j) {
-        const auto& g = groups[j];
-        std::vector<double> bx(g.size() * 4), cf(g.size());
-        std::vector<int> rows(g.size());
-        for (size_t i = 0; i < g.size(); ++i) {
-            memcpy(&bx[i * 4], xyxy + (size_t)g[i] * 4, 4 * sizeof(double));
-            cf[i] = conf[g[i]];
-            rows[i] = g[i];
-        }
-        const int ts = tracker_slot(e->trackers, tracker_ids[j]);             // (handles, as the caller holds them)
-        VC_CHECK(ts >= 0, VC_ERR_NOTFOUND, "bad or stale tracker handle %d", tracker_ids[j]);
-        FrameClassDets fc{labels[j], ts, {}};
-        prepare_dets(bx.data(), cf.data(), rows.data(), (int)g.size(), e->trackers[ts]->p, fc.dets);
-        total_tracks += e->trackers[ts]->known_tracks + (int)fc.dets.conf.size();
-        frames[0].push_back(std::move(fc));
-    }
-    int k = n;
-    if (e->opt.embed_kept_only) {                                              // kept boxes get consecutive feature rows, in box order
-        std::vector<int> row_of(n, -1);
-        for (const FrameClassDets& fc : frames[0])
-            for (int r : fc.dets.feat_rows) row_of[r] = 0;
-        k = 0;
-        for (int i = 0; i < n; ++i)
-            if (row_of[i] == 0) { memmove(&crops[(size_t)k * 5], &crops[(size_t)i * 5], 5 * sizeof(int)); row_of[i] = k++; }
-        for (FrameClassDets& fc : frames[0])
-            for (int& r : fc.dets.feat_rows) r = row_of[r];
-    }
+    for (const FrameClassDets& fc : frames[0]) total_tracks += e->trackers[fc.tracker]->known_tracks + (int)fc.dets.conf.size();
     e->boxes_detected += n; e->crops_embedded += k;
     if (k > 0) {
         memcpy(e->h_crops, crops.data(), (size_t)k * 5 * sizeof(int));
@@ -771,10 +709,10 @@ int vc_deepsort_update(vc_engine* e, int id, const uint8_t* bgr, int h, int w, c
     const size_t bytes = (size_t)h * w * 3;
     VC_CHECK(bytes <= e->d_frames_bytes, VC_ERR_CAPACITY, "frame exceeds the staging buffer");
     VC_HIP(hipMemcpyAsync(e->d_frames, bgr, bytes, hipMemcpyHostToDevice, e->stream));
-    std::vector<int> all(k);
-    std::iota(all.begin(), all.end(), 0);
+    FrameDets d;                                                // one tracker: every box is class 0 of one
+    d.xyxy.assign(bbox_xyxy, bbox_xyxy + (size_t)k * 4); d.conf.assign(conf, conf + k); d.label.assign(k, 0);
     std::vector<int64_t> rows6;
-    VC_TRY(frame_track(e, e->d_frames, 0, h, w, {id}, {0}, {all}, bbox_xyxy, conf, k, rows6));
+    VC_TRY(frame_track(e, e->d_frames, 0, h, w, &id, 1, d, rows6));
     const int m = (int)(rows6.size() / 6);
     VC_CHECK(m <= cap_rows, VC_ERR_CAPACITY, "need room for %d rows", m);
     for (int i = 0; i < m; ++i) {
@@ -795,32 +733,22 @@ int vc_videotracker_run(vc_engine* e, const int* trackers, int num_classes, cons
     const size_t bytes = (size_t)h * w * 3;
     VC_CHECK(bytes <= e->d_frames_bytes, VC_ERR_CAPACITY, "frame exceeds the staging buffer");
     VC_HIP(hipMemcpyAsync(e->d_frames, bgr, bytes, hipMemcpyHostToDevice, e->stream));
-    std::vector<double> xyxy((size_t)n * 4);
-    for (int i = 0; i < n; ++i) {                               // modules/track.py:39-41
-        xyxy[i * 4] = boxes_xywh[i * 4]; xyxy[i * 4 + 1] = boxes_xywh[i * 4 + 1];
-        xyxy[i * 4 + 2] = boxes_xywh[i * 4 + 2] + boxes_xywh[i * 4]; xyxy[i * 4 + 3] = boxes_xywh[i * 4 + 3] + boxes_xywh[i * 4 + 1];
+    // boxes of classes outside [0, num_classes) are ignored exactly like the reference's mask loop (modules/track.py:50-59), and only used
+    // boxes are embedded: frame_track gets the in-range boxes in class-major order
+    std::vector<int> lab(n);
+    for (int i = 0; i < n; ++i) lab[i] = labels[i] >= 0 && labels[i] < num_classes ? (int)labels[i] : -1;
+    LabelGroups groups;
+    group_by_label(lab.data(), n, groups);
+    FrameDets used;
+    for (int k = groups.first[groups.label[0] < 0 ? 1 : 0]; k < n; ++k) {
+        const double* b = boxes_xywh + (size_t)groups.order[k] * 4;
+        const double xyxy[4] = {b[0], b[1], b[2] + b[0], b[3] + b[1]};                      // modules/track.py:39-41
+        used.xyxy.insert(used.xyxy.end(), xyxy, xyxy + 4);
+        used.conf.push_back(scores[groups.order[k]]);
+        used.label.push_back(lab[groups.order[k]]);
     }
-    std::vector<int> ids, labs;
-    std::vector<std::vector<int>> groups;
-    for (int c = 0; c < num_classes; ++c) {                     // modules/track.py:50-59: classes without boxes are not stepped
-        std::vector<int> g;
-        for (int i = 0; i < n; ++i) if (labels[i] == c) g.push_back(i);
-        if (g.empty()) continue;
-        ids.push_back(trackers[c]); labs.push_back(c); groups.push_back(g);
-    }
-    // boxes of classes outside [0, num_classes) are ignored exactly like the reference's mask loop; embed only used boxes
     std::vector<int64_t> rows6;
-    if (!ids.empty()) {
-        std::vector<double> used_xyxy, used_conf;
-        std::vector<std::vector<int>> g2(groups.size());
-        for (size_t j = 0; j < groups.size(); ++j)
-            for (int i : groups[j]) {
-                g2[j].push_back((int)used_conf.size());
-                for (int c = 0; c < 4; ++c) used_xyxy.push_back(xyxy[(size_t)i * 4 + c]);
-                used_conf.push_back(scores[i]);
-            }
-        VC_TRY(frame_track(e, e->d_frames, 0, h, w, ids, labs, g2, used_xyxy.data(), used_conf.data(), (int)used_conf.size(), rows6));
-    }
+    if (!used.conf.empty()) VC_TRY(frame_track(e, e->d_frames, 0, h, w, trackers, num_classes, used, rows6));
     const int m = (int)(rows6.size() / 6);
     VC_CHECK(m <= cap_rows, VC_ERR_CAPACITY, "need room for %d rows", m);
     memcpy(out_rows6, rows6.data(), rows6.size() * sizeof(int64_t));
