@@ -511,6 +511,29 @@ int vc_bneck_fused_host(int b, int h, int w, const vc_fused_view* v, float* x, c
                         const float* w3, const float* b3, float* y, float* z);
 /* ReID BasicBlock(64 -> 64) on k maps of h x w (the kernel takes 25 x 25): w1, w2 [64][64][3][3] */
 int vc_reid_block_fused_host(int k, int h, int w, const vc_fused_view* v, float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* y);
+/* The kernels that open a detector pass (bf16) as ONE launch on host arrays, without an engine: the direct stem (stem_direct_kernel<CT>,
+ * stem_direct_wide_kernel<5>; 6x6 / s2 / p2 + SiLU, cout = 16 CT) and layers 0 + 1 in one kernel (front_fused_kernel; stem to 32 channels, then
+ * 3x3 / s2 / p1 + SiLU to 64).  The network input is EITHER x, the letterboxed tensor [b][net_h][net_w][3] as floats (rounded to bf16 into
+ * the 4-channel pair view the plan builds; frames NULL), OR frames, b packed u8 frames [h][w][3] whose letterbox into net_h x net_w (the
+ * engine's own geometry) the kernel folds in (x NULL).  net_w is even.  The ConvPs are filled as the plan fills them; inputs and outputs lie
+ * between guard blocks, the frames' base is 4-byte aligned; a launch that writes an input, a guard block or -- direct launches -- the
+ * letterboxed tensor or layer 0 is VC_ERR_HIP.  A launcher's own refusal is VC_ERR_ARG and leaves every array as passed. */
+typedef struct vc_front_view {
+    int out_cs, out_co;              /* the output: channels [out_co, out_co + cout) of y */
+    int q_cs, q_co;                  /* stem, q8 != NULL: the e4m3 copy of the output the fp8 engine's stem writes, bytes [q_co, q_co + cout) of q8 */
+    float inv_scale;                 /* ... of value x inv_scale */
+    int swap_rb;                     /* frames: channels 0 and 2 exchanged inside the image */
+    int mode;                        /* 1: the direct launcher (launch_stem_direct / launch_stem_direct_u8 / launch_front_fused; the tensor input
+                                        gives front_fused_kernel<false>); 0: the same ConvPs through launch_conv (VC_CONV_CFG, VC_CONV_STRICT as for
+                                        vc_conv2d_host), behind launch_letterbox for frames, followed by the bf16 -> fp8 launch under q8 */
+    int grid_cap;                    /* mode 1, > 0: at most this many workgroups, which then walk all tiles; 0 = the product's grid */
+} vc_front_view;
+/* w0 [cout][3][6][6], b0 [cout]; y [b][net_h / 2][net_w / 2][out_cs] and q8 [b][net_h / 2][net_w / 2][q_cs] (nullable) are in AND out */
+int vc_stem_host(int b, int net_h, int net_w, int cout, const vc_front_view* v, const float* x, const uint8_t* frames, int h, int w, const float* w0,
+                 const float* b0, float* y, uint8_t* q8);
+/* w0 [32][3][6][6], w1 [cout1][32][3][3] (the kernel takes cout1 = 64); y [b][h1][w1][out_cs], h1 = (net_h / 2 - 1) / 2 + 1, in AND out */
+int vc_front_fused_host(int b, int net_h, int net_w, int cout1, const vc_front_view* v, const float* x, const uint8_t* frames, int h, int w, const float* w0,
+                        const float* b0, const float* w1, const float* b1, float* y);
 int vc_kalman_initiate_host(const double* xyah, int n, double* mean8, double* cov64);
 int vc_kalman_predict_host(double* mean8, double* cov64, int n);
 int vc_kalman_update_host(double* mean8, double* cov64, const double* z4, int n);

@@ -63,6 +63,12 @@ class FusedView(C.Structure):
                 ("grid", C.c_int)]
 
 
+class FrontView(C.Structure):
+    """vc_front_view: output view, e4m3 view and switches of vc_stem_host / vc_front_fused_host."""
+    _fields_ = [("out_cs", C.c_int), ("out_co", C.c_int), ("q_cs", C.c_int), ("q_co", C.c_int), ("inv_scale", C.c_float), ("swap_rb", C.c_int),
+                ("mode", C.c_int), ("grid_cap", C.c_int)]
+
+
 class YuvDesc(C.Structure):
     """vc_yuv_desc: byte geometry of 4:2:0 frames, 0 = tightly packed."""
     _fields_ = [("format", C.c_int), ("matrix", C.c_int), ("full_range", C.c_int), ("pitch_y", C.c_int), ("pitch_c", C.c_int),
@@ -197,6 +203,8 @@ SIGNATURES = {
     "vc_c3_fused_host": [_i, _i, _i, _P(FusedView), _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf],
     "vc_bneck_fused_host": [_i, _i, _i, _P(FusedView), _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf, _pf],
     "vc_reid_block_fused_host": [_i, _i, _i, _P(FusedView), _pf, _pf, _pf, _pf, _pf, _pf],
+    "vc_stem_host": [_i, _i, _i, _i, _P(FrontView), _pf, _pu8, _i, _i, _pf, _pf, _pf, _pu8],
+    "vc_front_fused_host": [_i, _i, _i, _i, _P(FrontView), _pf, _pu8, _i, _i, _pf, _pf, _pf, _pf, _pf],
     "vc_kalman_initiate_host": [_pd, _i, _pd, _pd],
     "vc_kalman_predict_host": [_pd, _pd, _i],
     "vc_kalman_update_host": [_pd, _pd, _pd, _i],

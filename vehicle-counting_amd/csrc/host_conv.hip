@@ -1,5 +1,5 @@
 // The convolution kernels on host arrays (include/vcount_hip.h): one launch_conv under the launch views, the stride-2 + pointwise pair, the
-// fused C3 / Bottleneck / ReID blocks and the ReID stem.  Entry points only: each stages NumPy-style arrays (host_stage.h), fills its ConvPs
+// fused C3 / Bottleneck / ReID blocks, the detector's stem and fused front, and the ReID stem.  Entry points only: each stages NumPy-style arrays (host_stage.h), fills its ConvPs
 // with the engine's own conv_params (engine_plan.hip), runs one launcher and reads the result back.  None of them touches a vc_engine.
 #include <algorithm>
 #include <cstdlib>
@@ -156,6 +156,46 @@ bool fused_shape_ok(int b, int h, int w) { return b >= 1 && h >= 1 && w >= 1 && 
 size_t tile_guard(int w, int cs) { return ((size_t)(8 * w + 16) * cs * 2 + 255) / 256 * 256; }
 // channels [co, co + n) inside a pixel of cs channels
 bool fused_slice_ok(int cs, int co, int n) { return co >= 0 && cs >= co + n && cs <= 4096; }
+
+// ---- the stem and the fused front (include/vcount_hip.h: vc_front_view) ---------------------------------------------------------------------
+// The network input of both entry points, as run_detector_dev hands it to the plan: the letterboxed tensor [b][net_h][net_w][4] bf16 (channel 3
+// zero; the pair view reads it as net_w / 2 pixels of 8 channels) from the caller's floats, or u8 frames whose letterbox the kernel folds in
+// (mode 0: launch_letterbox writes the tensor).  Inputs lie between guard blocks of 0xFF: a bf16 NaN, the byte 255.
+struct FrontInput {
+    GuardedOut tensor, frames;
+    std::vector<uint8_t> before;         // the bytes of the input the kernels read
+    LetterboxGeom g{};
+    bool u8 = false;
+    const GuardedOut& in() const { return u8 ? frames : tensor; }
+};
+int front_input(DevScratch& mem, FrontInput& fi, int b, int net_h, int net_w, const float* x, const uint8_t* frames, int h, int w, int swap_rb) {
+    const size_t npix = (size_t)b * net_h * net_w;
+    fi.u8 = frames != nullptr;
+    if (fi.u8) {
+        fi.g = letterbox_geom(h, w, net_h, net_w, swap_rb != 0);
+        fi.before.assign(frames, frames + (size_t)b * h * w * 3);
+        VC_TRY(fi.frames.alloc(mem, fi.before.size(), fi.before.data(), GuardedOut::kGuard, 0xFF));   // (the base is 256-byte aligned: the front kernel wants 4)
+        return fi.tensor.alloc(mem, npix * 4 * 2);                                                    // all fill: no direct launch may touch it
+    }
+    std::vector<float> x4(npix * 4, 0.f);
+    for (size_t i = 0; i < npix; ++i)
+        for (int c = 0; c < 3; ++c) x4[i * 4 + c] = x[i * 3 + c];
+    fi.before = to_elems(x4.data(), x4.size(), PREC_BF16);
+    return fi.tensor.alloc(mem, fi.before.size(), fi.before.data(), GuardedOut::kGuard, 0xFF);
+}
+// after the launches: the input and its guard blocks are what they were
+int front_input_intact(const FrontInput& fi, const char* kernel) {
+    std::vector<uint8_t> now(fi.in().bytes);
+    VC_TRY(fi.in().read_back(now.data(), kernel));
+    VC_CHECK(now == fi.before, VC_ERR_HIP, "%s wrote its input", kernel);
+    return VC_OK;
+}
+bool front_args_ok(int b, int net_h, int net_w, const float* x, const uint8_t* frames, int h, int w) {
+    return b >= 1 && net_h >= 2 && net_w >= 2 && net_w % 2 == 0 && (long long)b * net_h * net_w <= (1 << 22) && (x != nullptr) != (frames != nullptr) &&
+           (!frames || (h >= 1 && w >= 1 && (long long)b * h * w <= (1 << 24)));
+}
+// guard blocks that hold every store of a th x tw output tile that lost its bounds tests (pixels of `bytes_per_pixel`)
+size_t front_guard(int th, int tw, int wo, size_t bytes_per_pixel) { return ((size_t)(th * wo + tw) * bytes_per_pixel + 255) / 256 * 256; }
 
 }  // namespace
 
@@ -357,6 +397,89 @@ int vc_reid_block_fused_host(int k, int h, int w, const vc_fused_view* v, float*
     VC_TRY(read_elems(gx, nx, PREC_BF16, x, "reid_block_fused_kernel (the input buffer)"));
     if (!v->out_buf) VC_TRY(read_elems(gy, ny, PREC_BF16, y, "reid_block_fused_kernel"));
     return VC_OK;
+}
+
+int vc_stem_host(int b, int net_h, int net_w, int cout, const vc_front_view* v, const float* x, const uint8_t* frames, int h, int w, const float* w0,
+                 const float* b0, float* y, uint8_t* q8) {
+    VC_CHECK(v && w0 && b0 && y, VC_ERR_ARG, "null argument");
+    set_error("%s", "");                               // the launchers refuse a shape without a message: the caller must not read an older one
+    VC_CHECK(front_args_ok(b, net_h, net_w, x, frames, h, w) && cout >= 1 && cout <= 1024 && v->grid_cap >= 0 && (v->mode == 0 || v->mode == 1), VC_ERR_ARG,
+             "stem: bad shape");
+    VC_CHECK(fused_slice_ok(v->out_cs, v->out_co, cout) && (!q8 || fused_slice_ok(v->q_cs, v->q_co, cout)), VC_ERR_ARG, "stem: a slice lies outside its stride");
+    const int Ho = (net_h + 4 - 6) / 2 + 1, Wo = (net_w + 4 - 6) / 2 + 1;
+    const size_t npix = (size_t)b * Ho * Wo, ny = npix * v->out_cs, nq = npix * (size_t)v->q_cs;
+    DevScratch mem;
+    ConvParam P;
+    P.pair_stem = true;                                // yolo_define: the stem of every bf16 engine (and of the fp8 one)
+    VC_TRY(host_param(mem, P, "model.0.conv", cout, 3, 6, 6, w0, b0));
+    FrontInput fi;
+    VC_TRY(front_input(mem, fi, b, net_h, net_w, x, frames, h, w, v->swap_rb));
+    GuardedOut gy, gq;
+    VC_TRY(guarded_elems(mem, gy, y, ny, PREC_BF16, front_guard(8, 32, Wo, (size_t)v->out_cs * 2)));
+    if (q8) VC_TRY(gq.alloc(mem, nq, q8, front_guard(8, 32, Wo, (size_t)v->q_cs)));
+    ConvP c = conv_params(P, {fi.tensor.out(), 8, 0}, {gy.out(), v->out_cs, v->out_co}, b, net_h, net_w, 6, 6, 2, 2, ACT_SILU, 1.0f, 1.0f);
+    const View yv{gy.out(), b, Ho, Wo, cout, v->out_cs, v->out_co, 2}, qv{q8 ? gq.out() : nullptr, b, Ho, Wo, cout, v->q_cs, v->q_co, 1};
+    const char* kernel = v->mode == 0 ? "the unfused stem" : cout == 80 ? "stem_direct_wide_kernel" : "stem_direct_kernel";
+    if (v->mode == 1) {                                // refused: y / q8 as passed
+        if (fi.u8) VC_TRY(launch_stem_direct_u8(c, fi.frames.out(), fi.g, nullptr, q8 ? &qv : nullptr, v->inv_scale, v->grid_cap));
+        else if (!stem_direct_applicable(c)) return VC_ERR_ARG;
+        else VC_TRY(launch_stem_direct(c, nullptr, q8 ? &qv : nullptr, v->inv_scale, v->grid_cap));
+    } else {                                           // what the engine runs with option "stem_direct" 0: letterbox, launch_conv, the bf16 -> fp8 launch
+        conv_env(c, true);
+        if (fi.u8) VC_TRY(launch_letterbox(fi.frames.out(), fi.tensor.out(), b, fi.g, PREC_BF16, nullptr));
+        VC_TRY(launch_conv(c, nullptr));
+        if (q8) VC_TRY(launch_bf16_to_fp8(yv, qv, v->inv_scale, nullptr));
+    }
+    VC_TRY(kernel_wait(kernel));
+    VC_TRY(front_input_intact(fi, kernel));
+    if (fi.u8 && v->mode == 1) VC_TRY(still_filled(fi.tensor, kernel, "the letterboxed tensor"));
+    std::vector<uint8_t> qh(nq);                       // both outputs checked before either array of the caller changes
+    if (q8) VC_TRY(gq.read_back(qh.data(), kernel));
+    VC_TRY(read_elems(gy, ny, PREC_BF16, y, kernel));
+    if (q8) memcpy(q8, qh.data(), nq);
+    return VC_OK;
+}
+
+int vc_front_fused_host(int b, int net_h, int net_w, int cout1, const vc_front_view* v, const float* x, const uint8_t* frames, int h, int w, const float* w0,
+                        const float* b0, const float* w1, const float* b1, float* y) {
+    VC_CHECK(v && w0 && b0 && w1 && b1 && y, VC_ERR_ARG, "null argument");
+    set_error("%s", "");
+    VC_CHECK(front_args_ok(b, net_h, net_w, x, frames, h, w) && net_h >= 4 && net_w >= 4 && cout1 >= 1 && cout1 <= 1024 && v->grid_cap >= 0 && (v->mode == 0 || v->mode == 1),
+             VC_ERR_ARG, "front fused: bad shape");
+    VC_CHECK(fused_slice_ok(v->out_cs, v->out_co, cout1), VC_ERR_ARG, "front fused: a slice lies outside its stride");
+    constexpr int C0 = 32;
+    const int H0 = (net_h + 4 - 6) / 2 + 1, W0 = (net_w + 4 - 6) / 2 + 1, H1 = (H0 + 2 - 3) / 2 + 1, W1 = (W0 + 2 - 3) / 2 + 1;
+    const size_t npix0 = (size_t)b * H0 * W0, ny = (size_t)b * H1 * W1 * v->out_cs;
+    DevScratch mem;
+    ConvParam P0, P1;
+    P0.pair_stem = true;
+    VC_TRY(host_param(mem, P0, "model.0.conv", C0, 3, 6, 6, w0, b0));
+    VC_TRY(host_param(mem, P1, "model.1.conv", cout1, C0, 3, 3, w1, b1));
+    FrontInput fi;
+    VC_TRY(front_input(mem, fi, b, net_h, net_w, x, frames, h, w, v->swap_rb));
+    GuardedOut gl0, gy;                                // gl0: layer 0, which the fused kernel keeps on chip (ybuf["l0"])
+    VC_TRY(gl0.alloc(mem, npix0 * C0 * 2));
+    VC_TRY(guarded_elems(mem, gy, y, ny, PREC_BF16, front_guard(16, 16, W1, (size_t)v->out_cs * 2)));
+    ConvP p0 = conv_params(P0, {fi.tensor.out(), 8, 0}, {gl0.out(), C0, 0}, b, net_h, net_w, 6, 6, 2, 2, ACT_SILU, 1.0f, 1.0f);
+    ConvP p1 = conv_params(P1, {gl0.out(), C0, 0}, {gy.out(), v->out_cs, v->out_co}, b, H0, W0, 3, 3, 2, 1, ACT_SILU, 1.0f, 1.0f);
+    const char* kernel = v->mode == 0 ? "the unfused front" : "front_fused_kernel";
+    if (v->mode == 1) {                                // refused: y as passed
+        if (!front_fused_applicable(p0, p1)) return VC_ERR_ARG;
+        p0.slots = v->grid_cap;                        // the field the engine's conv_slots uses; tile_ctr stays null: the fixed stride
+        VC_TRY(launch_front_fused(p0, p1, fi.u8 ? fi.frames.out() : nullptr, fi.g, nullptr));
+    } else {
+        conv_env(p0, false); conv_env(p1, false);
+        if (fi.u8) VC_TRY(launch_letterbox(fi.frames.out(), fi.tensor.out(), b, fi.g, PREC_BF16, nullptr));
+        VC_TRY(launch_conv(p0, nullptr));
+        VC_TRY(launch_conv(p1, nullptr));
+    }
+    VC_TRY(kernel_wait(kernel));
+    VC_TRY(front_input_intact(fi, kernel));
+    if (v->mode == 1) {
+        VC_TRY(still_filled(gl0, kernel, "layer 0"));
+        if (fi.u8) VC_TRY(still_filled(fi.tensor, kernel, "the letterboxed tensor"));
+    }
+    return read_elems(gy, ny, PREC_BF16, y, kernel);
 }
 
 int vc_reid_stem_pool_host(const float* crops, int k, const float* w, const float* bias, float* out) {

@@ -39,13 +39,16 @@ struct GuardedOut {
     static constexpr size_t kGuard = 256;
     uint8_t* base = nullptr;
     size_t bytes = 0, guard = kGuard;
+    uint8_t fill = 0xA5;
     // out_bytes + 2 guard blocks, all 0xA5; with `preload` the output starts as the caller's array.  guard_bytes (a multiple of 256): a
-    // caller that knows how far a kernel without its bounds tests would stray (a tile's overhang) asks for blocks that hold all of it
-    int alloc(DevScratch& mem, size_t out_bytes, const void* preload = nullptr, size_t guard_bytes = kGuard) {
+    // caller that knows how far a kernel without its bounds tests would stray (a tile's overhang) asks for blocks that hold all of it.
+    // fill_byte: an INPUT between guard blocks takes 0xFF -- a bf16 NaN, the byte 255 -- so that a read outside it shows in the result
+    int alloc(DevScratch& mem, size_t out_bytes, const void* preload = nullptr, size_t guard_bytes = kGuard, uint8_t fill_byte = 0xA5) {
         bytes = out_bytes;
         guard = guard_bytes;
+        fill = fill_byte;
         VC_TRY(mem.alloc(&base, bytes + 2 * guard));
-        VC_HIP(hipMemset(base, 0xA5, bytes + 2 * guard));
+        VC_HIP(hipMemset(base, fill, bytes + 2 * guard));
         if (preload) VC_HIP(hipMemcpy(out(), preload, bytes, hipMemcpyHostToDevice));
         return VC_OK;
     }
@@ -56,7 +59,7 @@ struct GuardedOut {
         std::vector<uint8_t> all(bytes + 2 * guard);
         VC_CHECK(hipMemcpy(all.data(), base, all.size(), hipMemcpyDeviceToHost) == hipSuccess, VC_ERR_HIP, "%s failed: %s", kernel, hipGetErrorString(hipGetLastError()));
         memcpy(host_out, all.data() + guard, bytes);
-        for (size_t i = 0; i < 2 * guard; ++i) VC_CHECK(all[i < guard ? i : bytes + i] == 0xA5, VC_ERR_HIP, "%s wrote outside its output (guard byte %zu)", kernel, i);
+        for (size_t i = 0; i < 2 * guard; ++i) VC_CHECK(all[i < guard ? i : bytes + i] == fill, VC_ERR_HIP, "%s wrote outside its output (guard byte %zu)", kernel, i);
         return VC_OK;
     }
 };

@@ -162,15 +162,17 @@ bool stem_direct_applicable(const ConvP& p) {
            p.Cout <= 80 && p.Kp >= 160 && p.out_cs % 8 == 0 && p.out_co % 8 == 0;
 }
 
-int launch_stem_direct_wide(const ConvP& p, const uint8_t* src8, const LetterboxGeom& g, int tiles_x, int tiles_y, hipStream_t s);   // stem_direct_wide.hip: Cout = 80
+int launch_stem_direct_wide(const ConvP& p, const uint8_t* src8, const LetterboxGeom& g, int tiles_x, int tiles_y, hipStream_t s, int grid_cap);   // stem_direct_wide.hip: Cout = 80
 
-static int launch_stem_impl(const ConvP& p, const uint8_t* src8, const LetterboxGeom& g, hipStream_t s, const View* q8 = nullptr, float q_inv_scale = 1.0f) {
+static int launch_stem_impl(const ConvP& p, const uint8_t* src8, const LetterboxGeom& g, hipStream_t s, const View* q8, float q_inv_scale, int grid_cap) {
     uint8_t* y8 = q8 ? (uint8_t*)q8->ptr : nullptr;
     const int q_cs = q8 ? q8->cs : 0, q_co = q8 ? q8->co : 0;
     const int tiles_x = (p.Wo + STEM_TW - 1) / STEM_TW, tiles_y = (p.Ho + STEM_TH - 1) / STEM_TH;
-    if (p.Cout == 80) return q8 ? VC_ERR_ARG : launch_stem_direct_wide(p, src8, g, tiles_x, tiles_y, s);     // (no fp8 engine has an 80-channel stem)
+    if (p.Cout == 80) return q8 ? VC_ERR_ARG : launch_stem_direct_wide(p, src8, g, tiles_x, tiles_y, s, grid_cap);     // (no fp8 engine has an 80-channel stem)
+    // the e4m3 copy leaves as 8-byte stores at q_co + 16 ct + 0 / 8
+    if (q8 && (q_cs % 8 != 0 || q_co % 8 != 0 || q_co < 0)) { set_error("stem_direct: the e4m3 view (stride %d, offset %d) must be 8-channel aligned", q_cs, q_co); return VC_ERR_ARG; }
     const int ntiles = p.B * tiles_x * tiles_y;
-    const int grid = std::min(ntiles, 256 * 3 - 64); // 3 workgroups per CU can be resident (VGPRs); 64 slots stay free for the tracker stream (conv_launch.h)
+    const int grid = grid_cap > 0 ? std::min(ntiles, grid_cap) : std::min(ntiles, 256 * 3 - 64); // 3 workgroups per CU can be resident (VGPRs); 64 slots stay free for the tracker stream (conv_launch.h)
     const uint4* x = (const uint4*)p.in; const uint4* w = (const uint4*)p.w;
     uint16_t* y = (uint16_t*)p.out;
     const int kw8 = p.Kp / 8;
@@ -191,7 +193,7 @@ static int launch_stem_impl(const ConvP& p, const uint8_t* src8, const Letterbox
     return VC_OK;
 }
 
-int launch_stem_direct(const ConvP& p, hipStream_t s, const View* q8, float q_inv_scale) { return launch_stem_impl(p, nullptr, LetterboxGeom{}, s, q8, q_inv_scale); }
+int launch_stem_direct(const ConvP& p, hipStream_t s, const View* q8, float q_inv_scale, int grid_cap) { return launch_stem_impl(p, nullptr, LetterboxGeom{}, s, q8, q_inv_scale, grid_cap); }
 
 // no-resize geometry only (the frame is already at network scale), pairs never straddle the image edge (even left pad and
 // width), 2-byte aligned pair reads (even source width)
@@ -200,9 +202,9 @@ bool stem_u8_applicable(const ConvP& p, const LetterboxGeom& g) {
            g.net_h == p.H && g.net_w == 2 * p.W;
 }
 
-int launch_stem_direct_u8(const ConvP& p, const uint8_t* frames, const LetterboxGeom& g, hipStream_t s, const View* q8, float q_inv_scale) {
+int launch_stem_direct_u8(const ConvP& p, const uint8_t* frames, const LetterboxGeom& g, hipStream_t s, const View* q8, float q_inv_scale, int grid_cap) {
     if (!frames || !stem_u8_applicable(p, g)) return VC_ERR_ARG;
-    return launch_stem_impl(p, frames, g, s, q8, q_inv_scale);
+    return launch_stem_impl(p, frames, g, s, q8, q_inv_scale, grid_cap);
 }
 
 }  // namespace vc

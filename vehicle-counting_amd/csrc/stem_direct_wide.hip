@@ -164,10 +164,10 @@ __global__ __launch_bounds__(256, 2) void stem_direct_wide_kernel(const uint4* _
 }
 
 // called by launch_stem_impl (stem_direct.hip), which has checked applicability and computed the tiling
-int launch_stem_direct_wide(const ConvP& p, const uint8_t* src8, const LetterboxGeom& g, int tiles_x, int tiles_y, hipStream_t s) {
+int launch_stem_direct_wide(const ConvP& p, const uint8_t* src8, const LetterboxGeom& g, int tiles_x, int tiles_y, hipStream_t s, int grid_cap) {
     if (p.Cout != 80) return VC_ERR_ARG;
     const int ntiles = p.B * tiles_x * tiles_y;
-    const int grid = std::min(ntiles, 256 * 2 - 64);     // 2 workgroups per CU can be resident (VGPRs); 64 slots stay free for the tracker stream (conv_launch.h)
+    const int grid = grid_cap > 0 ? std::min(ntiles, grid_cap) : std::min(ntiles, 256 * 2 - 64);     // 2 workgroups per CU can be resident (VGPRs); 64 slots stay free for the tracker stream (conv_launch.h)
     const uint4* x = (const uint4*)p.in; const uint4* w = (const uint4*)p.w;
     uint16_t* y = (uint16_t*)p.out;
     const int kw8 = p.Kp / 8;

@@ -220,11 +220,11 @@ int conv_num_cfgs();
 bool conv_stream_cfg(int cfg);                               // conv1x1_stream_kernel variants: offered to the autotuner only under VC_CONV_STREAM=1
 bool stem_direct_applicable(const ConvP& p);                    // stem_direct.hip: YOLO 6x6/s2 stem in bf16
 struct View;
-int launch_stem_direct(const ConvP& p, hipStream_t s, const View* q8 = nullptr, float q_inv_scale = 1.0f);   // q8: also write the e4m3 copy of the output
+int launch_stem_direct(const ConvP& p, hipStream_t s, const View* q8 = nullptr, float q_inv_scale = 1.0f, int grid_cap = 0);   // q8: also write the e4m3 copy of the output (8-channel-aligned view); grid_cap (both stem launchers): tests only, 0 = the product's grid
 struct LetterboxGeom;
 // the same with the letterbox folded into the patch fetch: reads the u8 frames directly (no-resize geometry, even source width)
 bool stem_u8_applicable(const ConvP& p, const LetterboxGeom& g);
-int launch_stem_direct_u8(const ConvP& p, const uint8_t* frames, const LetterboxGeom& g, hipStream_t s, const View* q8 = nullptr, float q_inv_scale = 1.0f);
+int launch_stem_direct_u8(const ConvP& p, const uint8_t* frames, const LetterboxGeom& g, hipStream_t s, const View* q8 = nullptr, float q_inv_scale = 1.0f, int grid_cap = 0);
 // front_fused.hip: YOLO layers 0 + 1 (stem + 3x3 / s2) in one kernel, the stem's output never leaves the CU
 bool c3_fused_applicable(const ConvP& p12, const ConvP& pm1, const ConvP& pm2, const ConvP& p3);     // c3_fused.hip: the first C3 block (64 -> 64, n = 1) in one kernel
 int launch_c3_fused(const ConvP& p12, const ConvP& pm1, const ConvP& pm2, const ConvP& p3, hipStream_t s, int grid_cap = 0);    // grid_cap (all four block launchers): tests only, 0 = the product's grid

@@ -582,6 +582,64 @@ def fused_block(kind, x, weights, *, view, y=None, z=None):
     return x, y, z
 
 
+def _front_call(inp, net, view, y):
+    """shared by stem / front_fused: (b, net_h, net_w, x, frames, h, w, vc_front_view, copy of y)"""
+    a = np.asarray(inp)
+    if a.dtype == np.uint8:
+        frames, x = np.ascontiguousarray(a), None
+        b, h, w = frames.shape[:3]
+        net_h, net_w = net
+    else:
+        frames, x = None, L.f32(a)
+        b, net_h, net_w = x.shape[:3]
+        h = w = 0
+        assert net is None or tuple(net) == (net_h, net_w)
+    assert a.ndim == 4 and a.shape[3] == 3
+    y = L.f32(y).copy()
+    v = L.FrontView(out_cs=y.shape[3], inv_scale=1.0, mode=1)
+    for k, val in view.items():
+        if not hasattr(v, k):
+            raise KeyError(k)
+        setattr(v, k, float(val) if k == "inv_scale" else int(val))
+    return b, net_h, net_w, x, frames, h, w, v, y
+
+
+def stem(inp, w0, b0, y, *, view, net=None, q8=None):
+    """One launch of the detector's stem on WHOLE buffers (vc_stem_host, bf16).  inp: the letterboxed tensor (b, net_h, net_w, 3) as floats, or
+    uint8 frames (b, h, w, 3) with net = (net_h, net_w).  w0 (cout, 3, 6, 6), b0 (cout,).  y (b, net_h / 2, net_w / 2, out_cs) and q8 (the
+    e4m3 view, uint8 (b, net_h / 2, net_w / 2, q_cs), or None) are uploaded, launched into and returned as copies (y, q8).  `view`: the other
+    vc_front_view fields.  A refusal raises VcError with the arrays as the call left them in err.outputs."""
+    b, net_h, net_w, x, frames, h, w, v, y = _front_call(inp, net, view, y)
+    w0, b0 = L.f32(w0), L.f32(b0)
+    assert w0.shape[1:] == (3, 6, 6) and b0.shape == (len(w0),) and y.shape[:3] == (b, net_h // 2, net_w // 2)
+    if q8 is not None:
+        q8 = np.ascontiguousarray(q8, dtype=np.uint8).copy()
+        assert q8.shape[:3] == y.shape[:3]
+        v.q_cs = q8.shape[3]
+    try:
+        L.check(L.lib().vc_stem_host(b, net_h, net_w, len(w0), C.byref(v), L.ptr(x, C.c_float), L.ptr(frames, C.c_uint8), h, w, L.ptr(w0, C.c_float),
+                                     L.ptr(b0, C.c_float), L.ptr(y, C.c_float), L.ptr(q8, C.c_uint8)))
+    except L.VcError as err:
+        err.outputs = (y, q8)
+        raise
+    return y, q8
+
+
+def front_fused(inp, w0, b0, w1, b1, y, *, view, net=None):
+    """One launch of the detector's layers 0 + 1 on WHOLE buffers (vc_front_fused_host, bf16): inp and `view` as for stem, w0 (32, 3, 6, 6),
+    w1 (cout1, 32, 3, 3); y (b, h1, w1, out_cs) is uploaded, launched into and returned as a copy."""
+    b, net_h, net_w, x, frames, h, w, v, y = _front_call(inp, net, view, y)
+    w0, b0, w1, b1 = L.f32(w0), L.f32(b0), L.f32(w1), L.f32(b1)
+    assert w0.shape == (32, 3, 6, 6) and w1.shape[1:] == (32, 3, 3) and y.shape[:3] == (b, (net_h // 2 - 1) // 2 + 1, (net_w // 2 - 1) // 2 + 1)
+    try:
+        L.check(L.lib().vc_front_fused_host(b, net_h, net_w, len(w1), C.byref(v), L.ptr(x, C.c_float), L.ptr(frames, C.c_uint8), h, w, L.ptr(w0, C.c_float),
+                                            L.ptr(b0, C.c_float), L.ptr(w1, C.c_float), L.ptr(b1, C.c_float), L.ptr(y, C.c_float)))
+    except L.VcError as err:
+        err.outputs = (y, None)
+        raise
+    return y
+
+
 def kalman_initiate(xyah):
     z = L.f64(xyah).reshape(-1, 4)
     m, c = np.zeros((len(z), 8)), np.zeros((len(z), 8, 8))
