@@ -29,6 +29,7 @@
 
 #include "kernels.h"
 #include "conv_launch.h"
+#include "tile_sched.h"
 
 namespace vc {
 
@@ -72,6 +73,7 @@ struct BnArgs {
     const uint16_t* y2; int y2_cs;
     uint16_t* z; int z_cs, z_co;
     long long* dbg;                        // diagnostics (VC_BN_DBG): per workgroup its first and last wall_clock64(); null in production
+    unsigned* ctr;                         // this launch's counter pair (vc_common.h: tile_claim_chunk); null = the fixed stride
 };
 
 // Two groups of four waves work on DIFFERENT tiles at the same time: the producers (waves 4-7) compute b1 of tile k + 1 -- few MFMAs,
@@ -87,7 +89,8 @@ __global__ __launch_bounds__(BN_NW * 64) void bneck_fused_kernel(const BnArgs a)
     __shared__ uint4 w2s[18 * 4 * 64];                     // 72 KB: cv2, [k step = 2 tap + half][channel tile][lane]
     __shared__ uint4 w3s[CV3 ? 4 * 8 * 64 : 1];            // CV3: 32 KB: cv3, [k step][channel tile][lane]
     __shared__ float b3s[CV3 ? 128 : 4];                   // CV3: cv3's bias: its epilogue reads it BETWEEN the tile's stores, where a global load would wait for them
-    static_assert(sizeof(bs) + sizeof(w1s) + sizeof(w2s) + sizeof(w3s) + sizeof(b3s) <= 160 * 1024, "static LDS of bneck_fused_kernel exceeds a CU's 160 KB");
+    __shared__ int tq[4];                                  // the tiles of steps k - 1 .. k + 2, slot = step & 3 (below: the tile walk)
+    static_assert(sizeof(bs) + sizeof(w1s) + sizeof(w2s) + sizeof(w3s) + sizeof(b3s) + sizeof(tq) <= 160 * 1024, "static LDS of bneck_fused_kernel exceeds a CU's 160 KB");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = lane & 15, kq = lane >> 4;
     constexpr int NT = BN_NW * 64;
@@ -112,9 +115,32 @@ __global__ __launch_bounds__(BN_NW * 64) void bneck_fused_kernel(const BnArgs a)
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) bv[ct] = *(const float4*)((producer ? a.b1 : a.b2) + ct * 16 + kq * 4);
     const int ntiles = a.B * a.tiles_y * a.tiles_x;
-    const int nk = (int)blockIdx.x < ntiles ? (ntiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;     // tiles of this workgroup
     const bool odd = (kq & 1) != 0;
-    __syncthreads();                                        // weights are in LDS
+    // The tile walk.  Step k: the producers fill bs[k & 1] with tile T(k), the consumers convolve T(k - 1).  T(0) = blockIdx.x; the later
+    // ones are decided by ONE lane, the producers' first (the walker), two steps ahead, and travel through tq: in step k the walker writes
+    // T(k + 2) to tq[(k + 2) & 3], behind the step's barrier the producers read T(k + 1) (whose operands they fetch) and T(k + 2) is there for
+    // step k + 1; the consumers read T(k - 1) = tq[(k - 1) & 3], which the walker overwrites in step k + 1 at the earliest.  Four slots, every
+    // read and its next write a barrier apart, one workgroup barrier per tile as before.  A tile >= ntiles is the end mark for both groups.
+    // With a counter pair (a.ctr) T follows tile_sched.h's chunks: inside a chunk T + 1, at its end the first tile of the chunk the walker
+    // claimed ONE STEP EARLIER (the fetch_add's answer is read a tile later, never waited for in place); a workgroup that gets its CU late
+    // takes what is left.  Without one: T + gridDim.x, the fixed stride.  Nobody waits for another workgroup.
+    unsigned* const ctr = a.ctr;
+    const bool walker = threadIdx.x == 4 * 64;
+    int w_cur = 0, w_left = 0, w_pend = 0;                  // walker only: T(k + 1); tiles of its chunk behind it; the chunk index claimed last
+    if (walker) {
+        const int t0 = (int)blockIdx.x < ntiles ? (int)blockIdx.x : ntiles;
+        tq[0] = t0;
+        if (ctr) {
+            int len;
+            w_cur = tile_chunk(tile_claim_chunk(ctr), ntiles, (int)gridDim.x, &len);      // the one claim whose answer is needed at once
+            w_left = len - 1;
+            if (w_cur < ntiles && w_left == 0) w_pend = tile_claim_chunk(ctr);
+        } else {
+            w_cur = t0 < ntiles - (int)gridDim.x ? t0 + (int)gridDim.x : ntiles;
+        }
+        tq[1] = w_cur;
+    }
+    __syncthreads();                                        // weights and T(0), T(1) are in LDS
 
     // producers: the y fragments (MFMA B operands) of a tile's three pixel tiles of this wave, loaded one tile ahead
     uint4 yf[3][2], yn[3][2];
@@ -132,13 +158,30 @@ __global__ __launch_bounds__(BN_NW * 64) void bneck_fused_kernel(const BnArgs a)
             }
         }
     };
-    if (producer && nk > 0) load_y(blockIdx.x, yf);
-    for (int k = 0; k <= nk; ++k) {
+    if (producer && (int)blockIdx.x < ntiles) load_y(blockIdx.x, yf);
+    for (int k = 0;; ++k) {
+        const int tk = __builtin_amdgcn_readfirstlane(tq[k & 3]);            // T(k); the end mark: the producers have nothing left, the consumers one tile
         if (producer) {
-            if (k < nk) {
-                // ---- cv1 (1x1) of tile k on its halo region -> bs[k & 1]; pixels outside the image hold 0 (the 3x3 pads b1 with zeros) ------
-                const int t = blockIdx.x + k * gridDim.x;
-                if (k + 1 < nk) load_y(t + gridDim.x, yn);
+            if (tk < ntiles) {
+                // ---- cv1 (1x1) of tile T(k) on its halo region -> bs[k & 1]; pixels outside the image hold 0 (the 3x3 pads b1 with zeros) ---
+                const int t = tk;
+                const int t1 = __builtin_amdgcn_readfirstlane(tq[(k + 1) & 3]);
+                if (walker) {                               // T(k + 2)
+                    int nx = ntiles;
+                    if (w_cur < ntiles) {
+                        if (!ctr) nx = w_cur < ntiles - (int)gridDim.x ? w_cur + (int)gridDim.x : ntiles;
+                        else if (w_left > 0) { nx = w_cur + 1; --w_left; }
+                        else {
+                            int len;
+                            nx = tile_chunk(w_pend, ntiles, (int)gridDim.x, &len);
+                            w_left = len - 1;
+                        }
+                        if (ctr && nx < ntiles && w_left == 0) w_pend = tile_claim_chunk(ctr);   // nx ends its chunk: read in the next step
+                    }
+                    tq[(k + 2) & 3] = nx;
+                    w_cur = nx;
+                }
+                if (t1 < ntiles) load_y(t1, yn);
                 const int tx = t % a.tiles_x, ty = (t / a.tiles_x) % a.tiles_y;
                 char* bsb = (char*)bs[k & 1];
                 // all 24 MFMAs first (12 independent accumulators), then the epilogues: the matrix pipe drains while the VALU / transcendental
@@ -180,7 +223,7 @@ __global__ __launch_bounds__(BN_NW * 64) void bneck_fused_kernel(const BnArgs a)
             }
         } else if (k >= 1) {
             // ---- cv2 (3x3) of tile k - 1 from bs[(k - 1) & 1] [+ shortcut] -> HBM: wave gw owns rows 2 gw, 2 gw + 1, all 64 channels -------
-            const int t = blockIdx.x + (k - 1) * gridDim.x;
+            const int t = __builtin_amdgcn_readfirstlane(tq[(k - 1) & 3]);       // T(k - 1) < ntiles: the loop ends behind the step whose T(k) is the end mark
             const int tx = t % a.tiles_x, ty = (t / a.tiles_x) % a.tiles_y, b = t / (a.tiles_x * a.tiles_y);
             const int oy0 = ty * BN_TH, ox0 = tx * BN_TW;
             const char* bsb = (const char*)bs[(k - 1) & 1];
@@ -344,8 +387,10 @@ __global__ __launch_bounds__(BN_NW * 64) void bneck_fused_kernel(const BnArgs a)
                 }
             }
         }
-        __syncthreads();                                    // bs[k & 1] is complete, bs[(k - 1) & 1] is free again
+        if (tk >= ntiles) break;                            // uniform: every thread read the same tq[k & 3]
+        __syncthreads();                                    // bs[k & 1] and tq[(k + 2) & 3] are complete, bs[(k - 1) & 1] is free again
     }
+    if (ctr && walker) tile_claims_done(ctr);
     if (a.dbg && threadIdx.x == 0) a.dbg[(size_t)blockIdx.x * 2 + 1] = wall_clock64();
 }
 
@@ -382,6 +427,9 @@ bool bneck_cv3_fused_applicable(const ConvP& pm1, const ConvP& pm2, const ConvP&
 // is left free: the kernel alone is ~14 % slower (28.6 instead of 25 tile rounds at 80^2), the step is 2.5 - 3.5 % faster (60-step runs on
 // one box, alternating: 18.36 / 18.42 / 18.47 k frames/s with 256 workgroups, 18.90 / 19.10 k with 224, 18.91 k with 192, 18.66 k with 240).
 // The same cap on front_fused_kernel (150 KB) and reid_block_fused_kernel (152 KB) stayed inside the run-to-run spread.
+// Re-measured with claimed tiles, whose grid has no reason of its own to hold CUs back (a workgroup that does not get its CU costs the
+// others nothing but its share): 256 against 224 workgroups, four alternating rounds of 100 steps at 256 frames: 23.35 / 23.41 / 23.35 /
+// 23.43 against 23.20 / 23.41 / 23.39 / 23.34 k frames/s -- inside each other's range, so 224 stays (profiles/dyn_tiles_blocks.md).
 static int bneck_grid_cap(int cus) {
     static const int forced = getenv("VC_BN_GRID") ? atoi(getenv("VC_BN_GRID")) : 0;      // A/B switch
     return forced > 0 ? forced : cus - cus / 8;
@@ -409,6 +457,7 @@ int launch_bneck_cv3_fused(const ConvP& pm1, const ConvP& pm2, const ConvP& p3, 
     if (grid_cap > 0) grid = std::min(grid, grid_cap);
     static WgStamps stamps("VC_BN_DBG", "bneck cv3", 1024, 2, 0, 1);
     a.dbg = stamps.next(grid, ntiles, s);
+    a.ctr = pm1.tile_ctr;
     launch_timed(pm1, bneck_fused_kernel<true>, dim3(grid), dim3(BN_NW * 64), 0, s, a);
     VC_HIP(hipGetLastError());
     if (a.dbg) stamps.report(s, [](const long long*, int, int) {});
@@ -436,6 +485,7 @@ int launch_bneck_fused(const ConvP& pm1, const ConvP& pm2, hipStream_t s, int gr
     a.res = pm2.res_mode == RES_AFTER_ACT ? 1 : 0;
     static WgStamps stamps("VC_BN_DBG", "bneck", 1024, 2, 0, 1);
     a.dbg = stamps.next(grid, ntiles, s);
+    a.ctr = pm1.tile_ctr;
     launch_timed(pm1, bneck_fused_kernel<false>, dim3(grid), dim3(BN_NW * 64), 0, s, a);
     VC_HIP(hipGetLastError());
     if (a.dbg) stamps.report(s, [](const long long*, int, int) {});

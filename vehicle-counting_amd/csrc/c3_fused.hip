@@ -21,6 +21,7 @@
 
 #include "kernels.h"
 #include "conv_launch.h"
+#include "tile_sched.h"
 
 namespace vc {
 
@@ -65,6 +66,7 @@ struct C3Args {
     int abl;                               // diagnostics (VC_C3_ABLATE, wrong results): 1 no transcendentals, 2 no global fetch, 4 no output stores,
                                            // 8 no 3x3 pass, 16 no cv12 pass, 32 no m.cv1 pass, 64 no cv3 pass
     long long* dbg;                        // diagnostics (VC_C3_DBG): per workgroup its first and last wall_clock64(); null in production
+    unsigned* ctr;                         // this launch's counter pair (vc_common.h: tile_claim_chunk); null = the fixed stride
 };
 
 template <bool DIAG>
@@ -120,11 +122,24 @@ __global__ __launch_bounds__(C3_NW * 64, 2) void c3_fused_kernel(const C3Args a)
     char* ybb = (char*)yb;
     char* ycb = (char*)yc;
     const bool odd = (kq & 1) != 0;
+    // Tiles after a workgroup's first are claimed in CHUNKS of consecutive tiles from the launch's counter pair (tile_sched.h: eights, then
+    // fours, pairs and single tiles at the end) when there is one; ctr == nullptr: the fixed stride.  Inside a chunk the next tile is t + 1
+    // (neighbours share halo rows in L2); the claim for the next chunk is issued by thread 0 where the fetch of the chunk's LAST tile is
+    // issued and read one tile later, where that tile's own next fetch is issued -- never waited for in place.
+    // One claim per 7 us tile (~ 70 claims per us on the one address) had slowed every tile down and lost the step 2 %; in chunks it is ~ 10
+    // claims per us, and per 256 frames (profiles/dyn_tiles_blocks.md): alone 0.819 -> 0.761 ms, because the workgroups now end together
+    // (the stride loop's p50 / p90 lifetimes were 600 / 780 us); inside the pipeline 1152 -> 843 us per launch on average (first start ->
+    // last end 1198 -> 836 us with workgroups late in 20 of 24 launches either way); the step + 1.1 % with this kernel's conversion on top
+    // of the front kernel's, + 2.4 % with the Bottleneck's too.
+    unsigned* const ctr = a.ctr;
+    int* const nxt_s = (int*)(ybb + (C3_NP - 1) * 64);    // {first tile, length} of the claimed chunk, thread 0 -> workgroup: pixel slot 191 of the y1 raster,
+                                                          // which no pass stores to (n < C3_NH) and whose reads are discarded; a word of its own would be
+                                                          // 81 924 B of LDS and the second workgroup per CU gone
+    int pend = 0;                                         // thread 0: the chunk index claimed last, not yet turned into tiles
+    if (ctr && threadIdx.x == 0) pend = tile_claim_chunk(ctr);
     if ((int)blockIdx.x < ntiles) fetch(blockIdx.x);
-    // (tiles claimed from a counter as in front_fused.hip, the claim issued one tile ahead: bit-identical, and late workgroups then took only
-    // their first tile, but 480 workgroups claiming a 7 us tile each slowed every tile down -- lifetimes 710 - 790 us where the stride loop has
-    // 600 (p50) - 780 (p90) -- and the step lost 2 % with this kernel alone converted; profiles/dyn_tiles.md)
-    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    int left = 0, tn;                                     // tiles of the current chunk behind t (the first tile is a chunk of one)
+    for (int t = blockIdx.x; t < ntiles; t = tn) {
         const int tx = t % a.tiles_x, ty = (t / a.tiles_x) % a.tiles_y, b = t / (a.tiles_x * a.tiles_y);
         const int oy0 = ty * C3_TH, ox0 = tx * C3_TW;
         // x halo tile -> LDS (region A is free: the previous tile's 3x3 pass, its last reader, ended before that tile's cv3 pass)
@@ -134,8 +149,19 @@ __global__ __launch_bounds__(C3_NW * 64, 2) void c3_fused_kernel(const C3Args a)
             const int n = i >> 3, c = i & 7;
             if (n < C3_NH) *(uint4*)(xab + (c >> 2) * (C3_NP * 64) + c3_addr(n, c & 3)) = pre[k];
         }
+        if (ctr && left == 0 && threadIdx.x == 0) {                           // (the slot's readers of the previous chunk are four barriers back or more)
+            int len;
+            nxt_s[0] = tile_chunk(pend, ntiles, (int)gridDim.x, &len);
+            nxt_s[1] = len;
+        }
         __syncthreads();
-        if (t + (int)gridDim.x < ntiles) fetch(t + gridDim.x);                // in flight during the four passes
+        if (!ctr) tn = t + (int)gridDim.x;
+        else if (left > 0) { tn = t + 1; --left; }
+        else { tn = nxt_s[0]; left = nxt_s[1] - 1; }
+        if (tn < ntiles) {
+            fetch(tn);                                                        // in flight during the four passes
+            if (ctr && left == 0 && threadIdx.x == 0) pend = tile_claim_chunk(ctr);   // tn ends its chunk: the answer is read one tile from here
+        }
 
         // ---- cv1 | cv2 on the halo region: y1 -> yb (all of it), y2 -> yc (interior pixels only) ------------------------------------
         for (int pt = wave; pt < C3_NT && !(abl & 16); pt += C3_NW) {
@@ -258,6 +284,7 @@ __global__ __launch_bounds__(C3_NW * 64, 2) void c3_fused_kernel(const C3Args a)
             }
         }
     }
+    if (ctr && threadIdx.x == 0) tile_claims_done(ctr);
     if (a.dbg && threadIdx.x == 0) a.dbg[(size_t)blockIdx.x * 2 + 1] = wall_clock64();
 }
 
@@ -293,6 +320,8 @@ int launch_c3_fused(const ConvP& p12, const ConvP& pm1, const ConvP& pm2, const 
     static const int slots_hw = resident_workgroups(c3_fused_kernel<false>, C3_NW * 64);
     int grid = std::min(ntiles, std::max(256, slots_hw - conv_slots_reserve() / 2));         // persistent; two workgroups per CU: half the usual number of slots stays free
     if (grid_cap > 0) grid = std::min(grid, grid_cap);
+    else if (p12.slots > 0) grid = std::min(grid, p12.slots);                        // the engine's VC_CONV_SLOTS (tests)
+    a.ctr = p12.tile_ctr;
     a.abl = p12.ablate;                                                              // diagnostics only (engine option "c3_ablate", tools/ff_ablate.py)
     static WgStamps stamps("VC_C3_DBG", "c3", 1024, 2, 0, 1);
     a.dbg = stamps.next(grid, ntiles, s);

@@ -136,20 +136,21 @@ struct vc_engine {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // Tile counters of the fused persistent kernels (vc_common.h: tile_claim): a ring of {next, done} pairs, one per 64-byte line, zeroed once
     // here; the kernels leave a pair zero.  A launch takes the next pair (tile_ctr_next).  Launches of one stream run one after the other, so a
-    // pair could only be shared by two running kernels if one stream fell a whole ring of such launches behind another: 1 024 pairs, one
-    // launch per detector pass today, and the host waits for a batch's rows before it submits the next but one.
+    // pair could only be shared by two running kernels if one stream fell a whole ring of such launches behind another: 1 024 pairs, five
+    // launches per detector pass today, and the host waits for a batch's rows before it submits the next but one.
     static constexpr unsigned kTileCtrPairs = 1024;
+    static constexpr int kDynTilesKept = 7;   // default of option "dyn_tiles_mask": the conversions that are kept (1 front_fused, 2 c3_fused, 4 bneck_fused kernels)
     unsigned* d_tile_ctr = nullptr;
     unsigned tile_ctr_seq = 0;
     unsigned tile_ctr_ring = kTileCtrPairs;   // pairs in use (option "dyn_tiles_ring", tests: 1 = every launch gets the pair the one before it left)
-    int conv_slots = 0;              // VC_CONV_SLOTS at creation (tests): grid of front_fused_kernel, ConvP::slots
+    int conv_slots = 0;              // VC_CONV_SLOTS at creation (tests): grid of front_fused_kernel and c3_fused_kernel, ConvP::slots
     void* d_zero = nullptr; size_t zero_bytes = 0; bool want_hc_count = false;   // per-pass counters cleared by one memset (engine_plan.hip)
     hipEvent_t ev_det[2] = {nullptr, nullptr};
     hipEvent_t ev_reid[3] = {nullptr, nullptr, nullptr};
     bool finalized = false;
     // kernel-selection switches: read from the environment ONCE at engine creation (VC_C3_FUSED, VC_BNECK_FUSED, VC_FRONT_FUSED,
     // VC_CROP_PER_PIXEL, VC_DOT_ARENA_MB), changed afterwards only through vc_engine_set_option -- nothing on the launch path calls getenv per launch
-    struct Options { int c3_fused = 1, bneck_fused = 1, bneck_cv3 = 1, front_fused = 1, crop_per_pixel = 0, sparse_head = 1, ff_ablate = 0, c3_ablate = 0, reid_block_fused = 1, dyn_tiles = 1, head_side = 1, fuse_upsample = 1, sppf_sep = 1, fuse_s2_pw = 1, stem_direct = 1, embed_kept_only = 1; } opt;
+    struct Options { int c3_fused = 1, bneck_fused = 1, bneck_cv3 = 1, front_fused = 1, crop_per_pixel = 0, sparse_head = 1, ff_ablate = 0, c3_ablate = 0, reid_block_fused = 1, dyn_tiles = 1, dyn_tiles_mask = kDynTilesKept, head_side = 1, fuse_upsample = 1, sppf_sep = 1, fuse_s2_pw = 1, stem_direct = 1, embed_kept_only = 1; } opt;
     std::vector<void*> allocs;       // everything hipMalloc'ed, freed on destroy
     std::vector<void*> host_allocs;  // hipHostMalloc'ed
 
@@ -327,9 +328,10 @@ namespace vc {
 // engine.hip
 int pack_and_upload(std::vector<void*>& allocs, ConvParam& p, int prec, float act_scale = 1.0f);   // p.w / p.b -> packed device weights, bias, fp8 scales
 inline int dev_alloc(vc_engine* e, void** p, size_t bytes) { return dev_alloc(e->allocs, p, bytes); }
-// the counter pair of the next fused launch; null (option "dyn_tiles" 0) = the fixed stride
-inline unsigned* tile_ctr_next(vc_engine* e) {
-    if (!e->d_tile_ctr || !e->opt.dyn_tiles) return nullptr;
+// the counter pair of the next fused launch of the kernel with this bit of option "dyn_tiles_mask" (1 front, 2 C3, 4 Bottleneck); null (its bit
+// clear, or option "dyn_tiles" 0, which switches every kernel back whatever the mask) = the fixed stride
+inline unsigned* tile_ctr_next(vc_engine* e, int bit) {
+    if (!e->d_tile_ctr || !e->opt.dyn_tiles || !(e->opt.dyn_tiles_mask & bit)) return nullptr;
     return e->d_tile_ctr + (size_t)(e->tile_ctr_seq++ % e->tile_ctr_ring) * 16;
 }
 int dev_realloc(vc_engine* e, void** p, size_t bytes);            // frees *p (if it belongs to the engine) and allocates anew

@@ -187,7 +187,7 @@ int vc_engine_create(const vc_engine_config* cfg, vc_engine** out) {
         e->opt.front_fused = env_int("VC_FRONT_FUSED", 1); e->opt.crop_per_pixel = getenv("VC_CROP_PER_PIXEL") ? 1 : 0;
         e->opt.sparse_head = env_int("VC_SPARSE_HEAD", 1); e->opt.reid_block_fused = env_int("VC_REID_BLOCK_FUSED", 1); e->opt.head_side = env_int("VC_HEAD_SIDE", 1); e->opt.fuse_upsample = env_int("VC_FUSE_UPSAMPLE", 1); e->opt.sppf_sep = env_int("VC_SPPF_SEP", 1); e->opt.fuse_s2_pw = env_int("VC_FUSE_S2PW", 1);
         e->opt.embed_kept_only = env_int("VC_EMBED_KEPT_ONLY", 1);
-        e->opt.dyn_tiles = env_int("VC_DYN_TILES", 1);
+        e->opt.dyn_tiles = env_int("VC_DYN_TILES", 1); e->opt.dyn_tiles_mask = env_int("VC_DYN_TILES_MASK", vc_engine::kDynTilesKept);
         e->conv_slots = env_int("VC_CONV_SLOTS", 0);
         e->tile_ctr_ring = (unsigned)std::min(std::max(env_int("VC_DYN_TILES_RING", (int)vc_engine::kTileCtrPairs), 1), (int)vc_engine::kTileCtrPairs);
     }
@@ -384,7 +384,8 @@ int vc_engine_set_option(vc_engine* e, const char* name, int value) {
     else if (n == "sparse_head") e->opt.sparse_head = value;
     else if (n == "reid_block_fused") e->opt.reid_block_fused = value;
     else if (n == "dyn_tiles_ring") { VC_CHECK(value >= 1 && value <= (int)vc_engine::kTileCtrPairs, VC_ERR_ARG, "dyn_tiles_ring must be 1 .. %u", vc_engine::kTileCtrPairs); e->tile_ctr_ring = (unsigned)value; return VC_OK; }   // tests: a short ring, pairs come round again at once
-    else if (n == "dyn_tiles") e->opt.dyn_tiles = value;              // front_fused_kernel claims its tiles from a counter (1) or walks them by fixed stride (0)
+    else if (n == "dyn_tiles") e->opt.dyn_tiles = value;              // the fused persistent kernels claim their tiles from a counter (1) or walk them by fixed stride (0)
+    else if (n == "dyn_tiles_mask") e->opt.dyn_tiles_mask = value;    // ablation: which of them claim while "dyn_tiles" is on: 1 front, 2 C3, 4 Bottleneck
     else if (n == "head_side") e->opt.head_side = value;
     else if (n == "fuse_upsample") e->opt.fuse_upsample = value;
     else if (n == "sppf_sep") e->opt.sppf_sep = value;

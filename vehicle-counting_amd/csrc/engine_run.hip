@@ -165,6 +165,7 @@ static int conv_select(ConvCtx& c, double fl, double by, ConvLaunch& L) {
         fused(103, 4, fl + conv_flops(*o1) + conv_flops(*o2) + conv_flops(*o3),
               in_bytes + w_bytes(op) + w_bytes(*o1) + w_bytes(*o2) + w_bytes(*o3) + out_bytes(*o3), 64, 64, 1, 1);
         cp.ablate = e->opt.c3_ablate;
+        cp.slots = e->conv_slots; cp.tile_ctr = tile_ctr_next(e, 2);
         L.launch = [](ConvCtx& x) { return launch_c3_fused(x.cp, x.op[1].conv, x.op[2].conv, x.op[3].conv, x.s); };
     } else if (e->opt.reid_block_fused != 0 && o1 && reid_block_fused_applicable(cp, o1->conv)) {
         // a 64-channel ReID BasicBlock in one kernel (reid_block_fused.hip): x in, both weights, y out
@@ -174,10 +175,12 @@ static int conv_select(ConvCtx& c, double fl, double by, ConvLaunch& L) {
         // the last 64-channel Bottleneck of a C3 + the block's cv3 in one kernel; cv3 reads the 64 channels of y2 beside the input
         fused(105, 3, fl + conv_flops(*o1) + conv_flops(*o2),
               (double)cp.B * cp.H * cp.W * (cp.Cin + 64) * es + w_bytes(op) + w_bytes(*o1) + w_bytes(*o2) + out_bytes(*o2), 128, 768, 3, 1);
+        cp.tile_ctr = tile_ctr_next(e, 4);
         L.launch = [](ConvCtx& x) { return launch_bneck_cv3_fused(x.cp, x.op[1].conv, x.op[2].conv, x.s); };
     } else if (e->opt.bneck_fused != 0 && o1 && bneck_fused_applicable(cp, o1->conv)) {
         // 64-channel Bottleneck in one kernel (bneck_fused.hip)
         fused(104, 2, fl + conv_flops(*o1), in_bytes + w_bytes(op) + w_bytes(*o1) + out_bytes(*o1), 64, 640, 3, 1);
+        cp.tile_ctr = tile_ctr_next(e, 4);
         L.launch = [](ConvCtx& x) { return launch_bneck_fused(x.cp, x.op[1].conv, x.s); };
     } else if (e->opt.fuse_s2_pw != 0 && op.sole_reader_next && o1 && s2halo_pw_applicable(cp, o1->conv)) {
         // a 3x3 / s2 conv and the pointwise conv that alone reads it in one launch (conv3x3s2_halo_kernel<..., F2>): YOLOv5s layer 3 +
@@ -193,7 +196,7 @@ static int conv_select(ConvCtx& c, double fl, double by, ConvLaunch& L) {
         // YOLO layers 0 + 1 in one kernel (front_fused.hip): layer 0 never reaches HBM.  The log line keeps the stem's own N / K / k / s.
         L.cfg = 102; L.n_ops = 2; L.flops = fl + conv_flops(*o1); L.bytes = in_bytes + w_bytes(op) + w_bytes(*o1) + out_bytes(*o1);
         cp.ablate = e->opt.ff_ablate;
-        cp.slots = e->conv_slots; cp.tile_ctr = tile_ctr_next(e);
+        cp.slots = e->conv_slots; cp.tile_ctr = tile_ctr_next(e, 1);
         L.launch = [](ConvCtx& x) {
             VC_TRY(launch_front_fused(x.cp, x.op[1].conv, x.u8_src ? x.e->stem_src : nullptr, x.e->stem_geom, x.s));
             x.e->l0_stale = true;                                     // layer 0 lived in LDS only

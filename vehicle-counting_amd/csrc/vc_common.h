@@ -178,7 +178,7 @@ struct ConvP {
                          // VC_CONV_SLOTS -- the launchers themselves never read the environment
     int ablate;          // diagnostics only (VC_CONV_ABLATE, timing experiments with wrong results): 1 = no staging DMA after the first tiles,
                          // 2 = no output stores, 3 = both, 6 = return at once (launch floor of the grid); per-phase times come from dbg
-    unsigned* tile_ctr;  // front_fused_kernel: this launch's counter pair {next, done} (zero; engine.h: tile_ctr_next), null = the fixed-stride loop
+    unsigned* tile_ctr;  // front_fused / c3_fused / bneck_fused kernels: this launch's counter pair {next, done} (zero; engine.h: tile_ctr_next), null = the fixed-stride loop
 };
 
 // Claimed tiles of a persistent kernel.  Workgroup b starts with tile b; every later tile is gridDim.x + (what `next` held), so a workgroup that
@@ -189,6 +189,10 @@ struct ConvP {
 #if defined(__HIPCC__)
 __device__ __forceinline__ int tile_claim(unsigned* ctr) {
     return (int)gridDim.x + (int)__hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// the same claim as a CHUNK index 0, 1, ... of tile_sched.h's schedule (c3_fused.hip, bneck_fused.hip): tile_chunk turns it into tiles
+__device__ __forceinline__ int tile_claim_chunk(unsigned* ctr) {
+    return (int)__hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ void tile_claims_done(unsigned* ctr) {
     if (__hip_atomic_fetch_add(ctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {

@@ -77,7 +77,7 @@ class Engine:
         L.check(L.lib().vc_engine_sync(self._h))
 
     def set_option(self, name, value):
-        """Kernel-selection switch of the live engine ("c3_fused", "bneck_fused", "bneck_cv3", "front_fused", "sparse_head", "reid_block_fused", "stem_direct", "crop_per_pixel", "dot_arena_mb", "dyn_tiles" (1: front_fused_kernel claims its tiles from a per-launch counter, 0: it walks them by fixed stride; same results); diagnostics: "ff_ablate", "c3_ablate", "dyn_tiles_ring" (counter pairs in use, 1 .. 1024: the tests make them come round again)), or "embed_kept_only" (1: crop and embed only the boxes DeepSort.update's own filter keeps; 0: every box)."""
+        """Kernel-selection switch of the live engine ("c3_fused", "bneck_fused", "bneck_cv3", "front_fused", "sparse_head", "reid_block_fused", "stem_direct", "crop_per_pixel", "dot_arena_mb", "dyn_tiles" (1: the fused persistent kernels claim their tiles from a per-launch counter, 0: they walk them by fixed stride; same results), "dyn_tiles_mask" (which of them claim while "dyn_tiles" is on: 1 front_fused_kernel, 2 c3_fused_kernel, 4 bneck_fused_kernel); diagnostics: "ff_ablate", "c3_ablate", "dyn_tiles_ring" (counter pairs in use, 1 .. 1024: the tests make them come round again)), or "embed_kept_only" (1: crop and embed only the boxes DeepSort.update's own filter keeps; 0: every box)."""
         L.check(L.lib().vc_engine_set_option(self._h, name.encode(), int(value)))
 
     def stream_reset(self):
