@@ -53,7 +53,7 @@ IDS_S2 = tuple(sorted(HALO_S2))
 IDS_DIRECT = tuple(sorted(DIRECT))
 IDS_STREAM = tuple(sorted(STREAM))
 IDS_D8 = tuple(sorted(DIRECT8))
-IDS_FP8 = (4, 5, 6, 43) + IDS_D8                 # the ids the fp8 path can take
+IDS_FP8 = (4, 5, 6, 43) + IDS_D8                 # the ids of the fp8 cases pw128 / pw64 (what the fp8 path can take: fp8_tile_cases.IDS)
 IDS_ALL = tuple(range(NIDS))
 # persistent grids: VC_CONV_SLOTS = 8 makes a few workgroups walk all tiles
 PERSISTENT = set(IDS_IGEMM) | set(IDS_DIRECT) | set(IDS_STREAM) | set(IDS_D8)

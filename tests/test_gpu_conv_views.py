@@ -7,7 +7,8 @@ kernel or an error), with a short persistent grid too where the family has one, 
       and y2 are intact (the entry point reports a broken guard as an error);
   (b) the written slice is inside the project's own gate against float64 on the rounded operands: bf16 stores rtol 2^-7 / atol 2e-3,
       f32 stores (the f32 path and out_f32) rtol 1e-4 / atol 1e-4, fp8 arithmetic with the bf16 store the bf16 gate on the quantised
-      operands; fp8 -> fp8 has no gate of its own and rests on (c);
+      operands; fp8 -> fp8 has no gate of its own and rests on (c) (tests/test_gpu_fp8_tiles.py holds the dense launch of every id, on
+      these operands too, to float64);
   (c) the written slice equals, bit for bit, the DENSE launch of the same configuration through vc_conv2d_host wherever both take the
       same store path: every fp8 -> fp8 and f32 case, and the bf16 cases whose view keeps conv_epilogue_fast_bf16 as the dense launch has
       it.  m_dev rows are the first rows of the full launch; an `up` launch is compared with the dense launch on the concat that NumPy
