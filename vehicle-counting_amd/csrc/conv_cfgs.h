@@ -53,11 +53,16 @@ namespace vc {
 #define VC_PAIR4_CFGS(P) P(67, 256, 128, 2, 2, 4, 3) P(68, 256, 128, 2, 2, 4, 2)
 // weights-in-registers 1x1 of the fp8 path (conv1x1_direct_fp8_kernel): F(index, CT, KS, PT, OCC); K <= 128 KS
 #define VC_DIRECT8_CFGS(F) F(69, 4, 1, 2, 2) F(70, 4, 2, 2, 2) F(71, 4, 1, 4, 2) F(72, 8, 1, 2, 2)
+// weights in registers, pixels through an LDS ring, epilogue under the next tile (conv1x1_wreg_kernel, bf16): W(index, KS, NG, PT, NS) for
+// K = KS * 32 in, NG * 64 out; pixel tiles of PT * 16 * 4 / NG rows of KS * 64 bytes, NS of them in the ring (at most 64 KB).
+// PT = 2 throughout: four pixel tiles per wave (64 accumulator registers x 2 sets) spill beside the weights, for K = 128 as well.
+// 73 / 74: 256 -> 256 (32-pixel tiles); 75: 256 -> 128 (64); 76: 128 -> 256 (32); 77 / 78: 128 -> 128 (64)
+#define VC_WREG_CFGS(W) W(73, 8, 4, 2, 3) W(74, 8, 4, 2, 4) W(75, 8, 2, 2, 2) W(76, 4, 4, 2, 4) W(77, 4, 2, 2, 3) W(78, 4, 2, 2, 4)
 
 // ---- the registry ------------------------------------------------------------------------------------------------------
-// FAM_IGEMM: conv_igemm.hip; FAM_HALO: conv_halo.hip; FAM_HALO_V2: conv_halo_v2.hip; FAM_HALO_S2: conv_halo_s2.hip; FAM_DIRECT, FAM_STREAM
-// and FAM_DIRECT8: conv_pointwise.hip
-enum ConvFamily : int { FAM_IGEMM, FAM_HALO, FAM_HALO_V2, FAM_HALO_S2, FAM_DIRECT, FAM_STREAM, FAM_DIRECT8 };
+// FAM_IGEMM: conv_igemm.hip; FAM_HALO: conv_halo.hip; FAM_HALO_V2: conv_halo_v2.hip; FAM_HALO_S2: conv_halo_s2.hip; FAM_DIRECT, FAM_STREAM,
+// FAM_DIRECT8 and FAM_WREG: conv_pointwise.hip
+enum ConvFamily : int { FAM_IGEMM, FAM_HALO, FAM_HALO_V2, FAM_HALO_S2, FAM_DIRECT, FAM_STREAM, FAM_DIRECT8, FAM_WREG };
 struct ConvCfgEntry { int id; ConvFamily family; };
 #define VC_REG_IGEMM(i, ...) {i, FAM_IGEMM},
 #define VC_REG_HALO(i, ...) {i, FAM_HALO},
@@ -66,10 +71,11 @@ struct ConvCfgEntry { int id; ConvFamily family; };
 #define VC_REG_DIRECT(i, ...) {i, FAM_DIRECT},
 #define VC_REG_STREAM(i, ...) {i, FAM_STREAM},
 #define VC_REG_DIRECT8(i, ...) {i, FAM_DIRECT8},
+#define VC_REG_WREG(i, ...) {i, FAM_WREG},
 constexpr ConvCfgEntry kConvCfgs[] = {
     VC_CONV_CFGS(VC_REG_IGEMM) VC_HALO_CFGS(VC_REG_HALO) VC_DIRECT_CFGS(VC_REG_DIRECT) VC_CONV_BIG_CFGS(VC_REG_IGEMM) VC_S2HALO_CFGS(VC_REG_HALO_S2)
     VC_STREAM_CFGS(VC_REG_STREAM) VC_HALO_V2_CFGS(VC_REG_HALO_V2) VC_SK_CFGS(VC_REG_IGEMM) VC_CONV_DEEP_CFGS(VC_REG_IGEMM) VC_PAIR_CFGS(VC_REG_IGEMM)
-    VC_PAIR4_CFGS(VC_REG_IGEMM) VC_DIRECT8_CFGS(VC_REG_DIRECT8)};
+    VC_PAIR4_CFGS(VC_REG_IGEMM) VC_DIRECT8_CFGS(VC_REG_DIRECT8) VC_WREG_CFGS(VC_REG_WREG)};
 #undef VC_REG_IGEMM
 #undef VC_REG_HALO
 #undef VC_REG_HALO_V2
@@ -77,6 +83,7 @@ constexpr ConvCfgEntry kConvCfgs[] = {
 #undef VC_REG_DIRECT
 #undef VC_REG_STREAM
 #undef VC_REG_DIRECT8
+#undef VC_REG_WREG
 constexpr int kNumConvCfgs = (int)(sizeof(kConvCfgs) / sizeof(kConvCfgs[0]));
 
 // the family of every id, indexed by id; ok = the ids are exactly 0 .. kNumConvCfgs - 1, each once

@@ -41,6 +41,7 @@ int launch_conv_cfg(const ConvP& p, int cfg, hipStream_t s) {
         case FAM_DIRECT:
         case FAM_STREAM:
         case FAM_DIRECT8: return launch_pointwise_cfg(p, cfg, s);
+        case FAM_WREG: return launch_wreg_cfg(p, cfg, s);
     }
     return VC_ERR_ARG;
 }

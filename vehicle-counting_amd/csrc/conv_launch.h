@@ -20,6 +20,7 @@ struct ConvSwitches {
     bool s2halo;        // VC_CONV_S2HALO: conv3x3s2_halo_kernel
     bool direct;        // VC_CONV_DIRECT: conv1x1_direct_kernel
     bool direct8;       // VC_CONV_DIRECT8: conv1x1_direct_fp8_kernel
+    bool wreg;          // VC_CONV_WREG: conv1x1_wreg_kernel
     bool halo_v2;       // VC_CONV_HALO_V2: conv3x3_halo_v2_kernel
     bool persist;       // VC_CONV_PERSIST: persistent grids of the implicit GEMM (0: one workgroup per tile)
     bool balanced;      // VC_CONV_BALANCED: persistent_grid's rounds-first rule (0: the old rule)
@@ -39,6 +40,7 @@ inline const ConvSwitches& conv_switches() {
         c.s2halo = num("VC_CONV_S2HALO", 1) != 0;
         c.direct = num("VC_CONV_DIRECT", 1) != 0;
         c.direct8 = num("VC_CONV_DIRECT8", 1) != 0;
+        c.wreg = num("VC_CONV_WREG", 1) != 0;
         c.halo_v2 = num("VC_CONV_HALO_V2", 1) != 0;
         c.persist = num("VC_CONV_PERSIST", 1) != 0;
         c.balanced = num("VC_CONV_BALANCED", 1) != 0;

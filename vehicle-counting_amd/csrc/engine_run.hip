@@ -64,6 +64,9 @@ void plans_retune(vc_engine* e) {
 static int tuned_cfg(vc_engine* e, const ConvP& c, hipStream_t s) {
     static const bool enabled = !(getenv("VC_AUTOTUNE") && atoi(getenv("VC_AUTOTUNE")) == 0);
     if (!enabled) return -1;
+    // VC_TUNE_WREG (tests, A/B; read per op, not per process): no autotuning at all.  1: every conv conv1x1_wreg_kernel takes runs on the
+    // family's first id for it, everything else on the heuristic's tile; 0: the heuristic's tile everywhere.  The two differ in that family alone.
+    if (const char* fw = getenv("VC_TUNE_WREG")) return atoi(fw) != 0 ? wreg_cfg_for(c) : -1;
     const std::string key = tune_key(c);
     auto it = e->tuned.find(key);
     if (it != e->tuned.end()) return it->second;

@@ -218,6 +218,9 @@ int launch_halo_cfg(const ConvP& p, int cfg, hipStream_t s);       // conv_halo.
 int launch_halo_v2_cfg(const ConvP& p, int cfg, hipStream_t s);    // conv_halo_v2.hip
 int launch_halo_s2_cfg(const ConvP& p, int cfg, hipStream_t s);    // conv_halo_s2.hip
 int launch_pointwise_cfg(const ConvP& p, int cfg, hipStream_t s);  // conv_pointwise.hip
+int launch_wreg_cfg(const ConvP& p, int cfg, hipStream_t s);       // conv_pointwise.hip (conv1x1_wreg_kernel)
+bool wreg_applicable(const ConvP& p, int ks, int ng);             // what conv1x1_wreg_kernel<KS, NG, ...> takes
+int wreg_cfg_for(const ConvP& p);                                  // the family's first id that takes p, or -1
 bool s2halo_pw_applicable(const ConvP& p, const ConvP& q);      // conv3x3s2_halo_kernel<..., F2>: a 3x3 / s2 conv and the pointwise conv that alone reads it, one launch
 int launch_s2halo_pw(ConvP p, ConvP q, hipStream_t s);
 int conv_num_cfgs();
