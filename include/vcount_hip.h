@@ -206,11 +206,27 @@ int vc_stream_run(vc_engine* e, const int* trackers, int num_classes, const void
  * modules/datasets.py:47-61) -------------------------------------------------------------------------------------------- */
 #define VC_PIX_NV12 0      /* Y plane, then one plane of interleaved U,V at half resolution (hardware decoder surfaces) */
 #define VC_PIX_I420 1      /* Y, U and V planes (software decoders) */
+/* Ingest only (every source descriptor takes them; egress and the render path's out_desc refuse them with VC_ERR_ARG).  Ids 2..15 and
+ * >= 20 are unknown formats. */
+#define VC_PIX_P016 16     /* NV12's planes with little-endian 16-bit samples, significant bits at the TOP: HEVC Main10 / AV1 10-bit decoder
+                              surfaces.  P010 and P012 surfaces are passed as this format. */
+#define VC_PIX_I010 17     /* I420's planes with little-endian 16-bit samples, 10 significant bits at the BOTTOM (yuv420p10le) */
+#define VC_PIX_I422 18     /* Y, U and V planes, 8-bit, chroma at half width and FULL height (MJPEG cameras) */
+#define VC_PIX_I444 19     /* Y, U and V planes, 8-bit, chroma at full resolution (H.264 High 4:4:4, screen sources) */
 #define VC_YUV_BT601 0
 #define VC_YUV_BT709 1
 /* Geometry in BYTES from the start of a frame; 0 = tightly packed (pitch_y = w; pitch_c = w for NV12, w / 2 for I420; offset_c =
  * pitch_y * h; offset_v = offset_c + pitch_c * h / 2; frame_stride = end of the last plane).  A decoder surface gives the explicit
- * form, e.g. pitch 1536 for a 1280-wide frame with the chroma plane at pitch x aligned height.  offset_v is ignored for NV12. */
+ * form, e.g. pitch 1536 for a 1280-wide frame with the chroma plane at pitch x aligned height.  offset_v is ignored for NV12.
+ * Per format (everything stays in bytes, the rule for the zeros is the same: offset_c = pitch_y * h, offset_v = offset_c + pitch_c *
+ * chroma rows; offset_v is ignored for P016 too; no evenness rule for pitches, offsets or addresses):
+ *              luma row bytes   chroma row bytes   chroma rows   chroma of pixel (x, y)   size rule            bytes read / px
+ *   NV12       w                w                  h / 2         (x >> 1, y >> 1)         h, w even            1.5
+ *   I420       w                w / 2              h / 2         (x >> 1, y >> 1)         h, w even            1.5
+ *   P016       2 w              2 w                h / 2         (x >> 1, y >> 1)         h, w even            3
+ *   I010       2 w              w                  h / 2         (x >> 1, y >> 1)         h, w even            3
+ *   I422       w                w / 2              h             (x >> 1, y)              w even, h >= 1       2
+ *   I444       w                w                  h             (x, y)                   h, w >= 1            3                     */
 typedef struct vc_yuv_desc {
     int format;            /* VC_PIX_* */
     int matrix;            /* VC_YUV_BT601 / VC_YUV_BT709 */
@@ -222,8 +238,13 @@ int vc_yuv_desc_default(vc_yuv_desc* d);   /* NV12, BT.601, limited range, tight
 /* Arithmetic (integer, 32-bit signed): u = U - 128, v = V - 128, chroma replicated over its 2 x 2 luma block,
  *   R = clamp((y + (1 << 19) + CVR * v) >> 20), G = clamp((y + (1 << 19) + CVG * v + CUG * u) >> 20), B = clamp((y + (1 << 19) + CUB * u) >> 20)
  * with y = max(0, Y - 16) * CY (limited) or Y << 20 (full) and constants int(literal * 2^20): OpenCV's COLOR_YUV2BGR_NV12 for
- * BT.601 limited.  h and w must be even.  Bad geometry (odd size, unknown format / matrix, a pitch below the row width, overlapping
- * planes) is VC_ERR_ARG before any HIP call.
+ * BT.601 limited.  The wider formats extend this arithmetic, they do not add a second one: every sample of every plane is first reduced
+ * to 8 bits -- P016: s8 = min(255, (s16 + 128) >> 8); I010: s8 = min(255, ((s16 & 1023) + 2) >> 2); 8-bit formats: s8 = s -- then the
+ * arithmetic above is applied verbatim with the chroma sample the table names, replicated, never interpolated.  A 4:2:0 frame whose
+ * samples are s8 << 8 (P016) or s8 << 2 (I010) therefore converts to the bytes NV12 / I420 of the s8 planes give.  10-bit input is
+ * treated as SDR under BT.601 / BT.709.  Parity with cv2 / swscale is UNPINNED for every format.
+ * h and w must be even where the table says so.  Bad geometry (a size the format refuses, unknown format / matrix, a pitch below the
+ * row bytes, overlapping planes, a frame_stride below the frame, offsets out of range) is VC_ERR_ARG before any HIP call.
  * vc_stream_stage_yuv_host / _dev fill one of the four ingest slots of vc_stream_stage_host with the CONVERTED frames (same slot
  * rules, same VC_ERR_STATE refusals; BGR and YUV staging may be mixed): *frames_dev_out is an ordinary B x H x W x 3 BGR buffer
  * for vc_stream_submit / vc_stream_run*.  _host copies the raw YUV (1.5 B per pixel over PCIe; pinned memory for the copy to
@@ -332,7 +353,8 @@ int vc_bgr_to_yuv_dev(const vc_yuv_desc* d, const void* bgr_dev, int b, int h, i
 typedef struct vc_render vc_render;
 #define VC_SRC_BGR_HOST 0  /* b x h x w x 3 BGR in (pinned) host memory */
 #define VC_SRC_BGR_DEV 1   /* the same in device memory: copied into the work buffer, the caller's frames are never painted */
-#define VC_SRC_YUV_HOST 2  /* 4:2:0 frames laid out as `desc` in (pinned) host memory: 1.5 B per pixel over PCIe, converted on the device */
+#define VC_SRC_YUV_HOST 2  /* YUV frames laid out as `desc` (any VC_PIX_* format) in (pinned) host memory: 1.5 B per pixel over PCIe for 8-bit
+                              4:2:0, 2 for I422, 3 for P016 / I010 / I444; converted on the device */
 #define VC_SRC_YUV_DEV 3   /* decoder surfaces in device memory */
 typedef struct vc_render_src {
     int kind;              /* VC_SRC_* */
@@ -364,7 +386,8 @@ typedef vc_render_src vc_frame_src;
  * overlap), one copy of the frame table, at most ONE frames_to_bgr_kernel launch whatever b and whatever the mix (none when every
  * frame is VC_SRC_BGR_HOST), the slot's event.  Device sources must stay valid until the vc_stream_run* call of the batch has
  * returned, host sources until its rows are collected.  Every refusal comes before a slot is taken or anything is enqueued: b < 1,
- * a null data, an unknown kind, bad geometry in any frame, an odd h or w when any frame is YUV are VC_ERR_ARG, and the message
+ * a null data, an unknown kind, bad geometry in any frame, an h or w that a YUV frame's format refuses (the table above vc_yuv_desc:
+ * odd sizes for NV12 / I420 / P016 / I010, an odd w for I422, none for I444) are VC_ERR_ARG, and the message
  * names the frame ("frame 3: pitch_y ..."). */
 int vc_stream_stage_frames(vc_engine* e, const vc_frame_src* frames /* b */, int b, int h, int w, void** frames_dev_out);
 /* The validation of vc_stream_stage_frames and the packing of its raw buffer.  Pure host function (no GPU), like vc_gather_offsets:
@@ -389,8 +412,8 @@ int vc_frames_to_bgr_dev(const vc_frame_src* frames /* device kinds only, or NUL
  * Layout in device memory: b CELLS of `cell` bytes, cell = the largest h * w * 3 of the batch rounded up to 16; frame f is tight BGR
  * (row pitch w_f * 3) at f * cell; the rest of a cell is never read and never written.
  * Refusals, all pure host logic before any HIP call: frames whose network shapes differ are VC_ERR_ARG, the message names the first
- * frame that differs and both shapes ("frame 3: 480x640 runs at 480x640, frame 0 at 384x640"); YUV frames need an even h and w (BGR
- * frames may be odd); h_f > max_frame_h, w_f > max_frame_w, b > max_batch or b * cell beyond an ingest slot are VC_ERR_CAPACITY (a slot
+ * frame that differs and both shapes ("frame 3: 480x640 runs at 480x640, frame 0 at 384x640"); a YUV frame needs the even h and / or w its format asks for (BGR
+ * and I444 frames may be odd, I422 frames in h); h_f > max_frame_h, w_f > max_frame_w, b > max_batch or b * cell beyond an ingest slot are VC_ERR_CAPACITY (a slot
  * holds max_batch frames of the configured maximum in cells).  Opt-in: every other entry point runs a uniform batch as before. */
 typedef struct vc_frame_dims { int h, w; } vc_frame_dims;
 /* The network shape AutoShape gives ONE h x w image at `img_size` (models/common.py v6.0).  Pure host function. */

@@ -3,7 +3,9 @@
      copy that moves the same total bytes (read + written), timed in the same process with the same events;
  (b) end-to-end frames/s of CountingPipeline.run_stream(host_frames=True, asynchronous=True) on one clip given as NV12 and as the BGR it converts to:
      640 x 640 and 1280 x 720, bf16 YOLOv5s, 256 frames per batch, both forms on one engine per geometry.
-usage (GPU box): python tools/yuv_ingest_time.py [--out profiles/yuv_ingest.md] [--batches 6] [--skip-e2e]"""
+ (c) the kernel alone as in (a) for all six source formats -- nv12, i420 and the wider p016, i010, i422, i444 -- each next to the copy of
+     ITS OWN read + written bytes (4.5, 5 or 6 B per pixel), all in one run.
+usage (GPU box): python tools/yuv_ingest_time.py [--out profiles/yuv_ingest.md] [--batches 6] [--skip-e2e] [--only-wide]"""
 import argparse
 import os
 import sys
@@ -77,6 +79,46 @@ def kernel_table(out):
     return worst
 
 
+FORMATS = ("nv12", "i420", "p016", "i010", "i422", "i444")
+FORMAT_ID = {**E.L.PIX_ID, **E.L.PIX_WIDE_ID}
+
+
+def wide_table(out):
+    out.append("## (c) all six source formats, kernel alone, 256 frames per launch\n")
+    out.append("As (a), one run for all rows.  Bytes = read + written: 3 B written per pixel, read 1.5 B (nv12, i420), 2 B (i422) or 3 B (p016, i010,")
+    out.append("i444).  Every format is held against the device-to-device copy of half ITS OWN total; `pitch` = the luma pitch in bytes of a padded")
+    out.append("decoder surface (the chroma pitch follows it, the chroma planes start below a 16-row aligned height).\n")
+    out.append("| frames | format | B / px read | layout | kernel ms | kernel TB/s | copy ms | copy TB/s | kernel / copy |")
+    out.append("|---|---|---|---|---|---|---|---|---|")
+    worst = {}
+    for h, w, _, _ in GEOMETRIES:
+        bgr = torch.empty((B, h, w, 3), dtype=torch.uint8, device="cuda")
+        copy_ms = {}
+        for fmt in FORMATS:
+            rowb, crow, hc, semi, _ = E.yuv_format_rows(FORMAT_ID[fmt], h, w)
+            read = h * rowb + (1 if semi else 2) * hc * crow                                  # plane bytes of one frame
+            total = B * (read + 3 * h * w)
+            if total not in copy_ms:
+                src_c = torch.randint(0, 256, (total // 2,), dtype=torch.uint8, device="cuda")
+                dst_c = torch.empty_like(src_c)
+                copy_ms[total] = event_ms(lambda: dst_c.copy_(src_c))
+                del src_c, dst_c
+            py = (rowb + 255) // 256 * 256 + (0 if rowb % 256 else 256)
+            layouts = [("tight", {}), (f"pitch {py}", dict(pitch_y=py, pitch_c=py if crow == rowb else py // 2, offset_c=py * ((h + 15) // 16 * 16)))]
+            for name, geo in layouts:
+                desc = E.yuv_desc(fmt, **geo)
+                yuv = torch.randint(0, 256, (E.yuv_batch_bytes(desc, B, h, w),), dtype=torch.uint8, device="cuda")
+                ms = event_ms(lambda: E.yuv_to_bgr_dev(yuv.data_ptr(), B, h, w, bgr.data_ptr(), desc))
+                c = copy_ms[total]
+                worst[fmt] = max(worst.get(fmt, 0.0), ms / c)
+                out.append(f"| {B} x {w}x{h} | {fmt} | {read / (h * w):.1f} | {name} | {ms:.4f} | {total / ms / 1e9:.2f} | {c:.4f} | {total / c / 1e9:.2f} | {ms / c:.2f} |")
+                print(out[-1], flush=True)
+                del yuv
+        del bgr
+    out.append("")
+    out.append("Worst kernel / copy ratio per format: " + ", ".join(f"{f} {worst[f]:.2f}" for f in FORMATS) + ".\n")
+
+
 def pinned(a):
     """The array in pinned host memory, as a numpy view (run_stream's own pin_memory() is then free: the frames are pinned already)."""
     t = torch.from_numpy(a).pin_memory()
@@ -130,14 +172,19 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--batches", type=int, default=6)
     ap.add_argument("--skip-e2e", action="store_true")
+    ap.add_argument("--only-wide", action="store_true", help="section (c) alone")
     a = ap.parse_args()
     out = ["# YUV ingest: conversion kernel and end-to-end rate\n",
            f"`python tools/yuv_ingest_time.py --batches {a.batches}` on {torch.cuda.get_device_name(0)}.\n"]
-    worst = kernel_table(out)
-    print("\n".join(out), flush=True)
-    out.append(f"Worst kernel / copy ratio: {worst:.2f}.\n")
-    if not a.skip_e2e:
-        e2e_table(out, a.batches)
+    if a.only_wide:
+        out = [f"`python tools/yuv_ingest_time.py --only-wide` on {torch.cuda.get_device_name(0)}.\n"]
+    else:
+        worst = kernel_table(out)
+        print("\n".join(out), flush=True)
+        out.append(f"Worst kernel / copy ratio: {worst:.2f}.\n")
+        if not a.skip_e2e:
+            e2e_table(out, a.batches)
+    wide_table(out)
     text = "\n".join(out) + "\n"
     print(text)
     if a.out:

@@ -20,6 +20,8 @@ NET_YOLO, NET_REID = 0, 1
 FEAT_DIM = 512
 PROF_CONV, PROF_DETECT_AUX, PROF_REID_AUX, PROF_TRACK = 0, 1, 2, 3
 PIX_ID = {"nv12": 0, "i420": 1}
+# ingest only (VC_PIX_P016 .. VC_PIX_I444): wider decoder output; P010 / P012 surfaces are passed as "p016".  Egress takes PIX_ID alone.
+PIX_WIDE_ID = {"p016": 16, "i010": 17, "i422": 18, "i444": 19}
 YUV_MATRIX_ID = {"bt601": 0, "bt709": 1}
 RENDER_SRC_ID = {"bgr_host": 0, "bgr_dev": 1, "yuv_host": 2, "yuv_dev": 3}
 

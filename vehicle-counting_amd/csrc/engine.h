@@ -113,8 +113,11 @@ struct TrackStage {
 
 // A validated vc_yuv_desc with the zeros resolved (yuv_ingest.hip: yuv_resolve); all byte quantities.  Shared by the ingest
 // conversion (yuv_ingest.hip), the egress conversion (yuv_egress.hip) and the render path (render.hip).
+// The source formats in the kernels' own numbering (fmt below; VC_PIX_* has a gap between 1 and 16).  Egress writes the first two only.
+enum { PF_NV12 = 0, PF_I420, PF_P016, PF_I010, PF_I422, PF_I444, PF_COUNT };
 struct YuvGeom {
     int nv12, h, w, pitch_y, pitch_c;
+    int fmt;                                            // PF_*; nv12 = (fmt == PF_NV12)
     size_t off_c, off_v, frame_stride, frame_end;      // frame_end: one past the last byte any plane of a frame occupies
     int yoff, cy, cvr, cvg, cug, cub;                   // decode: y = max(0, Y - yoff) * cy: full range is yoff = 0, cy = 1 << 20
     int matrix, full_range;                             // as the descriptor named them (the egress kernel picks its own constants)
@@ -377,6 +380,8 @@ int ingest_publish(vc_engine* e, int slot, void** frames_dev_out);
 inline bool nms_capacity_ok(int max_cand, int max_det) { return max_cand % 64 == 0 && max_cand >= 64 && max_cand <= 8192 && max_det >= 1; }   // launch_nms's sizes
 // yuv_ingest.hip / yuv_egress.hip: descriptor validation (pure host code) and the two conversions, both enqueued on `s`
 int yuv_resolve(const vc_yuv_desc* d, int b, int h, int w, YuvGeom& g);
+// yuv_resolve for a destination: the ingest-only formats (VC_PIX_P016 .. VC_PIX_I444) are refused first, by name
+int yuv_resolve_out(const vc_yuv_desc* d, int b, int h, int w, YuvGeom& g);
 // The rules of a sized batch (pure host code): every size in 1 .. 1 << 15, every frame's own network shape at img_size that of frame 0;
 // the cell (the largest frame, rounded up to 16 bytes) and the largest height and width.  Capacities are the caller's to check.
 struct SizedDims { size_t cell = 0; int net_h = 0, net_w = 0, max_h = 0, max_w = 0; };

@@ -129,7 +129,7 @@ int vc_render_submit(vc_render* r, const vc_render_src* src, int b, int h, int w
     VC_CHECK((prims12 == nullptr) == (frame_first == nullptr), VC_ERR_ARG, "prims12 and frame_first go together (both NULL = no overlay)");
     const bool src_yuv = src->kind == VC_SRC_YUV_HOST || src->kind == VC_SRC_YUV_DEV;
     YuvGeom go, gi{};
-    VC_TRY(yuv_resolve(out_desc, b, h, w, go));
+    VC_TRY(yuv_resolve_out(out_desc, b, h, w, go));
     if (src_yuv) VC_TRY(yuv_resolve(&src->desc, b, h, w, gi));
     if (prims12) VC_TRY(overlay_check_lists(b, prims12, frame_first));
     VC_CHECK(b <= r->max_batch && h <= r->max_h && w <= r->max_w, VC_ERR_CAPACITY, "batch of %d frames %dx%d exceeds the render context (%d frames %dx%d)",

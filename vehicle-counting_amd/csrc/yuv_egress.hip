@@ -176,7 +176,7 @@ extern "C" {
 int vc_bgr_to_yuv_host(const vc_yuv_desc* d, const uint8_t* bgr, int b, int h, int w, uint8_t* yuv_out) {
     VC_CHECK(bgr && yuv_out, VC_ERR_ARG, "null argument");
     YuvGeom g;
-    VC_TRY(yuv_resolve(d, b, h, w, g));
+    VC_TRY(yuv_resolve_out(d, b, h, w, g));
     const size_t in_bytes = (size_t)b * h * w * 3;
     DevScratch mem;
     uint8_t* ds = nullptr;
@@ -191,7 +191,7 @@ int vc_bgr_to_yuv_host(const vc_yuv_desc* d, const uint8_t* bgr, int b, int h, i
 int vc_bgr_to_yuv_dev(const vc_yuv_desc* d, const void* bgr_dev, int b, int h, int w, void* yuv_dev) {
     VC_CHECK(bgr_dev && yuv_dev, VC_ERR_ARG, "null argument");
     YuvGeom g;
-    VC_TRY(yuv_resolve(d, b, h, w, g));
+    VC_TRY(yuv_resolve_out(d, b, h, w, g));
     return launch_bgr_to_yuv(g, (const uint8_t*)bgr_dev, (uint8_t*)yuv_dev, b, nullptr);
 }
 

@@ -15,6 +15,14 @@
 // that both rows share one chroma fetch: 16 B of Y per row, 16 B of UV (8 B + 8 B for I420), three 16-byte stores per row.  The
 // generic variant (any even w, any pitch) owns the same 16 x 2 block, assembles the same words from byte loads and stores bytes.
 // Every factor fits 24 bits and every sum 31 bits (|chroma term| <= 2.3e6 * 128, y <= 255 << 20), hence the full-rate 24-bit multiplies.
+//
+// Wider decoder output (include/vcount_hip.h: P016 = P010 / P012 / P016 surfaces, I010 = yuv420p10le, I422, I444) extends the definition,
+// it is not a second one: every sample is first reduced to 8 bits -- P016 s8 = min(255, (s16 + 128) >> 8), I010 s8 = min(255, ((s16 &
+// 1023) + 2) >> 2) -- and the chroma sample of pixel (x, y) is (x >> 1, y >> 1), (x >> 1, y) for I422 or (x, y) for I444, replicated, never
+// interpolated; then the arithmetic above, verbatim (tests/yuv_wide_ref.py).  Parity with cv2 / swscale is UNPINNED here too.  The same
+// body: the format is a template parameter of frame_block that decides the fetch (32 B of luma per row for the 16-bit formats; chroma
+// 32 B per row pair for P016, 16 + 16 B for I010, 8 + 8 B per row for I422, 16 + 16 B per row for I444) and the chroma index; 2 to 3 B
+// read per pixel.  The generic variant takes any width (odd for I444), any pitch, and an odd h where the format allows one.
 #include <algorithm>
 
 #include "engine.h"
@@ -51,102 +59,169 @@ __device__ __forceinline__ uint32_t yuv_pixel(int Y, const YuvChroma& c, const Y
     return b | (g << 8) | (r << 16);
 }
 
-// 16 pixels of one row: yw = 16 Y bytes, cw[j] = U(2j) | V(2j) << 8 | U(2j+1) << 16 | V(2j+1) << 24 -> 48 bytes of BGR as 12 words
-__device__ __forceinline__ void yuv_row16(const uint32_t yw[4], const YuvChroma ch[8], const YuvGeom& k, uint32_t out[12]) {
+// What a format decides (F: PF_*, engine.h): the sample width, whether U and V share one plane, and which chroma sample a pixel uses.
+template <int F> struct PixTraits {
+    static constexpr bool wide = F == PF_P016 || F == PF_I010;      // little-endian 16-bit samples, reduced to 8 bits as they are fetched
+    static constexpr bool semi = F == PF_NV12 || F == PF_P016;      // one plane of interleaved U,V
+    static constexpr bool vsub = F != PF_I422 && F != PF_I444;      // chroma of pixel row y is row y >> 1 (else row y)
+    static constexpr bool hsub = F != PF_I444;                      // chroma of pixel column x is column x >> 1 (else column x)
+    static constexpr int ss = wide ? 2 : 1;                         // bytes of one sample
+};
+
+// A 16-bit sample reduced to 8 bits: P016 min(255, (s + 128) >> 8), I010 min(255, ((s & 1023) + 2) >> 2).  32-bit unsigned, the clamp before
+// the shift like yuv_pixel's (the same value for every s: the sums stay below 2^17, and the clamp bound shifts to 255).
+template <int F>
+__device__ __forceinline__ uint32_t yuv_reduce(uint32_t s) {
+    return F == PF_P016 ? min(s + 128u, 0xffffu) >> 8 : min((s & 1023u) + 2u, 1023u) >> 2;
+}
+
+template <int F>
+__device__ __forceinline__ uint32_t yuv_reduce4(uint32_t lo, uint32_t hi) {     // four 16-bit samples in two words -> four bytes in one
+    return yuv_reduce<F>(lo & 0xffffu) | (yuv_reduce<F>(lo >> 16) << 8) | (yuv_reduce<F>(hi & 0xffffu) << 16) | (yuv_reduce<F>(hi >> 16) << 24);
+}
+
+// 4 * NW consecutive samples of one plane row, the first n of them valid, as NW words of 8-bit samples.  FAST: one vector load of
+// 4 * NW * ss bytes (two 16-byte loads for 32), p aligned to min(16, that); else byte loads of the valid samples only.
+template <int F, bool FAST, int NW>
+__device__ __forceinline__ void yuv_fetch(const uint8_t* __restrict__ p, int n, uint32_t out[NW]) {
+    constexpr bool wide = PixTraits<F>::wide;
+    static_assert(NW == 2 || NW == 4, "8 or 16 samples");
+    if (FAST) {
+        if (NW * (wide ? 2 : 1) == 2) {
+            const uint2 a = *(const uint2*)p;
+            out[0] = a.x; out[1] = a.y;
+        } else {
+            const uint4 a = *(const uint4*)p;
+            if (!wide) {
+                out[0] = a.x; out[1] = a.y; out[NW - 2] = a.z; out[NW - 1] = a.w;
+            } else {
+                out[0] = yuv_reduce4<F>(a.x, a.y); out[1] = yuv_reduce4<F>(a.z, a.w);
+                if (NW == 4) {
+                    const uint4 b = ((const uint4*)p)[1];
+                    out[NW - 2] = yuv_reduce4<F>(b.x, b.y); out[NW - 1] = yuv_reduce4<F>(b.z, b.w);
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (4 * j + i < n) {
+                    const uint8_t* q = p + (4 * j + i) * (wide ? 2 : 1);
+                    v |= (wide ? yuv_reduce<F>((uint32_t)q[0] | ((uint32_t)q[1] << 8)) : (uint32_t)q[0]) << (8 * i);
+                }
+            out[j] = v;
+        }
+    }
+}
+
+// 16 pixels of one row: yw = 16 Y bytes -> 48 bytes of BGR as 12 words.  HSUB: ch = the chroma terms of the row, one per pixel pair.
+// Else one per pixel: each group of four is formed from its U / V bytes (cu, cv) just before its pixels, so that 4 and not 16 triples
+// are live at a time (with 16 the frame-table kernels need 77 VGPRs and drop from 8 to 6 waves per SIMD).
+template <bool HSUB>
+__device__ __forceinline__ void yuv_row16(const uint32_t yw[4], const YuvChroma* ch, const uint32_t cu[4], const uint32_t cv[4], const YuvGeom& k, uint32_t out[12]) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const uint32_t p0 = yuv_pixel(yw[j] & 255, ch[2 * j], k), p1 = yuv_pixel((yw[j] >> 8) & 255, ch[2 * j], k);
-        const uint32_t p2 = yuv_pixel((yw[j] >> 16) & 255, ch[2 * j + 1], k), p3 = yuv_pixel(yw[j] >> 24, ch[2 * j + 1], k);
+        YuvChroma c[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) c[i] = HSUB ? ch[2 * j + (i >> 1)] : yuv_chroma((cu[j] >> (8 * i)) & 255, (cv[j] >> (8 * i)) & 255, k);
+        const uint32_t p0 = yuv_pixel(yw[j] & 255, c[0], k), p1 = yuv_pixel((yw[j] >> 8) & 255, c[1], k);
+        const uint32_t p2 = yuv_pixel((yw[j] >> 16) & 255, c[2], k), p3 = yuv_pixel(yw[j] >> 24, c[3], k);
         out[3 * j] = p0 | (p1 << 24);
         out[3 * j + 1] = (p1 >> 8) | (p2 << 16);
         out[3 * j + 2] = (p2 >> 16) | (p3 << 8);
     }
 }
 
-__device__ __forceinline__ uint32_t yuv_bytes4(const uint8_t* p, int n) {      // up to four bytes, the first n of them valid
-    uint32_t v = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        if (i < n) v |= (uint32_t)p[i] << (8 * i);
-    return v;
+// the chroma samples of the 16 pixels from x0 in chroma row crow, 8 bits each: semi-planar cu = U0 V0 U1 V1 ... (4 words, cv unused);
+// planar cu / cv = the U / V samples (2 words each when the chroma is at half width, 4 at full width)
+template <int F, bool FAST>
+__device__ __forceinline__ void chroma_fetch(const uint8_t* __restrict__ sf, const YuvGeom& k, int crow, int x0, int npx, uint32_t cu[4], uint32_t cv[4]) {
+    using T = PixTraits<F>;
+    const uint8_t* up = sf + k.off_c + (size_t)crow * k.pitch_c;
+    const uint8_t* vp = sf + k.off_v + (size_t)crow * k.pitch_c;
+    if (T::semi) {
+        yuv_fetch<F, FAST, 4>(up + x0 * T::ss, npx, cu);
+    } else if (T::hsub) {
+        yuv_fetch<F, FAST, 2>(up + (x0 >> 1) * T::ss, npx >> 1, cu);
+        yuv_fetch<F, FAST, 2>(vp + (x0 >> 1) * T::ss, npx >> 1, cv);
+    } else {
+        yuv_fetch<F, FAST, 4>(up + x0 * T::ss, npx, cu);
+        yuv_fetch<F, FAST, 4>(vp + x0 * T::ss, npx, cv);
+    }
 }
 
-// the 16 x 2 block (row pair rp, column group cg) of the frame that starts at sf, converted into the h x w x 3 frame at df
-template <bool NV12, bool FAST>
-__device__ __forceinline__ void frame_block(const uint8_t* __restrict__ sf, uint8_t* __restrict__ df, const YuvGeom& k, int rp, int cg) {
-    const int x0 = cg * 16;
-    const int npx = min(16, k.w - x0);                      // even; 16 on the fast path
-    const uint8_t* y0p = sf + (size_t)(2 * rp) * k.pitch_y + x0;
-    const uint8_t* y1p = y0p + k.pitch_y;
-
-    uint32_t yw[2][4], cw[4];
-    if (FAST) {
-        const uint4 a = *(const uint4*)y0p, b = *(const uint4*)y1p;
-        yw[0][0] = a.x; yw[0][1] = a.y; yw[0][2] = a.z; yw[0][3] = a.w;
-        yw[1][0] = b.x; yw[1][1] = b.y; yw[1][2] = b.z; yw[1][3] = b.w;
-        if (NV12) {
-            const uint4 c = *(const uint4*)(sf + k.off_c + (size_t)rp * k.pitch_c + x0);
-            cw[0] = c.x; cw[1] = c.y; cw[2] = c.z; cw[3] = c.w;
-        } else {
-            const uint2 u = *(const uint2*)(sf + k.off_c + (size_t)rp * k.pitch_c + (x0 >> 1));
-            const uint2 v = *(const uint2*)(sf + k.off_v + (size_t)rp * k.pitch_c + (x0 >> 1));
-            const uint32_t uu[2] = {u.x, u.y}, vv[2] = {v.x, v.y};
+// the chroma terms of the 8 pixel pairs of a row whose chroma is at half width
+template <int F>
+__device__ __forceinline__ void chroma_terms(const uint32_t cu[4], const uint32_t cv[4], const YuvGeom& k, YuvChroma ch[8]) {
+    if (PixTraits<F>::semi) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t us = uu[j >> 1] >> (16 * (j & 1)), vs = vv[j >> 1] >> (16 * (j & 1));
-                cw[j] = (us & 255) | ((vs & 255) << 8) | ((us & 0xff00) << 8) | ((vs & 0xff00) << 16);
-            }
+        for (int j = 0; j < 4; ++j) {
+            ch[2 * j] = yuv_chroma(cu[j] & 255, (cu[j] >> 8) & 255, k);
+            ch[2 * j + 1] = yuv_chroma((cu[j] >> 16) & 255, cu[j] >> 24, k);
         }
     } else {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = npx - 4 * j;                      // pixels of this group of four that exist
-            yw[0][j] = yuv_bytes4(y0p + 4 * j, n);
-            yw[1][j] = yuv_bytes4(y1p + 4 * j, n);
-            if (NV12) {
-                cw[j] = yuv_bytes4(sf + k.off_c + (size_t)rp * k.pitch_c + x0 + 4 * j, n);
-            } else {
-                const uint32_t us = yuv_bytes4(sf + k.off_c + (size_t)rp * k.pitch_c + (x0 >> 1) + 2 * j, n >> 1);
-                const uint32_t vs = yuv_bytes4(sf + k.off_v + (size_t)rp * k.pitch_c + (x0 >> 1) + 2 * j, n >> 1);
-                cw[j] = (us & 255) | ((vs & 255) << 8) | ((us & 0xff00) << 8) | ((vs & 0xff00) << 16);
-            }
-        }
+        for (int i = 0; i < 8; ++i) ch[i] = yuv_chroma((cu[i >> 2] >> (8 * (i & 3))) & 255, (cv[i >> 2] >> (8 * (i & 3))) & 255, k);
+    }
+}
+
+// the 16 x 2 block (row pair rp, column group cg) of the frame that starts at sf, converted into the h x w x 3 frame at df.  The format
+// decides how the lane fetches its samples and which chroma row and column a pixel uses; everything after the fetch is shared.  A second
+// row that does not exist (odd h: I422 / I444 only) is neither loaded nor stored.
+template <int F, bool FAST>
+__device__ __forceinline__ void frame_block(const uint8_t* __restrict__ sf, uint8_t* __restrict__ df, const YuvGeom& k, int rp, int cg) {
+    using T = PixTraits<F>;
+    const int x0 = cg * 16;
+    const int npx = min(16, k.w - x0);                      // 16 on the fast path
+    const int rows = T::vsub ? 2 : min(2, k.h - 2 * rp);
+    const uint8_t* y0p = sf + (size_t)(2 * rp) * k.pitch_y + x0 * T::ss;
+
+    uint32_t yw[2][4], cu[2][4], cv[2][4];
+    yuv_fetch<F, FAST, 4>(y0p, npx, yw[0]);
+    if (rows == 2) yuv_fetch<F, FAST, 4>(y0p + k.pitch_y, npx, yw[1]);
+    if (T::vsub) {
+        chroma_fetch<F, FAST>(sf, k, rp, x0, npx, cu[0], cv[0]);
+    } else {
+        chroma_fetch<F, FAST>(sf, k, 2 * rp, x0, npx, cu[0], cv[0]);
+        if (rows == 2) chroma_fetch<F, FAST>(sf, k, 2 * rp + 1, x0, npx, cu[1], cv[1]);
     }
 
     YuvChroma ch[8];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        ch[2 * j] = yuv_chroma(cw[j] & 255, (cw[j] >> 8) & 255, k);
-        ch[2 * j + 1] = yuv_chroma((cw[j] >> 16) & 255, cw[j] >> 24, k);
-    }
-#pragma unroll
     for (int r = 0; r < 2; ++r) {
-        uint32_t o[12];
-        yuv_row16(yw[r], ch, k, o);
-        uint8_t* d = df + ((size_t)(2 * rp + r) * k.w + x0) * 3;
-        if (FAST) {
-            uint4* d4 = (uint4*)d;
-            d4[0] = make_uint4(o[0], o[1], o[2], o[3]);
-            d4[1] = make_uint4(o[4], o[5], o[6], o[7]);
-            d4[2] = make_uint4(o[8], o[9], o[10], o[11]);
-        } else {
+        if (r < rows) {
+            const int cr = T::vsub ? 0 : r;
+            if (T::hsub && (r == 0 || !T::vsub)) chroma_terms<F>(cu[cr], cv[cr], k, ch);
+            uint32_t o[12];
+            yuv_row16<T::hsub>(yw[r], ch, cu[cr], cv[cr], k, o);
+            uint8_t* d = df + ((size_t)(2 * rp + r) * k.w + x0) * 3;
+            if (FAST) {
+                uint4* d4 = (uint4*)d;
+                d4[0] = make_uint4(o[0], o[1], o[2], o[3]);
+                d4[1] = make_uint4(o[4], o[5], o[6], o[7]);
+                d4[2] = make_uint4(o[8], o[9], o[10], o[11]);
+            } else {
 #pragma unroll
-            for (int i = 0; i < 48; ++i)
-                if (i < npx * 3) d[i] = (uint8_t)(o[i >> 2] >> (8 * (i & 3)));
+                for (int i = 0; i < 48; ++i)
+                    if (i < npx * 3) d[i] = (uint8_t)(o[i >> 2] >> (8 * (i & 3)));
+            }
         }
     }
 }
 
 // grid: one lane per (frame, row pair, 16-pixel column group), flattened in that order so that a wavefront walks along a row pair
-template <bool NV12, bool FAST>
+template <int F, bool FAST>
 __global__ __launch_bounds__(256) void yuv_to_bgr_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, YuvGeom k, int ncg, long long total) {
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
     if (gid >= total) return;
-    const int hp = k.h >> 1;
+    const int hp = (k.h + 1) >> 1;
     const long long rowpair = gid / ncg;
     const int cg = (int)(gid - rowpair * ncg);
     const int f = (int)(rowpair / hp), rp = (int)(rowpair - (long long)f * hp);
-    frame_block<NV12, FAST>(src + (size_t)f * k.frame_stride, dst + (size_t)f * k.h * k.w * 3, k, rp, cg);
+    frame_block<F, FAST>(src + (size_t)f * k.frame_stride, dst + (size_t)f * k.h * k.w * 3, k, rp, cg);
 }
 
 // ---- frame table: one batch whose frames each come from their own place (S decoders' surface pools: own addresses, own pitch, format,
@@ -154,7 +229,8 @@ __global__ __launch_bounds__(256) void yuv_to_bgr_kernel(const uint8_t* __restri
 // fit kernel arguments).  blockIdx.y is the frame, so the entry is workgroup-uniform and neither the format branch nor the 16-byte
 // branch diverges.  Per frame the conversion is yuv_to_bgr_kernel's (frame_block, the same 16 x 2 block per lane); a BGR
 // entry is a byte copy; an entry of kind FRAME_NONE is a frame that is already in place (a host BGR frame copied straight into the slot).
-enum { FRAME_NONE = 0, FRAME_NV12 = 1, FRAME_I420 = 2, FRAME_BGR = 3 };
+enum { FRAME_NONE = 0, FRAME_NV12 = 1, FRAME_I420 = 2, FRAME_BGR = 3, FRAME_P016 = 4, FRAME_I010 = 5, FRAME_I422 = 6, FRAME_I444 = 7 };
+const int kFrameKind[PF_COUNT] = {FRAME_NV12, FRAME_I420, FRAME_P016, FRAME_I010, FRAME_I422, FRAME_I444};      // by YuvGeom::fmt
 struct FrameEntry {
     const uint8_t* src;                                 // device address of the frame
     int kind, fast;                                     // FRAME_*; fast: every address the 16-byte variant forms for THIS frame is aligned
@@ -163,6 +239,12 @@ struct FrameEntry {
     int yoff, cy, cvr, cvg, cug, cub;
 };
 static_assert(sizeof(FrameEntry) == VC_FRAME_ENTRY_BYTES, "FrameEntry is copied to the device as plain bytes");
+
+template <int F>
+__device__ __forceinline__ void frame_block_of(const FrameEntry& e, uint8_t* __restrict__ df, const YuvGeom& k, int rp, int cg) {
+    if (e.fast) frame_block<F, true>(e.src, df, k, rp, cg);
+    else frame_block<F, false>(e.src, df, k, rp, cg);
+}
 
 // one frame of a table-driven batch: this lane's share of entry e (workgroup-uniform), converted or copied into the frame at df
 __device__ __forceinline__ void frame_convert(const FrameEntry& e, uint8_t* __restrict__ df, int h, int w, int ncg) {
@@ -179,17 +261,19 @@ __device__ __forceinline__ void frame_convert(const FrameEntry& e, uint8_t* __re
         }
         return;
     }
-    if (lid >= (h >> 1) * ncg) return;
+    if (lid >= ((h + 1) >> 1) * ncg) return;
     const int rp = lid / ncg, cg = lid - rp * ncg;
     YuvGeom k;
     k.h = h; k.w = w; k.pitch_y = e.pitch_y; k.pitch_c = e.pitch_c; k.off_c = e.off_c; k.off_v = e.off_v;
     k.yoff = e.yoff; k.cy = e.cy; k.cvr = e.cvr; k.cvg = e.cvg; k.cug = e.cug; k.cub = e.cub;
-    if (e.kind == FRAME_NV12) {
-        if (e.fast) frame_block<true, true>(e.src, df, k, rp, cg);
-        else frame_block<true, false>(e.src, df, k, rp, cg);
-    } else {
-        if (e.fast) frame_block<false, true>(e.src, df, k, rp, cg);
-        else frame_block<false, false>(e.src, df, k, rp, cg);
+    switch (e.kind) {                                       // workgroup-uniform, like e.fast
+    case FRAME_NV12: frame_block_of<PF_NV12>(e, df, k, rp, cg); break;
+    case FRAME_I420: frame_block_of<PF_I420>(e, df, k, rp, cg); break;
+    case FRAME_P016: frame_block_of<PF_P016>(e, df, k, rp, cg); break;
+    case FRAME_I010: frame_block_of<PF_I010>(e, df, k, rp, cg); break;
+    case FRAME_I422: frame_block_of<PF_I422>(e, df, k, rp, cg); break;
+    case FRAME_I444: frame_block_of<PF_I444>(e, df, k, rp, cg); break;
+    default: break;
     }
 }
 
@@ -215,32 +299,45 @@ __global__ __launch_bounds__(256) void frames_to_bgr_sized_kernel(const FrameEnt
     frame_convert(e, dst + c.dst_off, c.h, c.w, (c.w + 15) >> 4);
 }
 
+template <int F>
+void launch_yuv_fmt(bool fast, dim3 grid, hipStream_t s, const uint8_t* src, uint8_t* dst, const YuvGeom& g, int ncg, long long total) {
+    if (fast) hipLaunchKernelGGL((yuv_to_bgr_kernel<F, true>), grid, dim3(256), 0, s, src, dst, g, ncg, total);
+    else hipLaunchKernelGGL((yuv_to_bgr_kernel<F, false>), grid, dim3(256), 0, s, src, dst, g, ncg, total);
+}
+
 }  // namespace
 
 // Validates a descriptor for b frames of h x w and resolves its zeros.  Pure host code: runs before any HIP call.
 int yuv_resolve(const vc_yuv_desc* d, int b, int h, int w, YuvGeom& g) {
     VC_CHECK(d, VC_ERR_ARG, "null vc_yuv_desc");
-    VC_CHECK(d->format == VC_PIX_NV12 || d->format == VC_PIX_I420, VC_ERR_ARG, "unknown pixel format %d (VC_PIX_NV12 / VC_PIX_I420)", d->format);
+    const bool known = d->format == VC_PIX_NV12 || d->format == VC_PIX_I420 || (d->format >= VC_PIX_P016 && d->format <= VC_PIX_I444);
+    VC_CHECK(known, VC_ERR_ARG, "unknown pixel format %d (VC_PIX_NV12 / VC_PIX_I420 / VC_PIX_P016 / VC_PIX_I010 / VC_PIX_I422 / VC_PIX_I444)", d->format);
     VC_CHECK(d->matrix == VC_YUV_BT601 || d->matrix == VC_YUV_BT709, VC_ERR_ARG, "unknown colour matrix %d (VC_YUV_BT601 / VC_YUV_BT709)", d->matrix);
     VC_CHECK(d->full_range == 0 || d->full_range == 1, VC_ERR_ARG, "full_range must be 0 or 1");
-    VC_CHECK(b >= 1 && h >= 2 && w >= 2, VC_ERR_ARG, "bad batch of %d frames %dx%d", b, h, w);
-    VC_CHECK(h % 2 == 0 && w % 2 == 0, VC_ERR_ARG, "4:2:0 frames need an even height and width, got %dx%d", h, w);
-    g.nv12 = d->format == VC_PIX_NV12;
+    g.fmt = d->format >= VC_PIX_P016 ? PF_P016 + (d->format - VC_PIX_P016) : d->format;
+    g.nv12 = g.fmt == PF_NV12;
+    const bool semi = g.fmt == PF_NV12 || g.fmt == PF_P016, vsub = g.fmt != PF_I422 && g.fmt != PF_I444, hsub = g.fmt != PF_I444;
+    const int ss = g.fmt == PF_P016 || g.fmt == PF_I010 ? 2 : 1;               // bytes of one sample
+    VC_CHECK(b >= 1 && h >= (vsub ? 2 : 1) && w >= (hsub ? 2 : 1), VC_ERR_ARG, "bad batch of %d frames %dx%d", b, h, w);
+    if (vsub) VC_CHECK(h % 2 == 0 && w % 2 == 0, VC_ERR_ARG, "4:2:0 frames need an even height and width, got %dx%d", h, w);
+    if (hsub) VC_CHECK(w % 2 == 0, VC_ERR_ARG, "4:2:2 frames need an even width, got %dx%d", h, w);
+    VC_CHECK(ss == 1 || w <= (1 << 29), VC_ERR_ARG, "bad batch of %d frames %dx%d", b, h, w);      // 2 * w is an int
     g.h = h; g.w = w;
-    const int crow = g.nv12 ? w : w / 2;                                      // bytes of one chroma row
-    g.pitch_y = d->pitch_y ? d->pitch_y : w;
+    const int rowb = w * ss;                                                   // bytes of one luma row
+    const int crow = (semi || !hsub ? w : w / 2) * ss;                         // bytes of one chroma row
+    g.pitch_y = d->pitch_y ? d->pitch_y : rowb;
     g.pitch_c = d->pitch_c ? d->pitch_c : crow;
-    VC_CHECK(g.pitch_y >= w, VC_ERR_ARG, "pitch_y %d is below the row width %d", d->pitch_y, w);
+    VC_CHECK(g.pitch_y >= rowb, VC_ERR_ARG, "pitch_y %d is below the row width %d", d->pitch_y, rowb);
     VC_CHECK(g.pitch_c >= crow, VC_ERR_ARG, "pitch_c %d is below the chroma row width %d", d->pitch_c, crow);
-    const size_t hc = (size_t)h / 2;
-    const size_t len_y = (size_t)g.pitch_y * (h - 1) + w, len_c = (size_t)g.pitch_c * (hc - 1) + crow;
+    const size_t hc = vsub ? (size_t)h / 2 : (size_t)h;                        // chroma rows
+    const size_t len_y = (size_t)g.pitch_y * (h - 1) + rowb, len_c = (size_t)g.pitch_c * (hc - 1) + crow;
     g.off_c = d->offset_c ? d->offset_c : (size_t)g.pitch_y * h;
-    g.off_v = g.nv12 ? 0 : (d->offset_v ? d->offset_v : g.off_c + (size_t)g.pitch_c * hc);
+    g.off_v = semi ? 0 : (d->offset_v ? d->offset_v : g.off_c + (size_t)g.pitch_c * hc);
     const size_t lim = (size_t)1 << 40;                                        // keeps every sum below far from overflow
     VC_CHECK(g.off_c < lim && g.off_v < lim && d->frame_stride < lim, VC_ERR_ARG, "plane offset or frame stride out of range");
     VC_CHECK(g.off_c >= len_y, VC_ERR_ARG, "the chroma plane (offset %zu) overlaps the luma plane (%zu bytes)", g.off_c, len_y);
     g.frame_end = g.off_c + len_c;
-    if (!g.nv12) {
+    if (!semi) {
         VC_CHECK(g.off_v >= len_y, VC_ERR_ARG, "the V plane (offset %zu) overlaps the luma plane (%zu bytes)", g.off_v, len_y);
         VC_CHECK(g.off_v >= g.off_c + len_c || g.off_c >= g.off_v + len_c, VC_ERR_ARG, "the U and V planes overlap (offsets %zu, %zu)", g.off_c, g.off_v);
         g.frame_end = std::max(g.frame_end, g.off_v + len_c);
@@ -252,6 +349,12 @@ int yuv_resolve(const vc_yuv_desc* d, int b, int h, int w, YuvGeom& g) {
     g.yoff = d->full_range ? 0 : 16;
     g.cy = c[0]; g.cvr = c[1]; g.cvg = c[2]; g.cug = c[3]; g.cub = c[4];
     return VC_OK;
+}
+
+int yuv_resolve_out(const vc_yuv_desc* d, int b, int h, int w, YuvGeom& g) {
+    VC_CHECK(!d || d->format < VC_PIX_P016 || d->format > VC_PIX_I444, VC_ERR_ARG,
+             "pixel format %d is an ingest-only format: egress writes VC_PIX_NV12 / VC_PIX_I420", d->format);
+    return yuv_resolve(d, b, h, w, g);
 }
 
 int sized_dims_resolve(const vc_frame_dims* dims, int b, int img_size, SizedDims& out) {
@@ -280,16 +383,18 @@ int launch_yuv_to_bgr(const YuvGeom& g, const uint8_t* src, uint8_t* dst, int b,
     const bool fast = g.w % 16 == 0 && g.pitch_y % 16 == 0 && g.pitch_c % 16 == 0 && g.off_c % 16 == 0 && g.off_v % 16 == 0 &&
                       g.frame_stride % 16 == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0;
     const int ncg = (g.w + 15) / 16;
-    const long long total = (long long)b * (g.h / 2) * ncg;
+    const long long total = (long long)b * ((g.h + 1) / 2) * ncg;
     const long long blocks = (total + 255) / 256;
     VC_CHECK(blocks <= 0x7fffffffll, VC_ERR_CAPACITY, "batch too large for one conversion launch");
-    const dim3 grid((unsigned)blocks), block(256);
-    if (g.nv12) {
-        if (fast) hipLaunchKernelGGL((yuv_to_bgr_kernel<true, true>), grid, block, 0, s, src, dst, g, ncg, total);
-        else hipLaunchKernelGGL((yuv_to_bgr_kernel<true, false>), grid, block, 0, s, src, dst, g, ncg, total);
-    } else {
-        if (fast) hipLaunchKernelGGL((yuv_to_bgr_kernel<false, true>), grid, block, 0, s, src, dst, g, ncg, total);
-        else hipLaunchKernelGGL((yuv_to_bgr_kernel<false, false>), grid, block, 0, s, src, dst, g, ncg, total);
+    const dim3 grid((unsigned)blocks);
+    switch (g.fmt) {
+    case PF_NV12: launch_yuv_fmt<PF_NV12>(fast, grid, s, src, dst, g, ncg, total); break;
+    case PF_I420: launch_yuv_fmt<PF_I420>(fast, grid, s, src, dst, g, ncg, total); break;
+    case PF_P016: launch_yuv_fmt<PF_P016>(fast, grid, s, src, dst, g, ncg, total); break;
+    case PF_I010: launch_yuv_fmt<PF_I010>(fast, grid, s, src, dst, g, ncg, total); break;
+    case PF_I422: launch_yuv_fmt<PF_I422>(fast, grid, s, src, dst, g, ncg, total); break;
+    case PF_I444: launch_yuv_fmt<PF_I444>(fast, grid, s, src, dst, g, ncg, total); break;
+    default: VC_CHECK(false, VC_ERR_ARG, "unresolved pixel format %d", g.fmt);
     }
     VC_HIP(hipGetLastError());
     return VC_OK;
@@ -358,7 +463,7 @@ FrameEntry frame_entry(int src_kind, const YuvGeom& g, const uint8_t* src, const
         t.fast = ends && ((size_t)h * w * 3) % 16 == 0;
         return t;
     }
-    t.kind = g.nv12 ? FRAME_NV12 : FRAME_I420;
+    t.kind = kFrameKind[g.fmt];
     // launch_yuv_to_bgr's test with this frame's own addresses in place of the batch's base and stride
     t.fast = g.w % 16 == 0 && g.pitch_y % 16 == 0 && g.pitch_c % 16 == 0 && g.off_c % 16 == 0 && g.off_v % 16 == 0 && ends;
     t.pitch_y = g.pitch_y; t.pitch_c = g.pitch_c; t.off_c = g.off_c; t.off_v = g.off_v;

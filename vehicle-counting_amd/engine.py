@@ -341,8 +341,9 @@ class Engine:
         return out.value
 
     def stream_stage_yuv_host(self, yuv_host_ptr, b, h, w, desc=None):
-        """Like stream_stage_host for a batch of 4:2:0 YUV frames in (pinned) host memory laid out as `desc` (`yuv_desc(...)`; None:
-        tight NV12, BT.601 limited): the raw bytes cross PCIe (1.5 B per pixel) and are converted on the engine's copy stream;
+        """Like stream_stage_host for a batch of YUV frames in (pinned) host memory laid out as `desc` (`yuv_desc(...)`, any of its
+        formats; None: tight NV12, BT.601 limited): the raw bytes cross PCIe (1.5 B per pixel for 8-bit 4:2:0, 2 for i422, 3 for p016 /
+        i010 / i444) and are converted on the engine's copy stream;
         returns the device address of the BGR batch for stream_submit / stream_run*."""
         out = C.c_void_p()
         d = desc if desc is not None else yuv_desc()
@@ -780,21 +781,41 @@ def reid_stem_pool(crops, w_oihw, bias):
 
 
 def yuv_desc(fmt="nv12", matrix="bt601", full_range=False, pitch_y=0, pitch_c=0, offset_c=0, offset_v=0, frame_stride=0):
-    """vc_yuv_desc: layout of 4:2:0 frames in bytes (0 = tightly packed; include/vcount_hip.h)."""
-    if fmt not in L.PIX_ID:
-        raise ValueError(f"unknown pixel format {fmt!r}: one of {sorted(L.PIX_ID)}")
+    """vc_yuv_desc: layout of YUV frames in bytes (0 = tightly packed; include/vcount_hip.h).  fmt: "nv12" / "i420" (8-bit 4:2:0), or for
+    ingest only "p016" (16-bit NV12 layout, significant bits at the top: P010 / P012 surfaces are passed as "p016"), "i010" (yuv420p10le),
+    "i422", "i444"."""
+    if fmt not in L.PIX_ID and fmt not in L.PIX_WIDE_ID:
+        raise ValueError(f"unknown pixel format {fmt!r}: one of {sorted(L.PIX_ID) + sorted(L.PIX_WIDE_ID)}")
     if matrix not in L.YUV_MATRIX_ID:
         raise ValueError(f"unknown colour matrix {matrix!r}: one of {sorted(L.YUV_MATRIX_ID)}")
-    return L.YuvDesc(L.PIX_ID[fmt], L.YUV_MATRIX_ID[matrix], 1 if full_range else 0, int(pitch_y), int(pitch_c), int(offset_c), int(offset_v),
-                     int(frame_stride))
+    return L.YuvDesc(L.PIX_ID[fmt] if fmt in L.PIX_ID else L.PIX_WIDE_ID[fmt], L.YUV_MATRIX_ID[matrix], 1 if full_range else 0, int(pitch_y), int(pitch_c),
+                     int(offset_c), int(offset_v), int(frame_stride))
+
+
+def yuv_format_rows(format_id, h, w):
+    """What a pixel format id (PIX_ID / PIX_WIDE_ID) makes of an h x w frame: (luma row bytes, chroma row bytes, chroma rows, U and V
+    share a plane, the size is one the format takes); None for an unknown id."""
+    #        sample bytes, interleaved, chroma at half height, chroma at half width
+    table = {0: (1, True, True, True), 1: (1, False, True, True), 16: (2, True, True, True), 17: (2, False, True, True),
+             18: (1, False, False, True), 19: (1, False, False, False)}
+    if format_id not in table:
+        return None
+    ss, semi, vsub, hsub = table[format_id]
+    size_ok = h >= (2 if vsub else 1) and w >= (2 if hsub else 1) and not (vsub and h % 2) and not (hsub and w % 2)
+    return w * ss, (w if semi or not hsub else w // 2) * ss, (h // 2 if vsub else h), semi, size_ok
 
 
 def yuv_to_bgr(yuv, b, h, w, fmt="nv12", matrix="bt601", full_range=False, *, desc=None, **geometry):
-    """yuv_to_bgr_kernel on a host array: `yuv` = uint8 bytes of b frames laid out as the descriptor says -> (b, h, w, 3) BGR."""
+    """yuv_to_bgr_kernel on a host array: `yuv` = uint8 bytes of b frames laid out as the descriptor says -> (b, h, w, 3) BGR.  For the
+    16-bit formats ("p016": P010 / P012 / P016 surfaces, "i010") a uint16 array is taken as its bytes."""
     d = desc if desc is not None else yuv_desc(fmt, matrix, full_range, **geometry)
+    yuv = np.asarray(yuv)
+    if yuv.dtype == np.uint16 and d.format in (L.PIX_WIDE_ID["p016"], L.PIX_WIDE_ID["i010"]):
+        yuv = np.ascontiguousarray(yuv).astype("<u2", copy=False).view(np.uint8)
     src = np.ascontiguousarray(yuv, dtype=np.uint8).reshape(-1)
     out = np.zeros((b, h, w, 3), np.uint8)
-    if b >= 1 and h >= 2 and w >= 2 and h % 2 == 0 and w % 2 == 0:      # the library refuses anything else; the length check needs a valid geometry
+    rows = yuv_format_rows(d.format, h, w)
+    if b >= 1 and rows is not None and rows[4]:      # the library refuses anything else; the length check needs a valid geometry
         need = yuv_batch_bytes(d, b, h, w)
         if need is not None and src.size < need:
             raise ValueError(f"yuv holds {src.size} bytes, the descriptor needs {need}")
@@ -911,22 +932,28 @@ def yuv_to_bgr_dev(yuv_dev_ptr, b, h, w, bgr_dev_ptr, desc=None):
 
 
 def yuv_batch_bytes(d, b, h, w):
-    """Bytes that b frames of h x w occupy under descriptor d (the zeros resolved like the library does); None if a pitch is too small."""
-    crow = w if d.format == 0 else w // 2
-    py, pc = d.pitch_y or w, d.pitch_c or crow
-    if py < w or pc < crow:
+    """Bytes that b frames of h x w occupy under descriptor d (the zeros resolved like the library does); None if a pitch is too small
+    (or the format id is unknown)."""
+    rows = yuv_format_rows(d.format, h, w)
+    if rows is None:
+        return None
+    rowb, crow, hc, semi, _ = rows
+    py, pc = d.pitch_y or rowb, d.pitch_c or crow
+    if py < rowb or pc < crow:
         return None
     off_c = d.offset_c or py * h
-    end = off_c + pc * (h // 2 - 1) + crow
-    if d.format != 0:
-        off_v = d.offset_v or off_c + pc * (h // 2)
-        end = max(end, off_v + pc * (h // 2 - 1) + crow)
+    end = off_c + pc * (hc - 1) + crow
+    if not semi:
+        off_v = d.offset_v or off_c + pc * hc
+        end = max(end, off_v + pc * (hc - 1) + crow)
     return (b - 1) * (d.frame_stride or end) + end
 
 
 def bgr_to_yuv(bgr, fmt="nv12", matrix="bt601", full_range=False, *, desc=None, **geometry):
     """bgr_to_yuv_kernel on a host array: (b, h, w, 3) uint8 BGR -> flat uint8 bytes of b frames laid out as the descriptor says
-    (`yuv_batch_bytes` of them).  Bytes that belong to no plane come back as the zero fill."""
+    (`yuv_batch_bytes` of them).  Bytes that belong to no plane come back as the zero fill.  Egress writes "nv12" / "i420" only."""
+    if desc is None and fmt in L.PIX_WIDE_ID:
+        raise ValueError(f"pixel format {fmt!r} is ingest only: egress writes one of {sorted(L.PIX_ID)}")
     d = desc if desc is not None else yuv_desc(fmt, matrix, full_range, **geometry)
     src = np.ascontiguousarray(bgr, dtype=np.uint8)
     if src.ndim != 4 or src.shape[3] != 3:

@@ -41,24 +41,28 @@ class FrameSource:
 
 
 def _yuv_geometry(h, w, fmt, matrix, full_range, pitch, pitch_c, offset_c, offset_v, frame_stride):
-    """(vc_yuv_desc, bytes from one frame to the next) of a clip of 4:2:0 frames.  Unless given, the chroma pitch follows the luma
-    pitch (`pitch` for nv12, `pitch // 2` for i420), the planes follow each other without a gap, and a frame ends with the last whole
-    row of its last plane."""
-    from .engine import yuv_batch_bytes, yuv_desc
+    """(vc_yuv_desc, bytes from one frame to the next) of a clip of YUV frames.  Unless given, the chroma pitch follows the luma pitch
+    (`pitch` where a chroma row has the bytes of a luma row: nv12, p016, i444; `pitch // 2` for i420, i010, i422), the planes follow each
+    other without a gap, and a frame ends with the last whole row of its last plane."""
+    from .engine import yuv_batch_bytes, yuv_desc, yuv_format_rows
     h, w, pitch, pitch_c = int(h), int(w), int(pitch), int(pitch_c)
-    if h < 2 or w < 2 or h % 2 or w % 2:
+    d = yuv_desc(fmt, matrix, full_range)                   # the name first: an unknown one has no size rule
+    rowb, crow, hc, semi, size_ok = yuv_format_rows(d.format, h, w)
+    if not size_ok:
+        if fmt in ("i422", "i444"):
+            raise ValueError(f"{fmt} frames need {'an even width' if fmt == 'i422' else 'a height and width of at least 1'}, got {h}x{w}")
         raise ValueError(f"4:2:0 frames need an even height and width, got {h}x{w}")
     if pitch and not pitch_c:
-        if fmt == "i420" and pitch % 2:
-            raise ValueError("an odd luma pitch needs an explicit pitch_c for i420")
-        pitch_c = pitch if fmt == "nv12" else pitch // 2
+        if crow != rowb and pitch % 2:
+            raise ValueError(f"an odd luma pitch needs an explicit pitch_c for {fmt}")
+        pitch_c = pitch if crow == rowb else pitch // 2
     d = yuv_desc(fmt, matrix, full_range, pitch, pitch_c, offset_c, offset_v, frame_stride)
     frame_bytes = yuv_batch_bytes(d, 1, h, w)
     if frame_bytes is None:
         raise ValueError(f"pitch {pitch} / {pitch_c} is below the row width of a {w}-wide {fmt} frame")
-    pc, hc = d.pitch_c or (w if fmt == "nv12" else w // 2), h // 2    # default stride: whole rows of the last plane (= the frame's bytes when tight)
-    off_c = d.offset_c or (d.pitch_y or w) * h
-    whole = off_c + pc * hc if fmt == "nv12" else max(off_c + pc * hc, (d.offset_v or off_c + pc * hc) + pc * hc)
+    pc = d.pitch_c or crow                                  # default stride: whole rows of the last plane (= the frame's bytes when tight)
+    off_c = d.offset_c or (d.pitch_y or rowb) * h
+    whole = off_c + pc * hc if semi else max(off_c + pc * hc, (d.offset_v or off_c + pc * hc) + pc * hc)
     stride = int(frame_stride) or whole
     if stride < frame_bytes:
         raise ValueError(f"frame_stride {stride} is below the frame's {frame_bytes} bytes")
@@ -66,10 +70,12 @@ def _yuv_geometry(h, w, fmt, matrix, full_range, pitch, pitch_c, offset_c, offse
 
 
 class YuvFrameSource:
-    """In-memory video as a decoder delivers it: T frames of 4:2:0 YUV (`fmt` "nv12" or "i420"), `data` = uint8 array whose first axis
-    is the frame (or a flat buffer of T whole frames).  Geometry in bytes, 0 = tightly packed (include/vcount_hip.h: vc_yuv_desc):
-    `pitch` is the luma pitch; unless given, the chroma pitch follows it (`pitch` for nv12, `pitch // 2` for i420), the planes
-    follow each other without a gap and a frame ends with the last whole row of its last plane.  
+    """In-memory video as a decoder delivers it: T frames of YUV, `data` = uint8 array whose first axis is the frame (or a flat buffer
+    of T whole frames).  `fmt`: "nv12" or "i420" (8-bit 4:2:0); "p016" (the NV12 layout with 16-bit samples, significant bits at the top:
+    P010 / P012 surfaces are passed as "p016") or "i010" (yuv420p10le), for which `data` may also be a uint16 array, taken as its bytes;
+    "i422" (any height) or "i444" (any height and width), 8-bit planar.  Geometry in bytes, 0 = tightly packed (include/vcount_hip.h:
+    vc_yuv_desc): `pitch` is the luma pitch; unless given, the chroma pitch follows it (`pitch` for nv12, p016 and i444, `pitch // 2`
+    for i420, i010 and i422), the planes follow each other without a gap and a frame ends with the last whole row of its last plane.
     `CountingPipeline.run_stream` takes it, and so does `run_streams` (one per camera, mixed freely with BGR `FrameSource`s and with
     YUV sources of other formats and pitches); `render` reads it as well.  The conversion to BGR runs on the device."""
 
@@ -77,6 +83,10 @@ class YuvFrameSource:
                  frame_stride=0, name="cam_04.mp4", fps=10):
         h, w = int(h), int(w)
         self.desc, stride = _yuv_geometry(h, w, fmt, matrix, full_range, pitch, pitch_c, offset_c, offset_v, frame_stride)
+        data = np.asarray(data)
+        if data.dtype == np.uint16 and fmt in ("p016", "i010"):                # 16-bit samples: little-endian bytes, the frame axis kept
+            data = np.ascontiguousarray(data).astype("<u2", copy=False)
+            data = data.view(np.uint8).reshape(data.shape[:-1] + (-1,)) if data.ndim > 1 else data.view(np.uint8)
         data = np.ascontiguousarray(data, dtype=np.uint8)
         if data.ndim == 1:
             if data.size == 0 or data.size % stride:
@@ -105,6 +115,9 @@ class YuvFrameSink:
         h, w, n_frames = int(h), int(w), int(n_frames)
         if n_frames < 1:
             raise ValueError(f"a sink needs at least one frame, got {n_frames}")
+        from ._lib import PIX_ID
+        if fmt not in PIX_ID:
+            raise ValueError(f"unknown egress pixel format {fmt!r}: a sink takes one of {sorted(PIX_ID)} (the wider formats are ingest only)")
         self.desc, stride = _yuv_geometry(h, w, fmt, matrix, full_range, pitch, pitch_c, offset_c, offset_v, frame_stride)
         self.desc.frame_stride = stride
         self.h, self.w, self.fmt, self.n_frames, self.frame_stride = h, w, fmt, n_frames, stride
@@ -274,8 +287,9 @@ class CountingPipeline:
         host_frames=True: the frames stay in (pinned) host memory, as the reference's loader delivers them, and cross PCIe batch by
         batch -- batch n+2 is staged (`stream_stage_host`) while the detector works on batch n+1, so a video of any length needs four
         batches of device memory; otherwise the whole clip is uploaded once.
-        A `YuvFrameSource` takes the same modes: its 4:2:0 frames are converted to BGR on the device as they are staged
-        (`stream_stage_yuv_host` from pinned YUV, half the PCIe bytes of BGR, or `stream_stage_yuv_dev` from the uploaded clip)."""
+        A `YuvFrameSource` takes the same modes: its frames (any of its formats) are converted to BGR on the device as they are staged
+        (`stream_stage_yuv_host` from pinned YUV -- half the PCIe bytes of BGR for 8-bit 4:2:0, two thirds for i422, the same for p016 /
+        i010 / i444 -- or `stream_stage_yuv_dev` from the uploaded clip)."""
         import torch
         tracker, counter = self._stages(cam_name, source.video_info, zone_path)
         obj = {"frames": [], "tracks": [], "labels": [], "boxes": []}
