@@ -325,6 +325,46 @@ int vc_comm_init(vc_engine* e, int rank, int world, const void* id128);
 int vc_comm_destroy(vc_engine* e);
 int vc_allgather_counts(vc_engine* e, const int32_t* local, int n, int32_t* out);
 
+/* ---- live counts: the same counts while the stream runs, kept on the device beside the tracker (csrc/live_count.hip) --------------
+ * The rule: the counts read at any moment equal vc_counts of a vc_counter that was fed exactly the rows of all batches enqueued so far
+ * (per camera, frame = the camera's 1-based frame number) -- utilities/counting/utils.py:276-297 for the video cut at that point, with
+ * utilities/counting/utils.py:139-152 (Q11) and utilities/counting/bb_polygon.py:96-114 (Q12) as above, integer for integer.  No row is
+ * kept: the state is one 88-byte record per tracker pool slot (vc_engine_config.max_tracks) and one int32 tensor per counter.
+ *
+ * vc_live_create attaches the counter to n_cam x n_labels trackers of the engine, trackers[cam * n_labels + label] (handles of
+ * vc_tracker_create).  polygons: the cameras' zone polygons one after the other, poly_n[cam] points (x, y) each; dir_lines: their
+ * direction lines one after the other, n_dir[cam] lines (x0, y0, x1, y1) each.  More than 64 points or 16 directions for a camera is
+ * VC_ERR_CAPACITY; a tracker that is attached already (or named twice) VC_ERR_STATE; a bad handle VC_ERR_NOTFOUND.  From then on
+ * EVERY tracker launch of the engine that steps one of these trackers -- the stream path, vc_videotracker_run*, vc_deepsort_update,
+ * vc_tracker_step -- advances the counter on the tracker stream; rows, vc_stream_collect and every other result are what they are
+ * without a counter.  While attached, vc_tracker_reset / vc_tracker_destroy / vc_tracker_restore of such a tracker are VC_ERR_STATE
+ * (vc_live_destroy first); vc_stream_reset leaves the counter as the batches that ran left it.
+ * Counts are int32 [n_cam][max_dir][n_labels], max_dir = the largest n_dir; rows d >= n_dir[cam] are zero. */
+typedef struct vc_live vc_live;
+int vc_live_create(vc_engine* e, int n_cam, int n_labels, const int* trackers, const double* polygons, const int* poly_n,
+                   const double* dir_lines, const int* n_dir, vc_live** out);
+int vc_live_destroy(vc_live* live);
+/* waits for the batches enqueued so far; frames_done (optional): per camera, the frames handed to the tracker so far */
+int vc_live_counts(vc_live* live, int32_t* out, int64_t* frames_done);
+/* the same tensor in device memory, valid until the next tracker launch or vc_live_* call of this engine */
+int vc_live_counts_dev(vc_live* live, const int32_t** dev_ptr);
+/* open_tracks: slots that hold a track seen in its zone which can still produce rows; retired_tracks: tracks folded into the totals */
+int vc_live_stats(vc_live* live, int* open_tracks, int* retired_tracks);
+/* ncclAllGather straight from the device tensor on the stream vc_allgather_counts uses (vc_comm_init first): out receives world x
+ * n_cam x max_dir x n_labels values, rank-major; every rank's counter must have the same shape. */
+int vc_live_allgather(vc_engine* e, vc_live* live, int32_t* out);
+/* One launch of live_count_apply_kernel and one of live_count_read_kernel on host arrays (parity tests): zones as for vc_live_create;
+ * tracker_cam[n_trackers] = camera of a tracker, -1 = not attached; slots88 = max_tracks records of 88 bytes {int32 open, cam, label,
+ * at_last; int64 last_frame, first[4], last[4]}, base and stats2 = {open, retired} as the previous batch left them (in / out); the batch:
+ * rows6 [n_rows][6] as the tracker emits them with the pool slot of each in row_slot, tasks5 [n_tasks][5] = {tracker, index into
+ * frame_no, label, first row, rows} with each tracker's tasks contiguous and in frame order, frame_no[n_frames] the camera's 1-based
+ * frame numbers, freed[n_freed] the slots the batch freed.  counts (out) = base + the open slots.  Everything written lies between
+ * guard blocks: a write outside is VC_ERR_HIP. */
+int vc_live_count_host(int n_cam, int n_labels, const double* polygons, const int* poly_n, const double* dir_lines, const int* n_dir,
+                       int n_trackers, const int* tracker_cam, int max_tracks, const int64_t* rows6, const int* row_slot, int n_rows,
+                       const int* tasks5, int n_tasks, const int64_t* frame_no, int n_frames, const int* freed, int n_freed,
+                       void* slots88, int32_t* base, int32_t* stats2, int32_t* counts);
+
 /* ---- visualisation egress (off the hot path) --------------------------------------------------------- */
 /* utilities/counting/utils.py:299-331 visualize_merged: draws the annotation overlay into b BGR u8 frames (h x w x 3) in device
  * memory.  prims12: n x 12 int32 [type, x0, y0, x1, y1, t, colour (B | G << 8 | R << 16), glyph bits lo, glyph bits hi, 0, 0, 0] with

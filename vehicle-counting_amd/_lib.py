@@ -188,6 +188,13 @@ SIGNATURES = {
     "vc_comm_init": [_vp, _i, _i, _vp],
     "vc_comm_destroy": [_vp],
     "vc_allgather_counts": [_vp, _pi, _i, _pi],
+    "vc_live_create": [_vp, _i, _i, _pi, _pd, _pi, _pd, _pi, _P(_vp)],
+    "vc_live_destroy": [_vp],
+    "vc_live_counts": [_vp, _pi, _pl],
+    "vc_live_counts_dev": [_vp, _P(_vp)],
+    "vc_live_stats": [_vp, _pi, _pi],
+    "vc_live_allgather": [_vp, _vp, _pi],
+    "vc_live_count_host": [_i, _i, _pd, _pi, _pd, _pi, _i, _pi, _i, _pl, _pi, _i, _pi, _i, _pl, _i, _pi, _i, _vp, _pi, _pi, _pi],
     "vc_overlay": [_vp, _vp, _i, _i, _i, _pi, _pi],
     "vc_profile_enable": [_vp, _i],
     "vc_profile_conv_busy": [_vp, _pd, _pd],

@@ -5,7 +5,8 @@
 // Reference: /root/reference/modules/track.py:81-137 (VideoCounting.run), utilities/counting/bb_polygon.py:14-124,
 // utilities/counting/utils.py:139-152 (find_best_match_direction: strict '>' from 0, first key as fallback, Q11),
 // utilities/counting/utils.py:276-297 (count_frame_directions: count[direction][label] += 1 where lframe == frame_id).
-// Host arithmetic only (a few thousand rows per video); the same double-precision operations as vehicle-counting_amd/counting.py.
+// Host arithmetic only (a few thousand rows per video); the same double-precision operations as vehicle-counting_amd/counting.py
+// (count_core.h).  The running counts of a stream that never ends are live_count.hip.
 #include <algorithm>
 #include <cmath>
 #include <map>
@@ -14,6 +15,7 @@
 #include <rccl/rccl.h>
 
 #include "engine.h"
+#include "count_core.h"
 
 struct vc_counter {
     std::vector<double> polygon;             // x0, y0, x1, y1, ...
@@ -27,60 +29,11 @@ struct vc_counter {
     size_t n_rows = 0;
 };
 
-// utilities/counting/utils.py:139-152 find_best_match_direction on the centres of a track's first and last box: index of the
-// direction with the largest cosine, strict '>' from 0, the first direction as fallback (Q11)
+// The zone test (any corner of a box in the polygon: ray cast to y = 1e9, exact double compares) and find_best_match_direction on the
+// centres of a track's first and last box are count_core.h, shared with the live-count kernels (live_count.hip).
 static int best_direction(const vc_counter* c, const int64_t* fbox, const int64_t* lbox, double* fpoint, double* lpoint) {
-    const double fx = (double)(fbox[2] + fbox[0]) / 2, fy = (double)(fbox[3] + fbox[1]) / 2;
-    const double lx = (double)(lbox[2] + lbox[0]) / 2, ly = (double)(lbox[3] + lbox[1]) / 2;
-    if (fpoint) { fpoint[0] = fx; fpoint[1] = fy; }
-    if (lpoint) { lpoint[0] = lx; lpoint[1] = ly; }
-    const double ax = lx - fx, ay = ly - fy;
-    const int nd = (int)(c->dirs.size() / 4);
-    double best = 0;
-    int bi = 0;
-    for (int d = 0; d < nd; ++d) {
-        const double* p = &c->dirs[(size_t)d * 4];
-        const double bx = p[2] - p[0], by = p[3] - p[1];
-        const double den = std::sqrt(ax * ax + ay * ay) * std::sqrt(bx * bx + by * by);
-        const double score = (ax * bx + ay * by) / den;           // 0/0 -> NaN, x/0 -> +-inf, like the reference's numpy division
-        if (score > best) { best = score; bi = d; }
-    }
-    return bi;
+    return vc::cc::best_direction(c->dirs.data(), (int)(c->dirs.size() / 4), fbox, lbox, fpoint, lpoint);
 }
-
-// Zone filter of VideoCounting.run (/root/reference/modules/track.py:102-104 -> utilities/counting/bb_polygon.py:14-114):
-// inside[i] = any corner of boxes[i] = (x1,y1,x2,y2) lies in the polygon (ray cast to y = 1e9, exact double compares).
-// Host-only (the post-pass runs once per video on a few thousand rows); same arithmetic as counting.py.
-namespace {
-struct P2 { double x, y; };
-inline int orient(P2 p, P2 q, P2 r) {
-    const double v = (q.y - p.y) * (r.x - q.x) - (q.x - p.x) * (r.y - q.y);
-    return v == 0 ? 0 : (v > 0 ? 1 : 2);
-}
-inline bool on_segment(P2 p, P2 q, P2 r) {
-    return q.x <= std::max(p.x, r.x) && q.x >= std::min(p.x, r.x) && q.y <= std::max(p.y, r.y) && q.y >= std::min(p.y, r.y);
-}
-inline bool intersect(P2 p1, P2 q1, P2 p2, P2 q2) {
-    const int o1 = orient(p1, q1, p2), o2 = orient(p1, q1, q2), o3 = orient(p2, q2, p1), o4 = orient(p2, q2, q1);
-    if (o1 != o2 && o3 != o4) return true;
-    if (o1 == 0 && on_segment(p1, p2, q1)) return true;
-    if (o2 == 0 && on_segment(p1, q2, q1)) return true;
-    if (o3 == 0 && on_segment(p2, p1, q2)) return true;
-    return o4 == 0 && on_segment(p2, q1, q2);
-}
-bool point_in_polygon(const P2* poly, int n, P2 pt) {
-    const P2 far{pt.x, 1e9};
-    int count = 0;
-    for (int i = 0; i < n; ++i) {
-        const P2 a = poly[i], b = poly[(i + 1) % n];
-        if (intersect(a, b, pt, far)) {
-            if (orient(a, pt, b) == 0) return on_segment(a, pt, b);
-            ++count;
-        }
-    }
-    return count % 2 == 1;
-}
-}  // namespace
 
 using namespace vc;
 
@@ -88,12 +41,7 @@ extern "C" {
 
 int vc_zone_filter_host(const double* polygon_xy, int n_points, const int64_t* boxes_xyxy, int n, uint8_t* inside) {
     VC_CHECK(polygon_xy && n_points >= 1 && (n == 0 || (boxes_xyxy && inside)), VC_ERR_ARG, "bad argument");
-    const P2* poly = (const P2*)polygon_xy;
-    for (int i = 0; i < n; ++i) {
-        const double x1 = (double)boxes_xyxy[i * 4], y1 = (double)boxes_xyxy[i * 4 + 1], x2 = (double)boxes_xyxy[i * 4 + 2], y2 = (double)boxes_xyxy[i * 4 + 3];
-        inside[i] = point_in_polygon(poly, n_points, P2{x1, y1}) || point_in_polygon(poly, n_points, P2{x2, y1}) ||
-                    point_in_polygon(poly, n_points, P2{x2, y2}) || point_in_polygon(poly, n_points, P2{x1, y2});
-    }
+    for (int i = 0; i < n; ++i) inside[i] = cc::box_in_polygon(polygon_xy, n_points, boxes_xyxy + (size_t)i * 4);
     return VC_OK;
 }
 
@@ -240,6 +188,27 @@ int vc_allgather_counts(vc_engine* e, const int32_t* local, int n, int32_t* out)
     VC_HIP(hipStreamSynchronize(e->stream));
     return VC_OK;
 }
+
+// The same collective for a live counter (live_count.hip): its device tensor goes into ncclAllGather as it is -- no host copy of the
+// local counts, no upload; only the gathered result crosses to the host.
+}  // extern "C"
+int vc::live_allgather(vc_engine* e, const LiveCountArgs& a, int32_t* out) {
+    VC_CHECK(e->comm, VC_ERR_STATE, "vc_comm_init first");
+    VC_HIP(hipSetDevice(e->cfg.device));
+    const size_t n = (size_t)a.n_cam * a.max_dir * a.n_labels, need = n * e->comm_world * sizeof(int32_t);
+    if (need > e->comm_buf_bytes) {
+        VC_HIP(hipStreamSynchronize(e->stream));
+        VC_TRY(dev_alloc(e, (void**)&e->d_comm_buf, need * 2));
+        e->comm_buf_bytes = need * 2;
+    }
+    VC_TRY(launch_live_count_read(a, e->stream));
+    const ncclResult_t r = ncclAllGather(a.counts, e->d_comm_buf, n, ncclInt32, (ncclComm_t)e->comm, e->stream);
+    VC_CHECK(r == ncclSuccess, VC_ERR_HIP, "ncclAllGather: %s", ncclGetErrorString(r));
+    VC_HIP(hipMemcpyAsync(out, e->d_comm_buf, need, hipMemcpyDeviceToHost, e->stream));
+    VC_HIP(hipStreamSynchronize(e->stream));
+    return VC_OK;
+}
+extern "C" {
 
 // Variable-length all-gather of detection rows and their embeddings (the frame-sharded front end): every rank hands in
 // n rows [7] float64 (host) with the device address of the matching [n][512] float32 embeddings and receives the rows of ALL ranks,

@@ -82,6 +82,8 @@ struct Tracker {
     int pending_dets = 0;            // detections of batches still in flight (each may start a track)
     bool released = false;           // vc_tracker_destroy: the slot is free for the next vc_tracker_create
     int gen = 0;                     // generation of the slot: part of the handle the caller holds
+    vc_live* live = nullptr;         // the live counter this tracker is attached to (live_count.hip), and its camera there
+    int live_cam = -1;
 };
 // A tracker HANDLE (what vc_tracker_create returns and every entry point takes) = slot | generation << 16: a handle kept past
 // vc_tracker_destroy never addresses the tracker that reuses its slot (the next video's), it is refused.  Inside the library
@@ -109,6 +111,7 @@ struct TrackStage {
     std::vector<int> dev_index;              // tasks[i] is the device's task dev_index[i]
     std::vector<std::pair<int, int>> tracker_dets;   // (tracker, detections enqueued) for the pending_dets bookkeeping
     std::vector<int> last_task_of;           // per entry of tracker_dets: device index of the tracker's last task
+    int* d_row_slot = nullptr; size_t row_slot_cap = 0;   // TrackBatchArgs::row_slot of this stage, allocated once a live counter is attached
 };
 
 // A validated vc_yuv_desc with the zeros resolved (yuv_ingest.hip: yuv_resolve); all byte quantities.  Shared by the ingest
@@ -289,6 +292,7 @@ struct vc_engine {
     float* d_nfeat = nullptr; float* d_det_ss = nullptr; size_t nfeat_cap = 0;
     float* d_feat_in = nullptr;                  // features handed in from the host (vc_tracker_step)
     int det_cap = 0;
+    std::vector<vc_live*> lives;                 // live counters (live_count.hip); vc_engine_destroy destroys what is left
 
     // ---- count all-gather (counting.hip): RCCL communicator of the engine's process group ----------------------
     void* comm = nullptr; int comm_rank = 0, comm_world = 1;
@@ -408,8 +412,16 @@ int tracker_init_pool(vc_engine* e);
 // (class label, tracker id, prepared detections) of frame f in class order.  Rows land in stage `st`; track_collect waits for them.
 struct FrameClassDets { int label, tracker; Prepared dets; };
 // frame_dims (a sized batch, else nullptr): the tasks of frame f clamp their rows to frame_dims[f] instead of W x H.
+// frame_tracker (else nullptr): per frame the slot of one tracker of the frame's camera -- a frame without tasks still advances the frame
+// number of its camera's live counter; without it the camera is that of the frame's first task.
 int track_enqueue(vc_engine* e, int st, const std::vector<std::vector<FrameClassDets>>& frames, const float* d_feat, int W, int H,
-                  int rows_cap, hipEvent_t wait, const vc_frame_dims* frame_dims = nullptr);
+                  int rows_cap, hipEvent_t wait, const vc_frame_dims* frame_dims = nullptr, const int* frame_tracker = nullptr);
+// live_count.hip: the counters that own one of batch_trackers (slots), ready for launch_track_batch; the next frame number of a tracker's
+// camera (0: not attached); what vc_engine_destroy calls.  counting.hip: the all-gather of a counter's device tensor.
+void live_batch_args(vc_engine* e, const std::vector<int>& batch_trackers, const long long* d_frame_no, std::vector<LiveCountArgs>& out);
+long long live_next_frame(vc_engine* e, int tracker_slot);
+void live_destroy_all(vc_engine* e);
+int live_allgather(vc_engine* e, const LiveCountArgs& a, int32_t* out);
 // rows6 per frame: out_rows6[f * cap_rows_per_frame * 6 ...], out_m[f]
 int track_collect(vc_engine* e, int st, int64_t* out_rows6, int cap_rows_per_frame, int* out_m);
 int track_idle(vc_engine* e);              // wait until no tracker batch is in flight (stream path included)

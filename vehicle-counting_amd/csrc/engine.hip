@@ -246,6 +246,8 @@ int vc_engine_destroy(vc_engine* e) {
     tune_cache_save(e);
     hipSetDevice(e->cfg.device);
     render_destroy_all(e);
+    if (e->stream) hipStreamSynchronize(e->stream);
+    live_destroy_all(e);
     vc_comm_destroy(e);
     if (e->stream) hipStreamSynchronize(e->stream);
     if (e->dstream) hipStreamSynchronize(e->dstream);

@@ -172,9 +172,41 @@ struct TrackBatchArgs {
     int lmat_doubles;                // dynamic LDS behind the step work arrays for the assignment's matrix (0: small_c / global scratch only)
     int no_reg;                      // diagnostics (VC_TRACK_NO_REG): steps of <= 64 x 64 take the LDS-list matching path as well
     long long* dbg;                  // diagnostics (VC_TRACK_DBG): per task 8 timestamps (100 MHz): start, predict, cost rows, match, apply, finish
+    int* row_slot;                   // [rows_cap] pool slot of the track behind every row of `rows`; null unless a live counter is attached (live_count.hip)
 };
 size_t track_scratch_per_wg();
-int launch_track_batch(const TrackBatchArgs& a, int n_wg, hipStream_t s);
+
+// ---- live per-camera counts beside the tracker (live_count.hip) -------------------------------------------------------------------
+// One live counter: its zones, the per-slot records of the tracks that can still produce rows, and the totals of those that cannot.
+namespace cc { struct LiveSlot; }                       // count_core.h (compiled with floating-point contraction off, like track_core.h)
+struct LiveCountArgs {
+    // the counter (device memory it owns)
+    const double* polygons;          // [n_cam][CC_MAX_POINTS][2]
+    const int* poly_n;               // [n_cam]
+    const double* dir_lines;         // [n_cam][CC_MAX_DIRS][4]
+    const int* n_dir;                // [n_cam]
+    int n_cam, n_labels, max_dir;
+    const int* owner;                // [n_trackers] camera of a tracker slot, -1 = not attached to this counter
+    int n_trackers;
+    cc::LiveSlot* slots;             // [max_tracks], indexed like TrackBatchArgs::recs
+    int max_tracks;
+    int* base;                       // [n_cam][max_dir][n_labels] tracks whose slot was freed
+    int* counts;                     // the same shape: base + the open slots (live_count_read_kernel)
+    int* stats;                      // [0] open slots at the last read, [1] slots folded into base so far
+    const long long* frame_no;       // [frames of the batch] 1-based frame number of the frame within its camera's stream
+    // the batch (filled by launch_track_batch from the tracker kernel's own arguments)
+    const TrackWgPlan* plans; int n_plans;
+    const TrackTask* tasks;
+    const long long* rows; const int* row_slot; const int* task_row_off; const int* task_row_n;
+    int rows_cap;                    // rows of `rows` / `row_slot`: a task whose range lies outside is skipped
+    const int* freed; const int* freed_count;
+};
+// steps 1 and 2 of a batch: rows in task order onto their slots, then every freed open slot into base.  One workgroup.
+int launch_live_count_apply(const LiveCountArgs& a, hipStream_t s);
+int launch_live_count_read(const LiveCountArgs& a, hipStream_t s);
+// live / n_live: the counters that own a tracker of this batch (their batch fields are filled here); their pass runs between the tracker
+// kernel and merge_free_kernel, which clears the freed list
+int launch_track_batch(const TrackBatchArgs& a, int n_wg, hipStream_t s, LiveCountArgs* live = nullptr, int n_live = 0);
 // test entry points: the batch kernel's own device functions on caller-supplied state
 int launch_kat_kalman(TrackPool& tp, int which /* 0 initiate, 1 predict, 2 update */, const double* z, int n, hipStream_t s);
 int launch_kat_lap(const double* cost, int nr, int nc, double* tbuf, int* out_rows, int* out_cols, int* out_n, hipStream_t s);

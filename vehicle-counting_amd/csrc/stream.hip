@@ -334,17 +334,20 @@ static int enqueue_batch_tracking(vc_engine* e, vc_engine::Pending& pd, const in
         if (!same) VC_TRY(reembed_unfiltered(e, pd));
     }
     std::vector<std::vector<FrameClassDets>> frames(b);
+    std::vector<int> cam_tracker(b);                                                  // one tracker of each frame's camera: its live counter counts the frame
     PrepScratch scratch;
     FramePrepared own;
     for (int f = 0; f < b; ++f) {
         const int* trackers = all_trackers + (size_t)(cam_of_frame ? cam_of_frame[f] : 0) * num_classes;
+        cam_tracker[f] = tracker_slot(e->trackers, trackers[0]);
         ndet[f] = (int)pd.fd[f].conf.size();                                         // a frame without boxes gives no task: Q1
         // filtered: prepared before the crops were cut (issue_reid); else here, box i of the frame on feature row row0[f] + i
         if (!pd.filtered) prepare_for_trackers(e, trackers, num_classes, pd.fd[f], pd.row0[f], scratch, own);
         VC_TRY(frame_tasks(e, trackers, num_classes, pd.filtered ? pd.prep[f] : own, frames[f]));
     }
     g_tm.lap(1);
-    VC_TRY(track_enqueue(e, stage, frames, e->d_feat2[pd.fslot], pd.w, pd.h, b * cap_rows_per_frame, e->ev_reid[pd.fslot], pd.dims.empty() ? nullptr : pd.dims.data()));
+    VC_TRY(track_enqueue(e, stage, frames, e->d_feat2[pd.fslot], pd.w, pd.h, b * cap_rows_per_frame, e->ev_reid[pd.fslot], pd.dims.empty() ? nullptr : pd.dims.data(),
+                         cam_tracker.data()));
     g_tm.lap(2);
     return VC_OK;
 }

@@ -659,6 +659,8 @@ __global__ __launch_bounds__(NW * 64) void track_batch_kernel(const TrackBatchAr
 #pragma unroll
                     for (int c = 0; c < 6; ++c) o[c] = row[c];
                 });
+                // live counting: the slot behind every row, so that a row finds its track without a search by id (ids repeat across trackers)
+                if (a.row_slot) compact(L, T, [&](int t) { return w.state[t] == CONFIRMED && w.tsu[t] <= 1; }, [&](int pos, int t) { a.row_slot[base + pos] = w.slot[t]; });
                 if (lane == 0) { a.task_row_n[task] = m; a.task_row_off[task] = base; }
             }
             if (lane == 0) { a.task_ntracks[task] = n; a.task_T[task] = T; }
@@ -686,8 +688,9 @@ __global__ __launch_bounds__(256) void merge_free_kernel(int* free_top, int* fre
 
 size_t track_scratch_per_wg() { return ((size_t)4 * TC_MAT * sizeof(double) + step_work_bytes(TC_HARD_CAP) + 255) & ~(size_t)255; }
 
-int launch_track_batch(const TrackBatchArgs& a, int n_wg, hipStream_t s) {
+int launch_track_batch(const TrackBatchArgs& a, int n_wg, hipStream_t s, LiveCountArgs* live, int n_live) {
     if (n_wg <= 0) return VC_OK;
+    VC_CHECK(n_live == 0 || (live && a.row_slot), VC_ERR_ARG, "a live counter needs the tracker kernel's row_slot output");
     const size_t lds = step_work_bytes(a.cap) + (size_t)a.lmat_doubles * sizeof(double);
     static const bool lds_ok = [] {                          // dynamic LDS beyond 64 KB (cap = 512) has to be allowed per kernel
         return hipFuncSetAttribute((const void*)track_batch_kernel<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, VC_TRACK_DYN_LDS) == hipSuccess &&
@@ -705,6 +708,13 @@ int launch_track_batch(const TrackBatchArgs& a, int n_wg, hipStream_t s) {
     if (a.all_tables) hipLaunchKernelGGL((track_batch_kernel<8, true>), dim3(n_wg), dim3(512), lds, s, a);
     else hipLaunchKernelGGL((track_batch_kernel<4, false>), dim3(n_wg), dim3(256), lds, s, a);
     VC_HIP(hipGetLastError());
+    for (int i = 0; i < n_live; ++i) {                      // before merge_free_kernel: it clears the freed list
+        LiveCountArgs& lc = live[i];
+        lc.plans = a.plans; lc.n_plans = n_wg; lc.tasks = a.tasks;
+        lc.rows = a.rows; lc.row_slot = a.row_slot; lc.task_row_off = a.task_row_off; lc.task_row_n = a.task_row_n; lc.rows_cap = a.rows_cap;
+        lc.freed = a.freed; lc.freed_count = a.freed_count;
+        VC_TRY(launch_live_count_apply(lc, s));
+    }
     hipLaunchKernelGGL(merge_free_kernel, dim3(1), dim3(256), 0, s, a.free_top, a.free_stack, a.freed_count, a.freed);
     VC_HIP(hipGetLastError());
     return VC_OK;

@@ -109,7 +109,7 @@ static OutLayout out_layout(int n_tasks, int rows_cap) {
 }
 
 int track_enqueue(vc_engine* e, int st, const std::vector<std::vector<FrameClassDets>>& frames, const float* d_feat, int W, int H,
-                  int rows_cap, hipEvent_t wait, const vc_frame_dims* frame_dims) {
+                  int rows_cap, hipEvent_t wait, const vc_frame_dims* frame_dims, const int* frame_tracker) {
     TrackStage& s = e->tstage[st];
     VC_CHECK(!s.busy, VC_ERR_STATE, "tracker staging slot %d is still in flight", st);
     // tasks in (frame, class) order -- the order rows are handed back in
@@ -123,7 +123,10 @@ int track_enqueue(vc_engine* e, int st, const std::vector<std::vector<FrameClass
         }
     const int n_tasks = (int)s.tasks.size();
     s.n_tasks = n_tasks; s.rows_cap = rows_cap; s.b = (int)frames.size(); s.W = W; s.H = H; s.n_wg = 0; s.n_dets = 0;
-    if (n_tasks == 0) { s.busy = true; VC_HIP(hipEventRecord(s.done, e->stream)); return VC_OK; }
+    if (n_tasks == 0) {                                      // nothing to step; the frames still count for their cameras' live counters
+        if (frame_tracker) for (size_t f = 0; f < frames.size(); ++f) (void)live_next_frame(e, frame_tracker[f]);
+        s.busy = true; VC_HIP(hipEventRecord(s.done, e->stream)); return VC_OK;
+    }
     // device order: grouped by tracker, frames ascending inside a group (stable sort of the frame-major list); the detection arrays
     // follow the same order, so every tracker's detections of the batch are one contiguous range
     std::vector<int> order(n_tasks);
@@ -180,6 +183,13 @@ int track_enqueue(vc_engine* e, int st, const std::vector<std::vector<FrameClass
     const size_t o_tlwh = p; p = align16(p + (size_t)n_dets * 32);
     const size_t o_xyah = p; p = align16(p + (size_t)n_dets * 32);
     const size_t o_frow = p; p = align16(p + (size_t)n_dets * 4);
+    // live counters (live_count.hip): does one own a tracker of this batch?  Then the batch carries its frames' numbers, and the kernel
+    // writes the slot behind every row
+    bool live = false;
+    for (const TrackWgPlan& pl : plans) live = live || e->trackers[pl.tracker]->live != nullptr;
+    if (frame_tracker) for (size_t f = 0; f < frames.size(); ++f) live = live || (tracker_ok(e->trackers, frame_tracker[f]) && e->trackers[frame_tracker[f]]->live);
+    const size_t o_fno = p;
+    if (live) p = align16(p + frames.size() * sizeof(long long));
     // The kernel reserves rows in chunks: a workgroup that needs m rows and has fewer left abandons the rest of its chunk and grabs
     // max(m, VC_ROW_CHUNK) fresh ones, so the rows it abandons are always fewer than the rows of the step that follows -- consumption
     // is bounded by twice the rows emitted plus one unfinished chunk per workgroup (`cap + chunk` was a spurious TERR_ROWS
@@ -188,6 +198,10 @@ int track_enqueue(vc_engine* e, int st, const std::vector<std::vector<FrameClass
     s.rows_cap = rows_cap;
     const OutLayout ol = out_layout(n_tasks, rows_cap);
     VC_TRY(stage_reserve(e, s, p, ol.total));
+    if (live && (size_t)rows_cap > s.row_slot_cap) {            // like the staging blocks: the old one stays allocated, a batch in flight may use it
+        s.row_slot_cap = (size_t)rows_cap * 3 / 2;
+        VC_TRY(dev_alloc(e, (void**)&s.d_row_slot, s.row_slot_cap * sizeof(int)));
+    }
     TrackTask* ht = (TrackTask*)(s.h_in + o_tasks);
     for (int k = 0; k < n_tasks; ++k) {
         const TrackTaskHost& t = s.tasks[order[k]];
@@ -241,6 +255,17 @@ int track_enqueue(vc_engine* e, int st, const std::vector<std::vector<FrameClass
         VC_TRY(dev_realloc(e, (void**)&e->d_dot_arena, want * sizeof(float)));
         e->dot_arena_floats = want;
     }
+    std::vector<LiveCountArgs> live_args;
+    if (live) {
+        // a frame belongs to the camera of frame_tracker[f] (else of its first task) and takes that camera's next number, 1-based and
+        // continuing across batches (modules/datasets.py:61); a frame of a camera without a counter gets 0, no row of it is read
+        long long* fno = (long long*)(s.h_in + o_fno);
+        for (size_t f = 0; f < frames.size(); ++f)
+            fno[f] = live_next_frame(e, frame_tracker ? frame_tracker[f] : frames[f].empty() ? -1 : frames[f][0].tracker);
+        std::vector<int> used;
+        for (const TrackWgPlan& pl : plans) used.push_back(pl.tracker);
+        live_batch_args(e, used, (const long long*)(s.d_in + o_fno), live_args);
+    }
     for (auto& td : s.tracker_dets) e->trackers[td.first]->pending_dets += td.second;
     hipStream_t ts = e->stream;
     if (wait) VC_HIP(hipStreamWaitEvent(ts, wait, 0));
@@ -264,6 +289,7 @@ int track_enqueue(vc_engine* e, int st, const std::vector<std::vector<FrameClass
     a.status = s.d_cursor + 4;                               // device memory (atomics), copied next to the rows below
     a.scratch = e->d_track_scratch; a.scratch_per_wg = track_scratch_per_wg(); a.cap = cap; a.frame_w = W; a.frame_h = H;
     a.all_tables = tables_fit ? 1 : 0;
+    a.row_slot = live ? s.d_row_slot : nullptr;
     // Dense steps (BASELINE.json configs[2]: ~90 tracks x ~70 detections): the matrix the assignment scans goes into LDS behind the work
     // arrays -- as much as the kernel's dynamic LDS allows; light batches ask for none (their problems fit the 2 KB static buffers, and
     // a small LDS footprint lets conv workgroups share the tracker's CUs).
@@ -280,7 +306,7 @@ int track_enqueue(vc_engine* e, int st, const std::vector<std::vector<FrameClass
     if (dbg_on && hipMalloc((void**)&dbg, (size_t)n_tasks * 128) == hipSuccess) { hipMemsetAsync(dbg, 0, (size_t)n_tasks * 128, ts); a.dbg = dbg; }
     {
         ProfScope ps(e, VC_PROF_TRACK);
-        VC_TRY(launch_track_batch(a, n_wg, ts));
+        VC_TRY(launch_track_batch(a, n_wg, ts, live_args.data(), (int)live_args.size()));
     }
     if (dbg) {
         std::vector<long long> h((size_t)n_tasks * 16);
@@ -414,7 +440,8 @@ int frame_track(vc_engine* e, const uint8_t* d_frame_base, int frame_index, int 
         VC_TRY(run_reid_dev(e, d_frame_base, H, W, k));
     }
     const int cap = std::max(total_tracks, 16);
-    VC_TRY(track_enqueue(e, 3, frames, e->d_feat, W, H, cap, nullptr));
+    const int cam_tracker = tracker_slot(e->trackers, trackers[0]);             // the frame counts for its camera's live counter even without a task
+    VC_TRY(track_enqueue(e, 3, frames, e->d_feat, W, H, cap, nullptr, nullptr, &cam_tracker));
     std::vector<int64_t> buf((size_t)cap * 6);
     int m = 0;
     VC_TRY(track_collect(e, 3, buf.data(), cap, &m));
@@ -496,6 +523,7 @@ int vc_tracker_create(vc_engine* e, const vc_tracker_params* p, int* id) {
 int vc_tracker_destroy(vc_engine* e, int handle) {
     const int id = e ? tracker_slot(e->trackers, handle) : -1;
     VC_CHECK(e && id >= 0, VC_ERR_NOTFOUND, "bad or stale tracker handle");
+    VC_CHECK(!e->trackers[id]->live, VC_ERR_STATE, "vc_tracker_destroy: the tracker is attached to a live counter (vc_live_destroy first)");
     VC_TRY(vc_tracker_reset(e, handle)); // waits for the batches in flight, returns the track slots to the pool
     e->trackers[id]->released = true;
     e->trackers[id]->gen = (e->trackers[id]->gen + 1) & 0x7fff;      // handles of this incarnation are refused from now on
@@ -505,6 +533,8 @@ int vc_tracker_destroy(vc_engine* e, int handle) {
 int vc_tracker_reset(vc_engine* e, int handle) {
     const int id = e ? tracker_slot(e->trackers, handle) : -1;
     VC_CHECK(e && id >= 0, VC_ERR_NOTFOUND, "bad or stale tracker handle");
+    // its tracks would leave the pool behind the counter's back: their slots are open there
+    VC_CHECK(!e->trackers[id]->live, VC_ERR_STATE, "vc_tracker_reset: the tracker is attached to a live counter (vc_live_destroy first)");
     VC_HIP(hipSetDevice(e->cfg.device));
     VC_TRY(async_wait_all(e));
     HostTrackerState st;
@@ -646,6 +676,7 @@ int vc_tracker_snapshot(vc_engine* e, int handle, void* buf, size_t cap, size_t*
 int vc_tracker_restore(vc_engine* e, int handle, const void* buf, size_t size) {
     const int id = e ? tracker_slot(e->trackers, handle) : -1;
     VC_CHECK(e && buf && id >= 0, VC_ERR_NOTFOUND, "bad or stale tracker handle");
+    VC_CHECK(!e->trackers[id]->live, VC_ERR_STATE, "vc_tracker_restore: the tracker is attached to a live counter (vc_live_destroy first)");
     VC_CHECK(size >= sizeof(SnapHeader), VC_ERR_ARG, "snapshot truncated");
     VC_HIP(hipSetDevice(e->cfg.device));
     VC_TRY(async_wait_all(e));

@@ -64,6 +64,8 @@ class Engine:
         if self._h:
             for r in list(getattr(self, "_renderers", ())):      # their contexts die with the engine: close them first
                 r.close()
+            for l in list(getattr(self, "_lives", ())):          # live counters too
+                l.close()
             L.lib().vc_engine_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -482,6 +484,106 @@ class Engine:
 
 
 # ---- single-function entry points (used by the parity tests) -------------------------------------------------------
+# one record of the live counter's per-slot state (csrc/count_core.h: cc::LiveSlot, 88 bytes)
+LIVE_SLOT_DTYPE = np.dtype([("open", np.int32), ("cam", np.int32), ("label", np.int32), ("at_last", np.int32), ("last_frame", np.int64),
+                            ("first", np.int64, 4), ("last", np.int64, 4)])
+
+
+def _live_zones(polygons, dir_lines):
+    """Per-camera polygons [(n, 2)] and direction lines [(d, 4)] -> the concatenated arrays and counts of vc_live_create."""
+    polys = [np.asarray(p, np.float64).reshape(-1, 2) for p in polygons]
+    dirs = [np.asarray(d, np.float64).reshape(-1, 4) for d in dir_lines]
+    if len(polys) != len(dirs) or not polys:
+        raise ValueError("one polygon and one list of direction lines per camera")
+    poly_n = np.array([len(p) for p in polys], np.int32)
+    n_dir = np.array([len(d) for d in dirs], np.int32)
+    return np.ascontiguousarray(np.concatenate(polys, 0)), poly_n, np.ascontiguousarray(np.concatenate(dirs, 0)), n_dir
+
+
+class LiveCounter:
+    """Running per-camera counts on the device (vc_live_*): attached to the engine's trackers tracker_ids [n_cam][n_labels], advanced by
+    every tracker launch that steps one of them.  `counts()` at any moment = `NativeCounter.counts()` of each camera over the rows of
+    all batches enqueued so far, as int32 (n_cam, max_dir, n_labels) -- rows d >= the camera's own number of directions are zero.
+    polygons: per camera (n, 2); dir_lines: per camera (n_dir, 4) = x0, y0, x1, y1 in the order of the zone file's direction shapes.
+    While it lives its trackers cannot be reset, destroyed or restored: `close()` first."""
+
+    def __init__(self, engine, tracker_ids, polygons, dir_lines):
+        tr = np.ascontiguousarray(tracker_ids, dtype=np.int32)
+        if tr.ndim != 2:
+            raise ValueError("tracker_ids must be [n_cam][n_labels]")
+        poly, poly_n, dirs, n_dir = _live_zones(polygons, dir_lines)
+        if len(poly_n) != tr.shape[0]:
+            raise ValueError(f"{tr.shape[0]} cameras of trackers, {len(poly_n)} zones")
+        self.engine, self.n_cam, self.n_labels, self.n_dir = engine, tr.shape[0], tr.shape[1], n_dir.copy()
+        self.max_dir = int(n_dir.max())
+        self._h = C.c_void_p()
+        L.check(L.lib().vc_live_create(engine._h, self.n_cam, self.n_labels, L.ptr(tr.reshape(-1), C.c_int), L.ptr(poly, C.c_double),
+                                       L.ptr(poly_n, C.c_int), L.ptr(dirs, C.c_double), L.ptr(n_dir, C.c_int), C.byref(self._h)))
+        engine._lives = getattr(engine, "_lives", [])
+        engine._lives.append(self)
+
+    @property
+    def shape(self):
+        return (self.n_cam, self.max_dir, self.n_labels)
+
+    def counts(self, with_frames=False):
+        """The counts after every batch enqueued so far (waits for them); with_frames: also the frames handed in per camera."""
+        out = np.zeros(self.shape, np.int32)
+        fd = np.zeros(self.n_cam, np.int64)
+        L.check(L.lib().vc_live_counts(self._h, L.ptr(out.reshape(-1), C.c_int), L.ptr(fd, C.c_int64)))
+        return (out, fd) if with_frames else out
+
+    def counts_dev(self):
+        """Device address of the same int32 tensor (valid until the engine's next tracker launch or live-counter call)."""
+        p = C.c_void_p()
+        L.check(L.lib().vc_live_counts_dev(self._h, C.byref(p)))
+        return p.value
+
+    def stats(self):
+        """(open_tracks, retired_tracks): tracks seen in their zone that can still produce rows / that were folded into the totals."""
+        a, b = C.c_int(), C.c_int()
+        L.check(L.lib().vc_live_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def allgather(self):
+        """The count tensors of all ranks, (world, n_cam, max_dir, n_labels) rank-major: ncclAllGather from the device tensor."""
+        from . import parallel
+        _, world = parallel.ensure_comm(self.engine)
+        out = np.zeros((world,) + self.shape, np.int32)
+        L.check(L.lib().vc_live_allgather(self.engine._h, self._h, L.ptr(out.reshape(-1), C.c_int)))
+        return out
+
+    def close(self):
+        if self._h and self.engine._h:
+            L.check(L.lib().vc_live_destroy(self._h))
+        self._h = None
+        if self in getattr(self.engine, "_lives", []):
+            self.engine._lives.remove(self)
+
+
+def live_count(polygons, dir_lines, n_labels, tracker_cam, rows6, row_slot, tasks5, frame_no, freed, slots, base, stats):
+    """vc_live_count_host: one launch of live_count_apply_kernel and live_count_read_kernel on host arrays.  slots (LIVE_SLOT_DTYPE
+    [max_tracks]), base (n_cam, max_dir, n_labels) and stats [2] are the state before the batch; returns (slots, base, stats, counts) after."""
+    poly, poly_n, dirs, n_dir = _live_zones(polygons, dir_lines)
+    n_cam, max_dir = len(poly_n), int(n_dir.max())
+    cam = np.ascontiguousarray(tracker_cam, dtype=np.int32).reshape(-1)
+    rows = np.ascontiguousarray(rows6, dtype=np.int64).reshape(-1, 6)
+    rs = np.ascontiguousarray(row_slot, dtype=np.int32).reshape(-1)
+    tk = np.ascontiguousarray(tasks5, dtype=np.int32).reshape(-1, 5)
+    fno = np.ascontiguousarray(frame_no, dtype=np.int64).reshape(-1)
+    fr = np.ascontiguousarray(freed, dtype=np.int32).reshape(-1)
+    slots = np.ascontiguousarray(slots, dtype=LIVE_SLOT_DTYPE).copy()
+    base = np.ascontiguousarray(base, dtype=np.int32).reshape(n_cam, max_dir, n_labels).copy()
+    stats = np.ascontiguousarray(stats, dtype=np.int32).reshape(2).copy()
+    counts = np.zeros_like(base)
+    assert len(rs) == len(rows)
+    L.check(L.lib().vc_live_count_host(n_cam, n_labels, L.ptr(poly, C.c_double), L.ptr(poly_n, C.c_int), L.ptr(dirs, C.c_double), L.ptr(n_dir, C.c_int),
+                                       len(cam), L.ptr(cam, C.c_int), len(slots), L.ptr(rows, C.c_int64), L.ptr(rs, C.c_int), len(rows),
+                                       L.ptr(tk, C.c_int), len(tk), L.ptr(fno, C.c_int64), len(fno), L.ptr(fr, C.c_int), len(fr),
+                                       C.c_void_p(slots.ctypes.data), L.ptr(base.reshape(-1), C.c_int), L.ptr(stats, C.c_int), L.ptr(counts.reshape(-1), C.c_int)))
+    return slots, base, stats, counts
+
+
 def conv2d(x_nhwc, w_oihw, bias, *, stride=1, pad=0, act=0, res=None, res_mode=0, precision="bf16"):
     x, w, b = L.f32(x_nhwc), L.f32(w_oihw), L.f32(bias)
     B, H, W, Ci = x.shape

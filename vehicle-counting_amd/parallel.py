@@ -96,6 +96,14 @@ def allgather_counts_native(engine, local_counts):
     return out.reshape((world * t.shape[0],) + t.shape[1:])
 
 
+def allgather_live_counts(live):
+    """The same collective for a live counter (`engine.LiveCounter`, or the `PipelineLive` of `CountingPipeline.open_live` while a run
+    has it attached): vc_live_allgather hands the counter's DEVICE tensor to ncclAllGather -- no local copy to the host and back.
+    Returns int32 (world * n_cam, max_dir, n_labels), rank-major; every rank's counter must have the same shape."""
+    out = live.allgather()
+    return out.reshape((-1,) + out.shape[2:])
+
+
 def share_tune_cache(engine, warm=None, src=0):
     """Rank `src` runs `warm()` (its conv autotune: one pass over every shape the run will use), exports the choices and broadcasts
     them; every other rank imports them BEFORE its own first launches.  N ranks then time the candidates once instead of N times, and

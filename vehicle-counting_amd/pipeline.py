@@ -150,6 +150,58 @@ class YuvFrameSink:
         return self.data[i]
 
 
+class PipelineLive:
+    """The live counter of a group of cameras, opened by `CountingPipeline.open_live` and handed to `run_stream` / `run_streams` as
+    `live=`: the call attaches it to the trackers it creates (`engine.LiveCounter`), calls `on_counts(batch_index, counts)` after every
+    collect -- counts int32 (n_cam, max_dir, n_labels) over the rows of batches 0..batch_index, the batches enqueued by then -- and
+    detaches it before the trackers are given back; `counts()` then keeps returning the final tensor.  `direction_keys[c]` names the
+    rows of camera c ('01', ...); rows past them are zero."""
+
+    def __init__(self, engine, cam_names, zone_paths, n_labels, on_counts=None):
+        from .counting import load_zone_anno
+        self.engine, self.cam_names, self.n_labels, self.on_counts = engine, list(cam_names), n_labels, on_counts
+        zones = [load_zone_anno(z) for z in zone_paths]
+        self.polygons = [np.asarray(p, np.float64).reshape(-1, 2) for p, _ in zones]
+        self.direction_keys = [list(d.keys()) for _, d in zones]
+        self.dir_lines = [np.asarray([d[k] for k in d], np.float64).reshape(-1, 4) for _, d in zones]
+        self.counter, self.last, self.last_stats = None, None, (0, 0)
+
+    def attach(self, tracker_ids):
+        from .engine import LiveCounter
+        if self.counter is not None:
+            raise RuntimeError("the live counter is attached already")
+        self.counter = LiveCounter(self.engine, tracker_ids, self.polygons, self.dir_lines)
+
+    def counts(self):
+        return self.counter.counts() if self.counter is not None else self.last
+
+    def stats(self):
+        return self.counter.stats() if self.counter is not None else self.last_stats
+
+    def allgather(self):
+        return self.counter.allgather()
+
+    def counts_of(self, cam):
+        """Camera `cam` (index or name) in the form `run_stream` returns its counts: {direction key: [per label]}."""
+        c = self.cam_names.index(cam) if isinstance(cam, str) else cam
+        t = self.counts()
+        return {k: t[c, i].tolist() for i, k in enumerate(self.direction_keys[c])}
+
+    def notify(self, batch_index):
+        if self.on_counts is not None:
+            self.on_counts(batch_index, self.counts())
+
+    def detach(self):
+        if self.counter is not None:
+            try:
+                self.last, self.last_stats = self.counter.counts(), self.counter.stats()
+            finally:
+                self.counter.close()
+                self.counter = None
+
+    close = detach
+
+
 class CountingPipeline:
     def __init__(self, args, config, cam_config, engine=None, class_names=None, synthetic=False, classes=None):
         """classes: the detector's class filter and label map (`Engine.set_class_map`: a list of class ids, labelled 0.. in list order,
@@ -196,6 +248,25 @@ class CountingPipeline:
             for t in trackers:
                 if t is not None:
                     t.close()
+
+    def open_live(self, cam_names, zone_paths, on_counts=None):
+        """A live counter for these cameras (one tracker per camera and label, as every driver creates them): hand it to `run_stream`
+        (one camera) or `run_streams` as `live=`.  Its counts after any batch are the counts the call would return for the video cut
+        there; nothing of the stream is kept for them."""
+        return PipelineLive(self.engine, cam_names, zone_paths, len(self.class_names), on_counts)
+
+    @contextlib.contextmanager
+    def _live(self, live, trackers):
+        """Attach `live` (or nothing) to these VideoTrackers for the length of a run; detached -- with its final counts kept -- before
+        `_video` gives the trackers back, which the engine refuses while a counter is attached."""
+        if live is None:
+            yield
+            return
+        live.attach(np.array([t.tracker_ids for t in trackers], np.int32))
+        try:
+            yield
+        finally:
+            live.detach()
 
     def _finish(self, counter, obj, cam_name):
         out = os.path.join(self.saved_path, cam_name + ".csv") if self.saved_path else None
@@ -281,7 +352,7 @@ class CountingPipeline:
                 collect()
         return self._finish(counter, obj, cam_name)
 
-    def run_stream(self, source, cam_name, zone_path, batch=16, asynchronous=False, host_frames=False):
+    def run_stream(self, source, cam_name, zone_path, batch=16, asynchronous=False, host_frames=False, live=None):
         """asynchronous=True: the tracker kernel of batch n runs on the engine's tracker stream while batch n+1 is submitted and
         embedded (`stream_run_async` / `stream_collect`); rows are identical, they arrive one batch later.
         host_frames=True: the frames stay in (pinned) host memory, as the reference's loader delivers them, and cross PCIe batch by
@@ -289,7 +360,8 @@ class CountingPipeline:
         batches of device memory; otherwise the whole clip is uploaded once.
         A `YuvFrameSource` takes the same modes: its frames (any of its formats) are converted to BGR on the device as they are staged
         (`stream_stage_yuv_host` from pinned YUV -- half the PCIe bytes of BGR for 8-bit 4:2:0, two thirds for i422, the same for p016 /
-        i010 / i444 -- or `stream_stage_yuv_dev` from the uploaded clip)."""
+        i010 / i444 -- or `stream_stage_yuv_dev` from the uploaded clip).
+        live (`open_live([cam_name], [zone_path])`): the running counts of this camera on the device, see PipelineLive."""
         import torch
         tracker, counter = self._stages(cam_name, source.video_info, zone_path)
         obj = {"frames": [], "tracks": [], "labels": [], "boxes": []}
@@ -319,7 +391,7 @@ class CountingPipeline:
             obj["labels"].extend(rows[:, 5].tolist())
             obj["boxes"].extend(list(rows[:, :4].copy()))
 
-        with self._video(tracker):
+        with self._video(tracker), self._live(live, [tracker]):
             for n in range(min(2, len(starts))):            # staging order = batch order (the engine hands its four host slots out round-robin)
                 stage(n)
             if starts:
@@ -336,9 +408,13 @@ class CountingPipeline:
                         record(starts[n - 1], *self.engine.stream_collect()[:2])
                 else:
                     record(f0, *self.engine.stream_run_packed(tracker.tracker_ids, ptr[n], b, h, w)[:2])
+                if live is not None and (n > 0 or not asynchronous):
+                    live.notify(n)                          # batches 0..n are enqueued: their rows are in the counts
                 ptr.pop(n - 1, None)
             if asynchronous and starts:
                 record(starts[-1], *self.engine.stream_collect()[:2])
+                if live is not None:
+                    live.notify(len(starts) - 1)
         return self._finish(counter, obj, cam_name)
 
     def visualizer(self, rows, zone_path):
@@ -392,7 +468,7 @@ class CountingPipeline:
                 rnd.collect()
         return sink
 
-    def run_streams(self, sources, cam_names, zone_paths, batch=16, host_frames=False, mixed_sizes=False):
+    def run_streams(self, sources, cam_names, zone_paths, batch=16, host_frames=False, mixed_sizes=False, live=None):
         """S videos at once on ONE engine (the reference runs them one after another, each with a new VideoTracker,
         modules/__init__.py:28-36): the frames of the cameras are interleaved round-robin into batches of `batch` frames, the
         detector and the ReID net see one batch, every camera's frames are stepped on that camera's own trackers
@@ -407,7 +483,8 @@ class CountingPipeline:
         mixed_sizes=True: the cameras may also differ in frame size, as long as every camera's own AutoShape network shape
         (`engine.autoshape_net_size`) is the same -- at size 640, 1920x1080, 1280x720, 640x360 and 320x180 all run at 384x640.  Each
         batch is a sized batch (`stream_stage_frames_sized`): one detector pass, and every camera still gets the result of running
-        alone.  Cameras whose network shapes differ are refused; run each group of equal shapes in a call of its own."""
+        alone.  Cameras whose network shapes differ are refused; run each group of equal shapes in a call of its own.
+        live (`open_live(cam_names, zone_paths)`): the running counts of all cameras on the device, see PipelineLive."""
         import torch
         S = len(sources)
         order = []                                                                       # (camera, frame) round-robin, exhausted cameras drop out
@@ -451,7 +528,7 @@ class CountingPipeline:
                 o["labels"].extend(rows[sel, 5].tolist())
                 o["boxes"].extend(list(rows[sel, :4].copy()))
 
-        with self._video(*[st[0] for st in stages]):
+        with self._video(*[st[0] for st in stages]), self._live(live, [st[0] for st in stages]):
             for n in range(min(2, len(starts))):            # staging order = batch order (four slots, round-robin)
                 stage(n)
             if starts:
@@ -465,8 +542,12 @@ class CountingPipeline:
                 run(n, tids, cams[f0:f0 + b])
                 if n > 0:
                     record(starts[n - 1], *self.engine.stream_collect()[:2])
+                    if live is not None:
+                        live.notify(n)                      # batches 0..n are enqueued: their rows are in the counts
             if starts:
                 record(starts[-1], *self.engine.stream_collect()[:2])
+                if live is not None:
+                    live.notify(len(starts) - 1)
         return [self._finish(st[1], o, n) for st, o, n in zip(stages, objs, cam_names)]
 
     def _frames_batches(self, sources, cam_names, host_frames, mixed_sizes, order, span):
