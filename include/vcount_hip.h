@@ -365,6 +365,46 @@ int vc_live_count_host(int n_cam, int n_labels, const double* polygons, const in
                        const int* tasks5, int n_tasks, const int64_t* frame_no, int n_frames, const int* freed, int n_freed,
                        void* slots88, int32_t* base, int32_t* stats2, int32_t* counts);
 
+/* ---- live overlay: the lists vc_overlay paints, built on the device per batch (csrc/live_overlay.hip) --------------------------------
+ * The picture of a stream that never ends: no CSV, no second pass.  The definition is overlay.py::LiveVisualizer; per
+ * frame, in order: the zone annotation; for every row with a box corner in the zone, in the order vc_stream_collect returns the rows,
+ * an arrow from the centre of its track's first in-zone box to its own centre and its box with "id: <id> || cls: <label>"; the count
+ * text as it stood BEFORE the batch (none before a camera's first frame); the camera's 1-based frame number.
+ *
+ * vc_live_overlay_enable: dir_keys = the cameras' direction names as numbers (a zone file's "direction01" -> 1; 0..99, drawn with two
+ * digits), n_dir[cam] per camera, concatenated.  max_batch (<= 1024) frames per batch and max_rows_per_frame rows size the arena of
+ * each of the `depth` (1..4) list buffers; more than 256 labels is VC_ERR_CAPACITY, a second call VC_ERR_STATE.  Without this call
+ * nothing below exists and every tracker launch is what it was: no extra kernel, copy or allocation.  From then on every UNIFORM
+ * tracker launch that advances the counter -- the stream path, vc_videotracker_run*, vc_deepsort_update, vc_tracker_step -- also
+ * builds its batch's lists into a free list buffer (two launches on the tracker stream behind the counter's); a sized batch
+ * (vc_stream_run_async_multi_sized) builds none.  If all `depth` buffers hold lists nobody has consumed, such a call is VC_ERR_STATE
+ * before anything of it is enqueued.  A frame that does not fit the arena owns nothing, nor do the frames after it: the call that
+ * looks next (vc_live_overlay_lists, or vc_render_collect of that batch) is VC_ERR_CAPACITY.  vc_live_destroy frees the overlay. */
+int vc_live_overlay_enable(vc_live* live, const int* dir_keys, int max_batch, int max_rows_per_frame, int depth);
+/* Waits for the OLDEST unconsumed batch, copies its lists to the host and consumes the buffer (tests, host consumers).  frame_first
+ * has room for cap_frames + 1 entries; *b frames and *n_prims primitives come back.  Nothing unconsumed, or the overlay not enabled:
+ * VC_ERR_STATE; too little room: VC_ERR_ARG, nothing consumed. */
+int vc_live_overlay_lists(vc_live* live, int32_t* prims12, int cap_prims, int32_t* frame_first, int cap_frames, int* b, int* n_prims);
+/* One launch of the two build kernels on host arrays (parity tests), like vc_live_count_host: zones and the batch as there, dir_keys
+ * as for vc_live_overlay_enable, slots88 the records AFTER the batch's apply launch, counts_before [n_cam][max_dir][n_labels] or NULL
+ * for "no text", cam_of_frame[b] the camera of every frame (-1: none, the frame owns nothing); a frame has one task per camera and
+ * label.  prims12 receives the WHOLE arena, cap_prims x 12 (what no frame owns keeps the byte 0xA5), frame_first b + 1 entries.  A
+ * frame that does not fit: VC_ERR_CAPACITY, the arrays are still written.  Everything written lies between guard blocks: a write
+ * outside is VC_ERR_HIP. */
+int vc_live_overlay_host(int n_cam, int n_labels, const double* polygons, const int* poly_n, const double* dir_lines, const int* n_dir,
+                         const int* dir_keys, int n_trackers, const int* tracker_cam, int max_tracks, const void* slots88,
+                         const int32_t* counts_before, const int64_t* rows6, const int* row_slot, int n_rows, const int* tasks5, int n_tasks,
+                         const int64_t* frame_no, const int* cam_of_frame, int b, int h, int w, int32_t* prims12, int cap_prims,
+                         int32_t* frame_first);
+/* The same arithmetic (csrc/overlay_build.h) compiled for the host: no HIP call.  prims12 beyond frame_first[b] is not touched. */
+int vc_overlay_build_host(int n_cam, int n_labels, const double* polygons, const int* poly_n, const double* dir_lines, const int* n_dir,
+                          const int* dir_keys, int n_trackers, const int* tracker_cam, int max_tracks, const void* slots88,
+                          const int32_t* counts_before, const int64_t* rows6, const int* row_slot, int n_rows, const int* tasks5, int n_tasks,
+                          const int64_t* frame_no, const int* cam_of_frame, int b, int h, int w, int32_t* prims12, int cap_prims,
+                          int32_t* frame_first);
+/* the 35-bit bitmap the builders draw character ch with (bit 5 * row + column; lower case as capitals, unknown as '?') */
+int vc_glyph_bits_host(int ch, uint64_t* bits);
+
 /* ---- visualisation egress (off the hot path) --------------------------------------------------------- */
 /* utilities/counting/utils.py:299-331 visualize_merged: draws the annotation overlay into b BGR u8 frames (h x w x 3) in device
  * memory.  prims12: n x 12 int32 [type, x0, y0, x1, y1, t, colour (B | G << 8 | R << 16), glyph bits lo, glyph bits hi, 0, 0, 0] with
@@ -412,6 +452,15 @@ int vc_render_submit(vc_render* r, const vc_render_src* src, int b, int h, int w
                      const vc_yuv_desc* out_desc, void* out, int out_is_dev);
 /* Blocks until the OLDEST outstanding batch is complete in its `out`; VC_ERR_STATE with nothing outstanding. */
 int vc_render_collect(vc_render* r);
+/* vc_render_submit with the lists taken IN DEVICE MEMORY from the counter's oldest unconsumed list buffer (vc_live_overlay_enable): the
+ * context's in-stream waits on the event recorded behind the build launches on the tracker stream -- no host wait, no list copy.  The
+ * counter and the context belong to one engine.  b, h, w must be that batch's own, else VC_ERR_ARG; nothing unconsumed (or, after a
+ * sized batch, no list of that batch) is VC_ERR_STATE; the other refusals are vc_render_submit's, and all leave the lists unconsumed.
+ * The list buffer counts as consumed when vc_render_collect has returned for this batch.  The source is any VC_SRC_* kind -- typically
+ * the decoder surfaces the batch came from, or the BGR slot vc_stream_stage_* returned for it: such a slot must not be restaged
+ * before the collect. */
+int vc_render_submit_live(vc_render* r, vc_live* live, const vc_render_src* src, int b, int h, int w, const vc_yuv_desc* out_desc, void* out,
+                          int out_is_dev);
 
 /* ---- multi-camera ingest: one batch from per-frame sources of mixed formats ------------------------------------------------------
  * A batch that interleaves S cameras has S decoders behind it: every frame has its own address and possibly its own pitch, format,

@@ -195,6 +195,12 @@ SIGNATURES = {
     "vc_live_stats": [_vp, _pi, _pi],
     "vc_live_allgather": [_vp, _vp, _pi],
     "vc_live_count_host": [_i, _i, _pd, _pi, _pd, _pi, _i, _pi, _i, _pl, _pi, _i, _pi, _i, _pl, _i, _pi, _i, _vp, _pi, _pi, _pi],
+    "vc_live_overlay_enable": [_vp, _pi, _i, _i, _i],
+    "vc_live_overlay_lists": [_vp, _pi, _i, _pi, _i, _pi, _pi],
+    "vc_live_overlay_host": [_i, _i, _pd, _pi, _pd, _pi, _pi, _i, _pi, _i, _vp, _pi, _pl, _pi, _i, _pi, _i, _pl, _pi, _i, _i, _i, _pi, _i, _pi],
+    "vc_overlay_build_host": [_i, _i, _pd, _pi, _pd, _pi, _pi, _i, _pi, _i, _vp, _pi, _pl, _pi, _i, _pi, _i, _pl, _pi, _i, _i, _i, _pi, _i, _pi],
+    "vc_glyph_bits_host": [_i, _P(C.c_uint64)],
+    "vc_render_submit_live": [_vp, _vp, _P(RenderSrc), _i, _i, _i, _P(YuvDesc), _vp, _i],
     "vc_overlay": [_vp, _vp, _i, _i, _i, _pi, _pi],
     "vc_profile_enable": [_vp, _i],
     "vc_profile_conv_busy": [_vp, _pd, _pd],

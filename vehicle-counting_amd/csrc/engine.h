@@ -331,6 +331,20 @@ struct vc_engine {
     int inject_b = 0, inject_n = 0;
 };
 
+// A live counter (live_count.hip) and, once vc_live_overlay_enable has run, its overlay list builder (live_overlay.hip)
+namespace vc { struct LiveOverlay; }
+struct vc_live {
+    vc_engine* e = nullptr;
+    int n_cam = 0, n_labels = 0, max_dir = 0;
+    std::vector<int> trackers;               // [n_cam * n_labels] tracker slots
+    std::vector<long long> frames_done;      // [n_cam] frames handed to the tracker so far
+    vc::LiveCountArgs dev{};                 // the counter part; the batch part is filled per launch
+    std::vector<void*> allocs;               // device memory of this counter
+    int32_t* h_out = nullptr;                // pinned: counts + stats
+    std::vector<int> n_dir;                  // [n_cam]
+    vc::LiveOverlay* ov = nullptr;           // null until vc_live_overlay_enable: then every uniform tracker launch builds its lists
+};
+
 namespace vc {
 // engine.hip
 int pack_and_upload(std::vector<void*>& allocs, ConvParam& p, int prec, float act_scale = 1.0f);   // p.w / p.b -> packed device weights, bias, fp8 scales
@@ -422,6 +436,23 @@ void live_batch_args(vc_engine* e, const std::vector<int>& batch_trackers, const
 long long live_next_frame(vc_engine* e, int tracker_slot);
 void live_destroy_all(vc_engine* e);
 int live_allgather(vc_engine* e, const LiveCountArgs& a, int32_t* out);
+// live_overlay.hip: the overlay lists a tracker launch builds for the counters whose overlay is enabled.
+//   live_overlay_room    what a run call asks first: VC_ERR_STATE if a counter of one of these tracker HANDLES has no free list buffer
+//   live_overlay_begin   in front of the batch's apply launch, before the batch's frames are numbered: the counters of the batch's frames
+//                        (frame_trk[f]: slot of a tracker of frame f's camera, -1 none) with an enabled overlay; enqueues their counts read
+//   live_overlay_finish  behind the apply launch: the build launches into a free list buffer, and the event behind them.  a: the tracker
+//                        launch's arguments, null for a batch without a task
+//   live_overlay_take    the oldest unconsumed lists in device memory for a render context (render.hip), released by live_overlay_release
+struct LiveOverlayPlan { vc_live* live; std::vector<int> text_cam; };
+int live_overlay_room(vc_engine* e, const int* tracker_handles, int n);
+int live_overlay_begin(vc_engine* e, const std::vector<int>& frame_trk, hipStream_t s, std::vector<LiveOverlayPlan>& plans);
+int live_overlay_finish(vc_engine* e, std::vector<LiveOverlayPlan>& plans, const std::vector<int>& frame_trk, const long long* frame_no,
+                        const TrackBatchArgs* a, int n_tasks, int b, int h, int w, hipStream_t s);
+int live_overlay_take(vc_live* l, int b, int h, int w, const void** d_prims, const int** d_first, hipEvent_t* built, int* token);
+int live_overlay_release(vc_live* l, int token);      // VC_ERR_CAPACITY if a frame of that batch did not fit its arena
+void live_overlay_free(vc_live* l);
+// render.hip: before a counter's lists are freed -- waits for the contexts that read them and drops their references
+void render_forget_live(vc_engine* e, vc_live* l);
 // rows6 per frame: out_rows6[f * cap_rows_per_frame * 6 ...], out_m[f]
 int track_collect(vc_engine* e, int st, int64_t* out_rows6, int cap_rows_per_frame, int* out_m);
 int track_idle(vc_engine* e);              // wait until no tracker batch is in flight (stream path included)

@@ -204,6 +204,33 @@ struct LiveCountArgs {
 // steps 1 and 2 of a batch: rows in task order onto their slots, then every freed open slot into base.  One workgroup.
 int launch_live_count_apply(const LiveCountArgs& a, hipStream_t s);
 int launch_live_count_read(const LiveCountArgs& a, hipStream_t s);
+// ---- live overlay lists beside the live counter (live_overlay.hip) ------------------------------------------------------------------
+// One batch's prims12 / frame_first lists (overlay.hip) built from what the tracker launch left in device memory.  The arithmetic is
+// overlay_build.h; the definition is overlay.py::LiveVisualizer.
+struct LiveOverlayArgs {
+    // the counter's zones, as LiveCountArgs holds them, and the names of its directions
+    const double* polygons; const int* poly_n; const double* dir_lines; const int* n_dir;
+    const int* dir_keys;             // [n_cam][CC_MAX_DIRS]
+    int n_cam, n_labels, max_dir;
+    const int* owner; int n_trackers;
+    const cc::LiveSlot* slots; int max_tracks;
+    const int* counts_before;        // [n_cam][max_dir][n_labels] as they stood before this batch; null = no count text
+    const int* text_cam;             // [n_cam] 0 = the camera had no frame before this batch (no text for it); null = every camera has text
+    // the batch
+    const TrackTask* tasks; int n_tasks;
+    const long long* rows; const int* row_slot; const int* task_row_off; const int* task_row_n; int rows_cap;
+    const long long* frame_no;       // [b] the camera's 1-based frame number
+    const int* cam_of_frame;         // [b] camera of the counter, -1 = none of its cameras (the frame's list stays empty)
+    int b, h, w;
+    // out
+    int* row_cnt;                    // [rows_cap] scratch: primitives of every row of a task that was visited, 0 = no corner in the zone
+    int* frame_cnt;                  // [b] primitives of every frame
+    int* prims; int cap_prims;       // [cap_prims][12] the arena
+    int* frame_first;                // [b + 1]
+    int* flags;                      // [0] set when a frame did not fit (it and every later frame own nothing)
+};
+// two launches: per frame the counts (live_overlay_count_kernel), then per frame the offsets and the primitives (live_overlay_build_kernel)
+int launch_live_overlay(const LiveOverlayArgs& a, hipStream_t s);
 // live / n_live: the counters that own a tracker of this batch (their batch fields are filled here); their pass runs between the tracker
 // kernel and merge_free_kernel, which clears the freed list
 int launch_track_batch(const TrackBatchArgs& a, int n_wg, hipStream_t s, LiveCountArgs* live = nullptr, int n_live = 0);

@@ -158,15 +158,7 @@ int live_pack_zones(int n_cam, const double* polygons, const int* poly_n, const 
 
 using namespace vc;
 
-struct vc_live {
-    vc_engine* e = nullptr;
-    int n_cam = 0, n_labels = 0, max_dir = 0;
-    std::vector<int> trackers;               // [n_cam * n_labels] tracker slots
-    std::vector<long long> frames_done;      // [n_cam] frames handed to the tracker so far
-    LiveCountArgs dev{};                     // the counter part; the batch part is filled per launch
-    std::vector<void*> allocs;               // device memory of this counter
-    int32_t* h_out = nullptr;                // pinned: counts + stats
-};
+// struct vc_live: engine.h (live_overlay.hip shares it)
 
 namespace vc {
 
@@ -192,6 +184,7 @@ long long live_next_frame(vc_engine* e, int tracker_slot_) {
 }
 
 static void live_free(vc_live* l) {
+    live_overlay_free(l);                                // waits for the render contexts that still read its lists
     for (void* p : l->allocs) (void)hipFree(p);
     if (l->h_out) (void)hipHostFree(l->h_out);
     delete l;
@@ -238,6 +231,7 @@ int vc_live_create(vc_engine* e, int n_cam, int n_labels, const int* trackers, c
     vc_live* l = new vc_live();
     l->e = e; l->n_cam = n_cam; l->n_labels = n_labels; l->max_dir = max_dir; l->trackers = slots;
     l->frames_done.assign(n_cam, 0);
+    l->n_dir.assign(n_dir, n_dir + n_cam);
     const int n = n_cam * max_dir * n_labels, T = e->cfg.max_tracks;
     std::vector<int> owner((size_t)e->max_trackers, -1);
     for (size_t i = 0; i < slots.size(); ++i) owner[slots[i]] = (int)(i / n_labels);

@@ -24,6 +24,7 @@ struct vc_render {
         char* h_lists = nullptr; char* d_lists = nullptr; size_t lists_bytes = 0;   // the batch's primitive lists: pinned copy made at submit, device copy
         hipEvent_t ev_in = nullptr, ev_done = nullptr;         // work buffer painted / output complete
         bool used = false;
+        vc_live* live = nullptr; int live_token = -1;          // vc_render_submit_live: the counter whose list buffer this batch reads until it is collected
     } set[4];
     unsigned seq = 0;                                          // batches submitted so far: batch n uses set n % depth
     std::deque<int> outstanding;                               // sets of the batches not yet collected, oldest first
@@ -64,6 +65,7 @@ int render_free(vc_render* r) {
     if (r->s_in) hipStreamSynchronize(r->s_in);
     if (r->s_out) hipStreamSynchronize(r->s_out);
     for (vc_render::Set& t : r->set) {
+        if (t.live) (void)live_overlay_release(t.live, t.live_token);     // a batch never collected: its list buffer is free again
         if (t.d_raw) hipFree(t.d_raw);
         if (t.d_bgr) hipFree(t.d_bgr);
         if (t.d_yuv) hipFree(t.d_yuv);
@@ -85,9 +87,23 @@ void render_destroy_all(vc_engine* e) {
     e->renders.clear();
 }
 
+void render_forget_live(vc_engine* e, vc_live* l) {
+    for (vc_render* r : e->renders)
+        for (vc_render::Set& t : r->set)
+            if (t.live == l) {
+                (void)hipStreamSynchronize(r->s_in);             // the overlay launch that reads the counter's lists
+                t.live = nullptr; t.live_token = -1;
+            }
+}
+
 }  // namespace vc
 
 using namespace vc;
+
+// vc_render_submit and vc_render_submit_live: the lists come from the host (copied here) or, with `live`, from the counter's oldest
+// unconsumed list buffer in device memory, behind the event recorded after its build launch
+static int render_submit(vc_render* r, const vc_render_src* src, int b, int h, int w, const int32_t* prims12, const int32_t* frame_first, vc_live* live,
+                         const vc_yuv_desc* out_desc, void* out, int out_is_dev);
 
 extern "C" {
 
@@ -123,6 +139,19 @@ int vc_render_destroy(vc_render* r) {
 
 int vc_render_submit(vc_render* r, const vc_render_src* src, int b, int h, int w, const int32_t* prims12, const int32_t* frame_first,
                      const vc_yuv_desc* out_desc, void* out, int out_is_dev) {
+    return render_submit(r, src, b, h, w, prims12, frame_first, nullptr, out_desc, out, out_is_dev);
+}
+
+int vc_render_submit_live(vc_render* r, vc_live* live, const vc_render_src* src, int b, int h, int w, const vc_yuv_desc* out_desc, void* out, int out_is_dev) {
+    VC_CHECK(r && live, VC_ERR_ARG, "null argument");
+    VC_CHECK(live->e == r->e, VC_ERR_ARG, "the counter and the render context belong to different engines");
+    return render_submit(r, src, b, h, w, nullptr, nullptr, live, out_desc, out, out_is_dev);
+}
+
+}  // extern "C"
+
+static int render_submit(vc_render* r, const vc_render_src* src, int b, int h, int w, const int32_t* prims12, const int32_t* frame_first, vc_live* live,
+                         const vc_yuv_desc* out_desc, void* out, int out_is_dev) {
     // ---- every refusal comes before anything is enqueued ----
     VC_CHECK(r && src && src->data && out_desc && out, VC_ERR_ARG, "null argument");
     VC_CHECK(src->kind >= VC_SRC_BGR_HOST && src->kind <= VC_SRC_YUV_DEV, VC_ERR_ARG, "unknown source kind %d (VC_SRC_*)", src->kind);
@@ -155,6 +184,11 @@ int vc_render_submit(vc_render* r, const vc_render_src* src, int b, int h, int w
         t.lists_bytes = lists_bytes * 2;
     }
 
+    // the counter's oldest unconsumed lists (the last refusal: nothing unconsumed VC_ERR_STATE, another batch's b / h / w VC_ERR_ARG)
+    const void* live_prims = nullptr; const int* live_first = nullptr; hipEvent_t live_built = nullptr; int live_token = -1;
+    if (live) VC_TRY(live_overlay_take(live, b, h, w, &live_prims, &live_first, &live_built, &live_token));
+    t.live = live; t.live_token = live_token;
+
     // ---- in: source -> work buffer, overlay ----
     if (t.used) VC_HIP(hipStreamWaitEvent(r->s_in, t.ev_done, 0));      // behind the batch that last used this set (`out` is behind it by stream order)
     switch (src->kind) {
@@ -172,6 +206,10 @@ int vc_render_submit(vc_render* r, const vc_render_src* src, int b, int h, int w
         VC_HIP(hipMemcpyAsync(t.d_lists, t.h_lists, lists_bytes, hipMemcpyHostToDevice, r->s_in));
         VC_TRY(launch_overlay(t.d_bgr, b, h, w, t.d_lists, (const int*)(t.d_lists + prim_bytes), r->s_in));
     }
+    if (live) {                                              // no host wait, no list copy: the lists are read where the build kernel wrote them
+        VC_HIP(hipStreamWaitEvent(r->s_in, live_built, 0));
+        VC_TRY(launch_overlay(t.d_bgr, b, h, w, live_prims, live_first, r->s_in));
+    }
     VC_HIP(hipEventRecord(t.ev_in, r->s_in));
     // ---- out: work buffer -> YUV -> the caller's surface ----
     VC_HIP(hipStreamWaitEvent(r->s_out, t.ev_in, 0));
@@ -188,12 +226,21 @@ int vc_render_submit(vc_render* r, const vc_render_src* src, int b, int h, int w
     return VC_OK;
 }
 
+extern "C" {
+
 int vc_render_collect(vc_render* r) {
     VC_CHECK(r, VC_ERR_ARG, "null argument");
     VC_CHECK(!r->outstanding.empty(), VC_ERR_STATE, "vc_render_collect: no batch is outstanding");
     const int si = r->outstanding.front();
     r->outstanding.pop_front();
-    VC_HIP(hipEventSynchronize(r->set[si].ev_done));
+    vc_render::Set& t = r->set[si];
+    VC_HIP(hipEventSynchronize(t.ev_done));
+    if (t.live) {                                            // the counter's list buffer counts as consumed from here on
+        vc_live* l = t.live;
+        const int token = t.live_token;
+        t.live = nullptr; t.live_token = -1;
+        VC_TRY(live_overlay_release(l, token));
+    }
     return VC_OK;
 }
 

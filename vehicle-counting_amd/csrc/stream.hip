@@ -402,6 +402,7 @@ static int run_async_batch(vc_engine* e, const int* trackers, int n_cam, int num
     VC_CHECK(e->finalized && e->cfg.with_detector && e->cfg.with_reid, VC_ERR_STATE, "engine not finalized");
     VC_HIP(hipSetDevice(e->cfg.device));
     VC_CHECK(e->jobs.size() < 2, VC_ERR_STATE, "two asynchronous batches are already outstanding: call vc_stream_collect");
+    if (!dims && !e->lives.empty()) VC_TRY(live_overlay_room(e, trackers, n_cam * num_classes));   // a uniform batch builds overlay lists: refused before anything is enqueued
     {
         // the filter of THIS call's trackers: take_front embeds under it when it issues the ReID itself (first batch of a stream), and
         // the look-ahead of the following batches remembers it; valid only if every tracker handed in agrees on both parameters
@@ -515,6 +516,7 @@ int vc_stream_embed(vc_engine* e, const void* frames_dev, int b, int h, int w, d
 int vc_videotracker_run_features(vc_engine* e, const int* trackers, int num_classes, const double* rows7, const float* feat_dev, int n, int h, int w,
                                  int64_t* out_rows6, int cap_rows_per_frame, int* out_m, int64_t* out_keys, int cap_frames, int* out_n_frames) {
     VC_CHECK(e && trackers && out_rows6 && out_m && out_keys && out_n_frames && (n == 0 || (rows7 && feat_dev)) && n >= 0, VC_ERR_ARG, "bad argument");
+    if (!e->lives.empty()) VC_TRY(live_overlay_room(e, trackers, num_classes));
     VC_HIP(hipSetDevice(e->cfg.device));
     VC_TRY(async_wait_all(e));
     std::vector<std::vector<FrameClassDets>> frames;

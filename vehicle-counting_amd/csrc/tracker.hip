@@ -123,8 +123,22 @@ int track_enqueue(vc_engine* e, int st, const std::vector<std::vector<FrameClass
         }
     const int n_tasks = (int)s.tasks.size();
     s.n_tasks = n_tasks; s.rows_cap = rows_cap; s.b = (int)frames.size(); s.W = W; s.H = H; s.n_wg = 0; s.n_dets = 0;
+    // Overlay lists (live_overlay.hip): the counters of this batch's cameras whose overlay is enabled -- none unless vc_live_overlay_enable
+    // has run, and then the launch below is exactly what it was.  Lists are built for uniform batches only.
+    std::vector<LiveOverlayPlan> ov;
+    std::vector<int> frame_trk;
+    if (!frame_dims && !e->lives.empty()) {
+        frame_trk.resize(frames.size());
+        for (size_t f = 0; f < frames.size(); ++f) frame_trk[f] = frame_tracker ? frame_tracker[f] : frames[f].empty() ? -1 : frames[f][0].tracker;
+        VC_TRY(live_overlay_begin(e, frame_trk, e->stream, ov));
+    }
     if (n_tasks == 0) {                                      // nothing to step; the frames still count for their cameras' live counters
-        if (frame_tracker) for (size_t f = 0; f < frames.size(); ++f) (void)live_next_frame(e, frame_tracker[f]);
+        std::vector<long long> fno(frames.size(), 0);
+        if (frame_tracker) for (size_t f = 0; f < frames.size(); ++f) fno[f] = live_next_frame(e, frame_tracker[f]);
+        if (!ov.empty()) {                                   // anno, text and frame number
+            ProfScope ps(e, VC_PROF_TRACK);
+            VC_TRY(live_overlay_finish(e, ov, frame_trk, fno.data(), nullptr, 0, (int)frames.size(), H, W, e->stream));
+        }
         s.busy = true; VC_HIP(hipEventRecord(s.done, e->stream)); return VC_OK;
     }
     // device order: grouped by tracker, frames ascending inside a group (stable sort of the frame-major list); the detection arrays
@@ -307,6 +321,11 @@ int track_enqueue(vc_engine* e, int st, const std::vector<std::vector<FrameClass
     {
         ProfScope ps(e, VC_PROF_TRACK);
         VC_TRY(launch_track_batch(a, n_wg, ts, live_args.data(), (int)live_args.size()));
+    }
+    // behind the apply launch and in front of s.done: the build reads this stage's tasks and rows, which the stage's next batch overwrites
+    if (!ov.empty()) {
+        ProfScope ps(e, VC_PROF_TRACK);                          // a launch of its own in the profile: a counter without the overlay shows none
+        VC_TRY(live_overlay_finish(e, ov, frame_trk, (const long long*)(s.h_in + o_fno), &a, n_tasks, (int)frames.size(), H, W, ts));
     }
     if (dbg) {
         std::vector<long long> h((size_t)n_tasks * 16);
@@ -552,6 +571,7 @@ int vc_tracker_step(vc_engine* e, int handle, const double* tlwh, const double* 
     VC_CHECK(e && id >= 0, VC_ERR_NOTFOUND, "bad or stale tracker handle");
     VC_CHECK(k == 0 || (tlwh && conf && feat), VC_ERR_ARG, "null argument");
     VC_CHECK(k >= 0 && k <= e->det_cap, VC_ERR_CAPACITY, "%d detections exceed capacity %d", k, e->det_cap);
+    if (!e->lives.empty()) VC_TRY(live_overlay_room(e, &handle, 1));
     VC_HIP(hipSetDevice(e->cfg.device));
     VC_TRY(async_wait_all(e));
     if (k > 0) VC_HIP(hipMemcpyAsync(e->d_feat_in, feat, (size_t)k * VC_FEAT_DIM * sizeof(float), hipMemcpyHostToDevice, e->stream));
@@ -735,6 +755,7 @@ int vc_deepsort_update(vc_engine* e, int id, const uint8_t* bgr, int h, int w, c
                        int64_t* out_rows7, int cap_rows, int* out_m) {
     VC_CHECK(e && bgr && out_m && tracker_slot(e->trackers, id) >= 0, VC_ERR_ARG, "bad argument (null pointer, bad or stale tracker handle)");
     VC_CHECK(k >= 1 && bbox_xyxy && conf, VC_ERR_ARG, "DeepSort.update needs at least one box (the reference only calls it then)");
+    if (!e->lives.empty()) VC_TRY(live_overlay_room(e, &id, 1));
     VC_HIP(hipSetDevice(e->cfg.device));
     VC_TRY(async_wait_all(e));
     const size_t bytes = (size_t)h * w * 3;
@@ -759,6 +780,7 @@ int vc_videotracker_run(vc_engine* e, const int* trackers, int num_classes, cons
                         const int64_t* labels, const double* scores, int n, int64_t* out_rows6, int cap_rows, int* out_m) {
     VC_CHECK(e && trackers && bgr && out_m, VC_ERR_ARG, "null argument");
     VC_CHECK(n >= 1 && boxes_xywh && labels && scores, VC_ERR_ARG, "VideoTracker.run needs at least one box (quirk Q1)");
+    if (!e->lives.empty()) VC_TRY(live_overlay_room(e, trackers, num_classes));
     VC_HIP(hipSetDevice(e->cfg.device));
     VC_TRY(async_wait_all(e));
     const size_t bytes = (size_t)h * w * 3;

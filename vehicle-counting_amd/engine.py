@@ -553,6 +553,27 @@ class LiveCounter:
         L.check(L.lib().vc_live_allgather(self.engine._h, self._h, L.ptr(out.reshape(-1), C.c_int)))
         return out
 
+    def enable_overlay(self, dir_keys, max_batch, max_rows_per_frame=64, depth=2):
+        """From now on every uniform tracker launch that advances the counter also builds its batch's overlay lists on the device
+        (vc_live_overlay_enable; the definition is overlay.LiveVisualizer).  dir_keys: per camera the names of its directions in the
+        order of dir_lines, as the zone file spells them ("01") or as numbers.  depth: list buffers (1..4) -- a run call with all of
+        them unconsumed raises VcError (VC_ERR_STATE)."""
+        keys = [int(k) for cam in dir_keys for k in cam]
+        if [len(cam) for cam in dir_keys] != self.n_dir.tolist():
+            raise ValueError(f"direction keys per camera {[len(c) for c in dir_keys]}, direction lines {self.n_dir.tolist()}")
+        k = np.array(keys, np.int32)
+        L.check(L.lib().vc_live_overlay_enable(self._h, L.ptr(k, C.c_int), int(max_batch), int(max_rows_per_frame), int(depth)))
+        self.overlay_depth, self._ov_cap = int(depth), None
+
+    def overlay_lists(self, cap_prims=1 << 16, cap_frames=1024):
+        """(prims12 (n, 12) int32, frame_first (b + 1) int32) of the OLDEST unconsumed batch, copied to the host (waits for it); the
+        list buffer is consumed.  For tests and host consumers: the render path takes the lists on the device (Renderer.submit_live)."""
+        prims = np.zeros((cap_prims, 12), np.int32)
+        first = np.zeros(cap_frames + 1, np.int32)
+        b, n = C.c_int(), C.c_int()
+        L.check(L.lib().vc_live_overlay_lists(self._h, L.ptr(prims.reshape(-1), C.c_int), cap_prims, L.ptr(first, C.c_int), cap_frames, C.byref(b), C.byref(n)))
+        return prims[:n.value].copy(), first[:b.value + 1].copy()
+
     def close(self):
         if self._h and self.engine._h:
             L.check(L.lib().vc_live_destroy(self._h))
@@ -582,6 +603,41 @@ def live_count(polygons, dir_lines, n_labels, tracker_cam, rows6, row_slot, task
                                        L.ptr(tk, C.c_int), len(tk), L.ptr(fno, C.c_int64), len(fno), L.ptr(fr, C.c_int), len(fr),
                                        C.c_void_p(slots.ctypes.data), L.ptr(base.reshape(-1), C.c_int), L.ptr(stats, C.c_int), L.ptr(counts.reshape(-1), C.c_int)))
     return slots, base, stats, counts
+
+
+OVERLAY_UNWRITTEN = np.frombuffer(b"\xa5" * 4, np.int32)[0]          # what an arena word no frame owns holds after vc_live_overlay_host
+
+
+def live_overlay(polygons, dir_lines, dir_keys, n_labels, tracker_cam, slots, counts_before, rows6, row_slot, tasks5, frame_no, cam_of_frame, hw,
+                 cap_prims, *, host=False, allow_overflow=False):
+    """vc_live_overlay_host: one launch of the two overlay build kernels on host arrays (host=True: vc_overlay_build_host, the same
+    arithmetic on the CPU, no GPU needed).  slots: LIVE_SLOT_DTYPE records AFTER the batch's apply launch; counts_before
+    (n_cam, max_dir, n_labels) or None for "no text".  Returns (arena (cap_prims, 12) int32, frame_first (b + 1) int32, overflow): frame
+    f owns arena[frame_first[f]:frame_first[f + 1]].  A frame that does not fit raises VcError (VC_ERR_CAPACITY) unless allow_overflow."""
+    poly, poly_n, dirs, n_dir = _live_zones(polygons, dir_lines)
+    n_cam, max_dir = len(poly_n), int(n_dir.max())
+    keys = np.array([int(k) for cam in dir_keys for k in cam], np.int32)
+    assert [len(c) for c in dir_keys] == n_dir.tolist()
+    cam = np.ascontiguousarray(tracker_cam, dtype=np.int32).reshape(-1)
+    rows = np.ascontiguousarray(rows6, dtype=np.int64).reshape(-1, 6)
+    rs = np.ascontiguousarray(row_slot, dtype=np.int32).reshape(-1)
+    tk = np.ascontiguousarray(tasks5, dtype=np.int32).reshape(-1, 5)
+    fno = np.ascontiguousarray(frame_no, dtype=np.int64).reshape(-1)
+    cof = np.ascontiguousarray(cam_of_frame, dtype=np.int32).reshape(-1)
+    slots = np.ascontiguousarray(slots, dtype=LIVE_SLOT_DTYPE)
+    cb = None if counts_before is None else np.ascontiguousarray(counts_before, dtype=np.int32).reshape(n_cam, max_dir, n_labels)
+    assert len(rs) == len(rows) and len(cof) == len(fno)
+    arena = np.full((cap_prims, 12), OVERLAY_UNWRITTEN, np.int32)
+    first = np.zeros(len(fno) + 1, np.int32)
+    fn = L.lib().vc_overlay_build_host if host else L.lib().vc_live_overlay_host
+    rc = fn(n_cam, n_labels, L.ptr(poly, C.c_double), L.ptr(poly_n, C.c_int), L.ptr(dirs, C.c_double), L.ptr(n_dir, C.c_int), L.ptr(keys, C.c_int),
+            len(cam), L.ptr(cam, C.c_int), len(slots), C.c_void_p(slots.ctypes.data), L.ptr(None if cb is None else cb.reshape(-1), C.c_int),
+            L.ptr(rows, C.c_int64), L.ptr(rs, C.c_int), len(rows), L.ptr(tk, C.c_int), len(tk), L.ptr(fno, C.c_int64), L.ptr(cof, C.c_int), len(fno),
+            int(hw[0]), int(hw[1]), L.ptr(arena.reshape(-1), C.c_int), cap_prims, L.ptr(first, C.c_int))
+    overflow = rc == 4                                      # VC_ERR_CAPACITY
+    if not (allow_overflow and overflow):
+        L.check(rc)
+    return arena, first, overflow
 
 
 def conv2d(x_nhwc, w_oihw, bias, *, stride=1, pad=0, act=0, res=None, res_mode=0, precision="bf16"):
@@ -1106,11 +1162,24 @@ class Renderer:
                                          1 if out_is_dev else 0))
         self._alive.append((sk, ok))
 
+    def submit_live(self, live, src, b, h, w, out, *, kind="bgr_host", src_desc=None, out_desc=None, out_is_dev=False):
+        """`submit` with the overlay lists taken in device memory from `live` (a LiveCounter after enable_overlay): its oldest
+        unconsumed batch, which must be this one (b, h, w).  No list crosses to the host; the list buffer is free again when
+        `collect` has returned for this batch.  A BGR slot of the stream path given as `src` must not be restaged before that."""
+        sa, sk = self._addr(src)
+        oa, ok = self._addr(out)
+        rs = L.RenderSrc(L.RENDER_SRC_ID[kind], sa, src_desc if src_desc is not None else yuv_desc())
+        od = out_desc if out_desc is not None else yuv_desc()
+        L.check(L.lib().vc_render_submit_live(self._h, live._h, C.byref(rs), b, h, w, C.byref(od), C.c_void_p(oa), 1 if out_is_dev else 0))
+        self._alive.append((sk, ok))
+
     def collect(self):
         """Block until the oldest outstanding batch is complete in its destination."""
-        L.check(L.lib().vc_render_collect(self._h))
-        if self._alive:
-            self._alive.pop(0)
+        try:
+            L.check(L.lib().vc_render_collect(self._h))
+        finally:                                           # the batch has left the context even where the call reports its overlay's overflow
+            if self._alive:
+                self._alive.pop(0)
 
     @property
     def outstanding(self):

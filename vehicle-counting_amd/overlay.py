@@ -222,6 +222,110 @@ class MergedVisualizer:
         overlay(engine, frames_dev_ptr, len(frame_ids), h, w, prims, first)
 
 
+def pack_prims(lists):
+    """PrimLists of a batch's frames -> (prims12 int32 (n, 12), frame_first int32 (b + 1)), the arrays vc_overlay takes."""
+    first = np.zeros(len(lists) + 1, np.int32)
+    for i, pl in enumerate(lists):
+        first[i + 1] = first[i] + len(pl.rows)
+    prims = np.array([r for pl in lists for r in pl.rows], dtype=np.int64).astype(np.uint32).view(np.int32).reshape(-1, 12) if first[-1] else np.zeros((0, 12), np.int32)
+    return np.ascontiguousarray(prims), first
+
+
+def count_text(counts):
+    """count_frame_directions' text for counts {int(direction key): {label: n}}: one line per direction, every label listed."""
+    _, text = count_frame_directions([], counts)
+    return text
+
+
+def live_frame(hw, zone, directions, rows, firsts, text_before, frame_no):
+    """The live overlay of ONE frame, stateless: rows = the frame's rows (x1, y1, x2, y2, track id, label) in emit
+    order, firsts[i] = the first in-zone box of row i's track (this row included; not read for a row without a corner in the zone),
+    text_before = the count text before the batch or None, frame_no = the camera's 1-based frame number."""
+    from . import counting as pc
+    h, w = hw
+    pl = PrimList()
+    pl.draw_anno(zone, directions)
+    for r, f in zip(rows, firsts):
+        box, tid, label = [int(v) for v in r[:4]], int(r[4]), int(r[5])
+        if not pc.check_bbox_intersect_polygon(zone, box):
+            continue
+        fpoint = (int((f[0] + f[2]) / 2), int((f[1] + f[3]) / 2))
+        cpoint = (int((box[0] + box[2]) / 2), int((box[1] + box[3]) / 2))
+        color = track_color(label, tid)
+        pl.draw_arrow(fpoint, cpoint, color)
+        pl.draw_one_box((h, w), box, f"id: {tid}", f"cls: {label}", color)
+    if text_before is not None:
+        pl.draw_text(h, text_before)
+    pl.draw_frame_count(h, int(frame_no))
+    return pl
+
+
+class LiveVisualizer:
+    """The overlay of a stream that never ends: what can be drawn on a frame when the tracker launch of its batch has
+    run, with no CSV and no second pass.  This class, with live_frame above, is the DEFINITION; csrc/overlay_build.h restates it and
+    live_overlay.hip builds the same lists on the device.
+
+    Per camera: the zone polygon, the {direction key: line} dict (keys as load_zone_anno gives them, two digits), the first in-zone
+    box of every (label, track id) seen so far, and the counter state of counting.py's rule fed the in-zone rows so far.  Two stated
+    differences from MergedVisualizer: rows are painted in emit order, not CSV order; the count text is that of the video CUT at the
+    end of the previous batch (tracks still open count where they stand), not the full video's `lframe` hindsight."""
+
+    def __init__(self, zones, directions, num_classes):
+        if len(zones) != len(directions):
+            raise ValueError("one zone polygon and one direction dict per camera")
+        for d in directions:
+            for k in d:
+                if "%02d" % int(k) != str(k):
+                    raise ValueError(f"direction key {k!r}: the live overlay draws keys as two digits, as load_zone_anno names them")
+        self.zones, self.directions, self.num_classes = [list(z) for z in zones], [dict(d) for d in directions], int(num_classes)
+        self.tracks = [{} for _ in zones]           # per camera (label, track id) -> [first box, last box, last frame, rows at the last frame]
+        self.seen = [False] * len(zones)            # a frame of the camera has been handed to the tracker
+
+    def first_box(self, cam, label, track_id):
+        return self.tracks[cam][int(label), int(track_id)][0]
+
+    def counts(self, cam):
+        """{int(key): {label: n}} of the video cut here: every track counts rows-at-its-last-frame times in its direction"""
+        from . import counting as pc
+        out = {int(k): {label: 0 for label in range(self.num_classes)} for k in self.directions[cam]}
+        for (label, _), (f, l, _, at_last) in self.tracks[cam].items():
+            vec = (((f[2] + f[0]) / 2, (f[3] + f[1]) / 2), ((l[2] + l[0]) / 2, (l[3] + l[1]) / 2))
+            out[int(pc.find_best_match_direction(vec, self.directions[cam]))][label] += at_last
+        return out
+
+    def text(self, cam):
+        """count_frame_directions' text on counts(cam); None before the camera's first frame (the reference's prev_text = None)"""
+        return count_text(self.counts(cam)) if self.seen[cam] else None
+
+    def batch_lists(self, cams, frame_nos, rows, hw):
+        """One batch: cams[f] / frame_nos[f] (1-based within the camera) / rows[f] = the frame's rows (x1, y1, x2, y2, track id, label)
+        in the order vc_stream_collect returns them.  Returns the frames' PrimLists and advances the state."""
+        from . import counting as pc
+        text_before = [self.text(c) for c in range(len(self.zones))]
+        lists = []
+        for cam, frame_no, frame_rows in zip(cams, frame_nos, rows):
+            cam, frame_no = int(cam), int(frame_no)
+            firsts = []
+            for r in frame_rows:
+                box, tid, label = [int(v) for v in r[:4]], int(r[4]), int(r[5])
+                if not pc.check_bbox_intersect_polygon(self.zones[cam], box):
+                    firsts.append(box)                       # not read
+                    continue
+                rec = self.tracks[cam].get((label, tid))
+                if rec is None:
+                    rec = self.tracks[cam][label, tid] = [box, box, frame_no, 1]
+                else:
+                    rec[3] = rec[3] + 1 if rec[2] == frame_no else 1
+                    rec[1], rec[2] = box, frame_no
+                firsts.append(rec[0])
+            lists.append(live_frame(hw, self.zones[cam], self.directions[cam], frame_rows, firsts, text_before[cam], frame_no))
+            self.seen[cam] = True
+        return lists
+
+    def batch_prims(self, cams, frame_nos, rows, hw):
+        return pack_prims(self.batch_lists(cams, frame_nos, rows, hw))
+
+
 def overlay(engine, frames_dev_ptr, b, h, w, prims, first):
     prims = np.ascontiguousarray(prims, dtype=np.int32)
     first = np.ascontiguousarray(first, dtype=np.int32)

@@ -166,11 +166,20 @@ class PipelineLive:
         self.dir_lines = [np.asarray([d[k] for k in d], np.float64).reshape(-1, 4) for _, d in zones]
         self.counter, self.last, self.last_stats = None, None, (0, 0)
 
-    def attach(self, tracker_ids):
+    def attach(self, tracker_ids, annotate=None):
+        """annotate: None, or the keyword arguments of `LiveCounter.enable_overlay` (max_batch, max_rows_per_frame, depth) -- every
+        batch then also leaves its overlay lists on the device for `Renderer.submit_live`."""
         from .engine import LiveCounter
         if self.counter is not None:
             raise RuntimeError("the live counter is attached already")
         self.counter = LiveCounter(self.engine, tracker_ids, self.polygons, self.dir_lines)
+        if annotate is not None:
+            try:
+                self.counter.enable_overlay(self.direction_keys, **annotate)
+            except BaseException:
+                self.counter.close()
+                self.counter = None
+                raise
 
     def counts(self):
         return self.counter.counts() if self.counter is not None else self.last
@@ -256,17 +265,48 @@ class CountingPipeline:
         return PipelineLive(self.engine, cam_names, zone_paths, len(self.class_names), on_counts)
 
     @contextlib.contextmanager
-    def _live(self, live, trackers):
+    def _live(self, live, trackers, annotate=None):
         """Attach `live` (or nothing) to these VideoTrackers for the length of a run; detached -- with its final counts kept -- before
         `_video` gives the trackers back, which the engine refuses while a counter is attached."""
         if live is None:
             yield
             return
-        live.attach(np.array([t.tracker_ids for t in trackers], np.int32))
+        live.attach(np.array([t.tracker_ids for t in trackers], np.int32), annotate=annotate)
         try:
             yield
         finally:
             live.detach()
+
+    @contextlib.contextmanager
+    def _annotator(self, live, sink, n_frames, batch, h, w, mixed_sizes=False, depth=2, rows_per_frame=64):
+        """The render side of run_stream / run_streams(annotate=sink): a Renderer of `depth` batches, and paint(n_frames_done, src, b) that
+        renders one tracked batch through `Renderer.submit_live` into the sink's next b frames.  before_run() is called in front of every
+        run call and before an ingest slot is restaged: it collects until fewer than `depth` batches are in flight, so a list buffer is
+        free for the run and the slot's last reader is done.  Yields (overlay arguments for PipelineLive.attach, before_run, paint,
+        drain)."""
+        if sink is None:
+            yield None, (lambda: None), None, (lambda: None)
+            return
+        if live is None:
+            raise ValueError("annotate= needs live=: the overlay lists are built beside the live counter")
+        if mixed_sizes:
+            raise ValueError("annotate= with mixed_sizes=True: overlay lists are built for uniform batches only")
+        if (sink.h, sink.w) != (h, w) or len(sink) < n_frames:
+            raise ValueError(f"the sink holds {len(sink)} frames of {sink.h}x{sink.w}, the stream has {n_frames} of {h}x{w}")
+        from .engine import Renderer
+        with Renderer(self.engine, max_batch=batch, max_hw=(h, w), depth=depth) as rnd:
+            def before_run():
+                while rnd.outstanding >= depth:
+                    rnd.collect()
+
+            def paint(f0, src, b):
+                rnd.submit_live(live.counter, src, b, h, w, sink.address(f0), kind="bgr_dev", out_desc=sink.desc, out_is_dev=sink.is_device)
+
+            def drain():                                    # while the counter is still attached: its lists are what the batches read
+                while rnd.outstanding:
+                    rnd.collect()
+
+            yield dict(max_batch=batch, max_rows_per_frame=rows_per_frame, depth=depth), before_run, paint, drain
 
     def _finish(self, counter, obj, cam_name):
         out = os.path.join(self.saved_path, cam_name + ".csv") if self.saved_path else None
@@ -352,7 +392,7 @@ class CountingPipeline:
                 collect()
         return self._finish(counter, obj, cam_name)
 
-    def run_stream(self, source, cam_name, zone_path, batch=16, asynchronous=False, host_frames=False, live=None):
+    def run_stream(self, source, cam_name, zone_path, batch=16, asynchronous=False, host_frames=False, live=None, annotate=None):
         """asynchronous=True: the tracker kernel of batch n runs on the engine's tracker stream while batch n+1 is submitted and
         embedded (`stream_run_async` / `stream_collect`); rows are identical, they arrive one batch later.
         host_frames=True: the frames stay in (pinned) host memory, as the reference's loader delivers them, and cross PCIe batch by
@@ -361,7 +401,11 @@ class CountingPipeline:
         A `YuvFrameSource` takes the same modes: its frames (any of its formats) are converted to BGR on the device as they are staged
         (`stream_stage_yuv_host` from pinned YUV -- half the PCIe bytes of BGR for 8-bit 4:2:0, two thirds for i422, the same for p016 /
         i010 / i444 -- or `stream_stage_yuv_dev` from the uploaded clip).
-        live (`open_live([cam_name], [zone_path])`): the running counts of this camera on the device, see PipelineLive."""
+        live (`open_live([cam_name], [zone_path])`): the running counts of this camera on the device, see PipelineLive.
+        annotate (a `YuvFrameSink` of the stream's frame size, with `live`): the live annotated video in ONE pass -- every batch's
+        overlay lists are built on the device behind its tracker launch (`overlay.LiveVisualizer` is the definition) and the batch is
+        rendered into the sink's next frames through `Renderer.submit_live` while the following batches run, two batches in flight.
+        Rows, counts and the CSV are what they are without it."""
         import torch
         tracker, counter = self._stages(cam_name, source.video_info, zone_path)
         obj = {"frames": [], "tracks": [], "labels": [], "boxes": []}
@@ -391,13 +435,15 @@ class CountingPipeline:
             obj["labels"].extend(rows[:, 5].tolist())
             obj["boxes"].extend(list(rows[:, :4].copy()))
 
-        with self._video(tracker), self._live(live, [tracker]):
+        with self._video(tracker), self._annotator(live, annotate, t, batch, h, w) as (ov_args, before_run, paint, drain), \
+                self._live(live, [tracker], annotate=ov_args):
             for n in range(min(2, len(starts))):            # staging order = batch order (the engine hands its four host slots out round-robin)
                 stage(n)
             if starts:
                 self.engine.stream_submit(ptr[0], size(0), h, w)
             for n, f0 in enumerate(starts):
                 b = size(n)
+                before_run()                                # annotate: a list buffer is free, and batch n - 2 no longer reads the slot staged next
                 if n + 2 < len(starts):                     # copy batch n+2 (host frames) under the detector of batch n+1
                     stage(n + 2)
                 if n + 1 < len(starts):                     # detect the next batch while this one is tracked
@@ -408,6 +454,8 @@ class CountingPipeline:
                         record(starts[n - 1], *self.engine.stream_collect()[:2])
                 else:
                     record(f0, *self.engine.stream_run_packed(tracker.tracker_ids, ptr[n], b, h, w)[:2])
+                if paint is not None:                       # the batch's lists were built behind its tracker launch: rendered from the BGR frames it ran on
+                    paint(f0, ptr[n], b)
                 if live is not None and (n > 0 or not asynchronous):
                     live.notify(n)                          # batches 0..n are enqueued: their rows are in the counts
                 ptr.pop(n - 1, None)
@@ -415,6 +463,7 @@ class CountingPipeline:
                 record(starts[-1], *self.engine.stream_collect()[:2])
                 if live is not None:
                     live.notify(len(starts) - 1)
+            drain()
         return self._finish(counter, obj, cam_name)
 
     def visualizer(self, rows, zone_path):
@@ -468,7 +517,7 @@ class CountingPipeline:
                 rnd.collect()
         return sink
 
-    def run_streams(self, sources, cam_names, zone_paths, batch=16, host_frames=False, mixed_sizes=False, live=None):
+    def run_streams(self, sources, cam_names, zone_paths, batch=16, host_frames=False, mixed_sizes=False, live=None, annotate=None):
         """S videos at once on ONE engine (the reference runs them one after another, each with a new VideoTracker,
         modules/__init__.py:28-36): the frames of the cameras are interleaved round-robin into batches of `batch` frames, the
         detector and the ReID net see one batch, every camera's frames are stepped on that camera's own trackers
@@ -484,8 +533,13 @@ class CountingPipeline:
         (`engine.autoshape_net_size`) is the same -- at size 640, 1920x1080, 1280x720, 640x360 and 320x180 all run at 384x640.  Each
         batch is a sized batch (`stream_stage_frames_sized`): one detector pass, and every camera still gets the result of running
         alone.  Cameras whose network shapes differ are refused; run each group of equal shapes in a call of its own.
-        live (`open_live(cam_names, zone_paths)`): the running counts of all cameras on the device, see PipelineLive."""
+        live (`open_live(cam_names, zone_paths)`): the running counts of all cameras on the device, see PipelineLive.
+        annotate (a `YuvFrameSink`, with `live`; not with mixed_sizes): as in `run_stream`, for all cameras into ONE sink in batch
+        (interleaved) order; the call then returns (results, [(camera index, 1-based frame number) of every sink frame]).  Each sink
+        frame is a self-contained surface: an encoder per camera takes its frames by `sink.address(i)`."""
         import torch
+        if annotate is not None and mixed_sizes:
+            raise ValueError("annotate= with mixed_sizes=True: overlay lists are built for uniform batches only")
         S = len(sources)
         order = []                                                                       # (camera, frame) round-robin, exhausted cameras drop out
         for t in range(max(len(s) for s in sources)):
@@ -513,7 +567,10 @@ class CountingPipeline:
 
             stage = lambda n: None                                                       # the whole clip is on the device already
             submit = lambda n: self.engine.stream_submit(*batch_ptr(n), h, w)
-            run = lambda n, tids, bcams: self.engine.stream_run_async_multi(tids, bcams, *batch_ptr(n), h, w)
+
+            def run(n, tids, bcams):                                                     # returns the batch's BGR frames on the device
+                self.engine.stream_run_async_multi(tids, bcams, *batch_ptr(n), h, w)
+                return batch_ptr(n)[0]
         stages = [self._stages(n, s.video_info, z) for n, s, z in zip(cam_names, sources, zone_paths)]
         tids = np.array([st[0].tracker_ids for st in stages], np.int32)                 # [S][num_classes]
         objs = [{"frames": [], "tracks": [], "labels": [], "boxes": []} for _ in range(S)]
@@ -528,18 +585,24 @@ class CountingPipeline:
                 o["labels"].extend(rows[sel, 5].tolist())
                 o["boxes"].extend(list(rows[sel, :4].copy()))
 
-        with self._video(*[st[0] for st in stages]), self._live(live, [st[0] for st in stages]):
+        s0 = sources[0]
+        h0, w0 = (s0.h, s0.w) if isinstance(s0, YuvFrameSource) else s0.frames.shape[1:3]
+        with self._video(*[st[0] for st in stages]), self._annotator(live, annotate, len(order), batch, h0, w0, mixed_sizes) as (ov_args, before_run, paint, drain), \
+                self._live(live, [st[0] for st in stages], annotate=ov_args):
             for n in range(min(2, len(starts))):            # staging order = batch order (four slots, round-robin)
                 stage(n)
             if starts:
                 submit(0)
             for n in range(len(starts)):
                 f0, b = span(n)
+                before_run()                                # annotate: a list buffer is free, and batch n - 2 no longer reads the slot staged next
                 if n + 2 < len(starts):                     # gather batch n+2 under the detector of batch n+1
                     stage(n + 2)
                 if n + 1 < len(starts):
                     submit(n + 1)
-                run(n, tids, cams[f0:f0 + b])
+                frames_dev = run(n, tids, cams[f0:f0 + b])
+                if paint is not None:                       # sink frame f0 + i = frame i of the batch: interleaved order
+                    paint(f0, frames_dev, b)
                 if n > 0:
                     record(starts[n - 1], *self.engine.stream_collect()[:2])
                     if live is not None:
@@ -548,7 +611,11 @@ class CountingPipeline:
                 record(starts[-1], *self.engine.stream_collect()[:2])
                 if live is not None:
                     live.notify(len(starts) - 1)
-        return [self._finish(st[1], o, n) for st, o, n in zip(stages, objs, cam_names)]
+            drain()
+        results = [self._finish(st[1], o, n) for st, o, n in zip(stages, objs, cam_names)]
+        if annotate is not None:
+            return results, [(int(c), int(t) + 1) for c, t in order]
+        return results
 
     def _frames_batches(self, sources, cam_names, host_frames, mixed_sizes, order, span):
         """run_streams over per-camera clips: camera c frame t is read at base_c + t * stride_c with that camera's descriptor.  Returns
@@ -590,11 +657,13 @@ class CountingPipeline:
             else:
                 self.engine.stream_submit(ptr[n], span(n)[1], h, w)
 
-        def run(n, tids, bcams):
+        def run(n, tids, bcams):                             # returns the batch's BGR slot
+            p = ptr.pop(n)
             if mixed_sizes:
-                self.engine.stream_run_async_multi_sized(tids, bcams, ptr.pop(n), dims(n))
+                self.engine.stream_run_async_multi_sized(tids, bcams, p, dims(n))
             else:
-                self.engine.stream_run_async_multi(tids, bcams, ptr.pop(n), span(n)[1], h, w)
+                self.engine.stream_run_async_multi(tids, bcams, p, span(n)[1], h, w)
+            return p
 
         return stage, submit, run
 
