@@ -1,6 +1,6 @@
 """GPU: the live overlay (csrc/live_overlay.hip) -- the build kernels in one launch each against the definition on the case table of
 tests/live_overlay_cases.py; attached to an engine: the lists of every batch equal overlay.LiveVisualizer fed the collected rows, rows
-and counts are what they are without it; CountingPipeline.run_stream / run_streams(annotate=sink): every output byte equals the
+and counts are what they are without it, and a batch without a single box still numbers and draws its frames; CountingPipeline.run_stream / run_streams(annotate=sink): every output byte equals the
 existing Renderer.submit given the host-built lists of the same batches; refusals leave the state as it was; a counter without the
 overlay launches what it launched before."""
 import json
@@ -141,6 +141,69 @@ def test_rows_and_counts_are_untouched_by_the_overlay(attached_runs, multi):
         np.testing.assert_array_equal(x["fidx"], y["fidx"])
         np.testing.assert_array_equal(x["counts"], y["counts"])
     assert a[-1]["counts"].sum() >= 3
+
+
+def test_a_batch_without_a_box_still_numbers_and_draws_its_frames(eng):
+    """track_enqueue's path for a batch that steps no tracker, with a counter and its overlay attached: two cameras x two labels, three
+    batches of four frames, the middle one without a single box.  It gives no row, its frames take their cameras' next numbers (the
+    third batch's lists carry frames 5 and 6), its lists are the definition's for frames without rows, and the rows of the batches
+    around it are the oracle's VideoTracker.run per camera, which is never called for a frame without boxes (Q1)."""
+    import torch
+    import vehicle_counting_amd.engine as E
+    from oracle import deepsort as od
+    from oracle import reid as orr
+    from oracle import yolov5 as oy
+    from vehicle_counting_amd.weights import synth_reid
+    NB = 3
+    clips = [clip(0), clip(1)]
+    order = [(k, t) for t in range(NB * B // 2) for k in range(2)]
+    dev = torch.from_numpy(np.stack([clips[k][0][t] for k, t in order])).cuda()
+    nmax = max(len(clips[k][1][t]) for k, t in order)
+    assert nmax <= 8
+    det, cnt = np.zeros((len(order), nmax, 6), np.float32), np.zeros(len(order), np.int32)
+    for g, (k, t) in enumerate(order):
+        if B <= g < 2 * B:
+            continue
+        for i, (x, y, w, h, label) in enumerate(clips[k][1][t]):
+            det[g, i] = (x, y, x + w, y + h, 0.9, label)
+        cnt[g] = len(clips[k][1][t])
+    cfg = dict(MAX_DIST=0.2, MIN_CONFIDENCE=0.25, NMS_MAX_OVERLAP=1.0, MAX_IOU_DISTANCE=0.7, MAX_AGE=2, N_INIT=1, NN_BUDGET=8)     # TRACK_KW
+    oracle = [od.VideoTrackerOracle(NL, cfg, orr.make_embedder(synth_reid(1702))) for _ in range(2)]
+    want_rows = []
+    for g, (k, t) in enumerate(order):
+        if cnt[g] == 0:
+            want_rows.append(np.zeros((0, 6), np.int64))
+            continue
+        m = oy.marshal_like_reference(det[g, :cnt[g]])
+        res = oracle[k].run(clips[k][0][t], m["bboxes"], m["classes"], m["scores"])
+        want_rows.append(np.array([list(b) + [tr, lb] for b, tr, lb in zip(res["boxes"], res["tracks"], res["labels"])], dtype=np.int64).reshape(-1, 6))
+    tids = np.array([[eng.tracker_create(**TRACK_KW) for _ in range(NL)] for _ in range(2)], np.int32)
+    live = E.LiveCounter(eng, tids, [ZONE] * 2, CAM_LINES)
+    lv = ov.LiveVisualizer([ZONE] * 2, CAM_DIRS, NL)
+    live.enable_overlay(CAM_KEYS, max_batch=B, max_rows_per_frame=16, depth=2)
+    try:
+        for n in range(NB):
+            sl = slice(n * B, (n + 1) * B)
+            eng.stream_inject(det[sl], cnt[sl])
+            eng.stream_submit(dev[sl].data_ptr(), B, H, W)
+            eng.stream_run_async_multi(tids, [k for k, _ in order[sl]], dev[sl].data_ptr(), B, H, W, cap_rows=32)
+            rows, fidx, _ = eng.stream_collect()
+            got = per_frame(rows, fidx, B)
+            print(f"batch {n}: {len(rows)} rows")
+            assert (len(rows) == 0) == (n == 1)
+            for f in range(B):
+                np.testing.assert_array_equal(got[f], want_rows[n * B + f], err_msg=f"batch {n}, frame {f}")
+            assert live.counts(with_frames=True)[1].tolist() == [(n + 1) * B // 2] * 2
+            prims, first = live.overlay_lists()
+            want_prims, want_first = lv.batch_prims([k for k, _ in order[sl]], [t + 1 for _, t in order[sl]], got, (H, W))
+            np.testing.assert_array_equal(first, want_first, err_msg=f"batch {n}")
+            np.testing.assert_array_equal(prims, want_prims, err_msg=f"batch {n}")
+    finally:
+        eng.stream_inject(None)
+        eng.stream_reset()
+        live.close()
+        for t in tids.reshape(-1):
+            eng.tracker_destroy(int(t))
 
 
 @pytest.fixture()

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "track_batch_plan.h"   // TrackTaskHost, TrackBatchPlan: what track_enqueue decides about a batch, which needs no engine either
 #include "det_prep.h"     // FrameDets, Prepared, FramePrepared: the detection hand-over that needs no engine
 #include "host_stage.h"   // dev_alloc, and DevScratch for the entry points that stage host arrays beside their kernels (yuv_ingest.hip, yuv_egress.hip)
 
@@ -94,9 +95,6 @@ inline int tracker_slot(const std::vector<std::unique_ptr<Tracker>>& v, int hand
     return handle >= 0 && tracker_ok(v, s) && v[s]->gen == g ? s : -1;
 }
 
-// one (frame, class) step of a batch as the host sees it
-struct TrackTaskHost { int tracker, label, frame, det_off, det_n; };
-
 // Staging of one tracker batch: inputs (tasks, plans, detections) in one pinned block mirrored on the device by a single copy;
 // outputs (rows, per-task counts, status) written by the kernel straight into pinned host memory.
 struct TrackStage {
@@ -105,12 +103,8 @@ struct TrackStage {
     int* d_cursor = nullptr;                 // [0] row cursor
     hipEvent_t done = nullptr;
     bool busy = false;
-    // layout of the current batch
-    int n_tasks = 0, n_wg = 0, n_dets = 0, rows_cap = 0, b = 0, W = 0, H = 0, step_cap = 0;
-    std::vector<TrackTaskHost> tasks;        // (frame, class) order = output order
-    std::vector<int> dev_index;              // tasks[i] is the device's task dev_index[i]
-    std::vector<std::pair<int, int>> tracker_dets;   // (tracker, detections enqueued) for the pending_dets bookkeeping
-    std::vector<int> last_task_of;           // per entry of tracker_dets: device index of the tracker's last task
+    TrackBatchPlan plan;                     // the current batch: tasks, sizes and the layout of both blocks (track_batch_plan.h)
+    std::vector<int> frame_trk;              // per frame of it the slot of a tracker of the frame's camera, -1 none (filled while a live counter exists)
     int* d_row_slot = nullptr; size_t row_slot_cap = 0;   // TrackBatchArgs::row_slot of this stage, allocated once a live counter is attached
 };
 

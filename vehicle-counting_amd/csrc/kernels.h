@@ -2,6 +2,7 @@
 // track_kernels.hip).  All take the stream they run on; none allocates or synchronises.
 #pragma once
 #include "vc_common.h"
+#include "track_batch_plan.h"   // TrackTask, TrackWgPlan, VC_ROW_CHUNK, VC_TRACK_DYN_LDS_BYTES: what the tracker kernels share with the batch planner
 
 namespace vc {
 
@@ -117,19 +118,11 @@ struct CostJob {
     int out_off;     // offset into the output cost array
     int tsu;         // time since update
 };
-// One tracker step = (tracker, frame): Tracker.predict() + Tracker.update(detections) on the prepared (confidence-filtered,
-// DeepSORT-NMS'ed, deep_sort.py:31-41) detections [det_off, det_off + det_n) of the batch's detection arrays.
-// frame_w / frame_h: the size this task's boxes are clamped to (a camera of a sized batch); 0 = TrackBatchArgs.frame_w / frame_h.
-struct TrackTask { int tracker, det_off, det_n, frame, label, frame_w, frame_h, pad2; };
-// workgroup b of the batch kernel owns one tracker and runs its tasks [task_begin, task_end) in order; the tracker's detections of
-// the batch are the contiguous range [det_begin, det_begin + det_n) of the detection arrays (frames ascending)
-struct TrackWgPlan { int tracker, task_begin, task_end, det_begin, det_n, pad0, pad1, pad2; };
+// (TrackTask and TrackWgPlan, one tracker step and one workgroup's share of a batch: track_batch_plan.h)
 // Appearance dot products hoisted out of the sequential tracker loop (track_kernels.hip, "dots"): every gallery sample a tracker
 // can hold during the batch is either a sample it held when the batch began or the normalised feature of one of the batch's own
 // detections, so <sample, detection feature> for ALL pairs is state-independent and is computed up front by a grid-wide kernel.
 // table[row * n_dets + d]: rows [0, n_old_rows) = the old samples (track order, ring position), rows n_old_rows + e = detection e.
-#define VC_TRACK_DYN_LDS_BYTES (96 * 1024)   // dynamic LDS the tracker kernels may ask for: step work arrays (62.5 KB at 512 tracks + detections) + the assignment matrix
-#define VC_ROW_CHUNK 128          // rows of the output arena a tracker workgroup reserves at a time
 struct TrackDotPlan { long long table_off; int n_old_rows, n_dets, row_src_off, tile_begin, tiles, det_tiles, use_table, pad; };
 struct TrackBatchArgs {
     TrackPool pool;

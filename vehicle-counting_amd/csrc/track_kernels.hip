@@ -643,7 +643,7 @@ __global__ __launch_bounds__(NW * 64) void track_batch_kernel(const TrackBatchAr
             // rows: the arena is handed out in chunks (one atomic per VC_ROW_CHUNK rows instead of one per step)
             const int m = compact(L, T, [&](int t) { return w.state[t] == CONFIRMED && w.tsu[t] <= 1; }, [](int, int) {});
             if (m > row_left) {
-                const int grab = max(m, VC_ROW_CHUNK);
+                const int grab = track_row_grab(m);             // track_batch_plan.h, next to the arena bound that relies on it
                 int b0 = 0;
                 if (lane == 0) b0 = __hip_atomic_fetch_add(a.row_cursor, grab, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 row_base = __shfl(b0, 0); row_left = grab;

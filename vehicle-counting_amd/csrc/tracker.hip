@@ -5,6 +5,11 @@
 // (modules/track.py:16).  (The single-function entry points -- vc_kalman_*_host, vc_iou_cost_host, vc_cosine_cost_host, vc_lap_host --
 // are host_track.hip.)
 //
+// What a batch needs is decided without the engine by plan_track_batch (track_batch_plan.h: device order, workgroup plans, step capacity,
+// assignment-matrix LDS, table fit, arena sizes, block layouts; held to hand-computed numbers by tests/test_track_batch_plan_host.py).
+// track_enqueue is the sequence around it -- tasks, plan, overlay begin, reserve buffers, fill the input block, number the frames, upload,
+// launch, overlay build, event -- one static function per step above it; TrackStage keeps the plan for track_collect.
+//
 // Reference (paths relative to /root/reference/networks/deepsort/):
 //   deep_sort.py:25-59            DeepSort.update (confidence filter :31, tlwh :68-87, NMS :37-41 -> det_prep.h; predict/update :44-45, rows :46-58)
 //   sort/preprocessing.py:6-73    non_max_suppression (quirk Q6)                      -> det_prep.h: dsort_nms (host: state-independent)
@@ -19,6 +24,7 @@
 #include <cstdint>
 #include <cstdlib>
 
+#define VC_TRACK_BATCH_PLANNER    // track_batch_plan.h, reached through engine.h: with plan_track_batch, which brings track_core.h in
 #include "engine.h"
 #include "track_core.h"
 
@@ -27,8 +33,6 @@ namespace vc {
 using namespace tc;
 
 // ------------------------------------------------------------------------------------------------ pool
-static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 int tracker_init_pool(vc_engine* e) {
     const size_t T = e->cfg.max_tracks, S = e->cfg.nn_budget_cap;
     VC_CHECK(T >= 1 && S >= 1, VC_ERR_ARG, "max_tracks and nn_budget_cap must be positive");
@@ -93,278 +97,230 @@ int track_idle(vc_engine* e) {
     return VC_OK;
 }
 
-// output block layout (pinned, written by the kernel)
-struct OutLayout { size_t rows, row_off, row_n, ntracks, tT, status, total; };
-static OutLayout out_layout(int n_tasks, int rows_cap) {
-    OutLayout o;
-    size_t p = 0;
-    o.rows = p; p = align16(p + (size_t)rows_cap * 6 * sizeof(long long));
-    o.row_off = p; p = align16(p + (size_t)n_tasks * 4);
-    o.row_n = p; p = align16(p + (size_t)n_tasks * 4);
-    o.ntracks = p; p = align16(p + (size_t)n_tasks * 4);
-    o.tT = p; p = align16(p + (size_t)n_tasks * 4);
-    o.status = p; p = align16(p + 16);
-    o.total = p;
-    return o;
-}
-
-int track_enqueue(vc_engine* e, int st, const std::vector<std::vector<FrameClassDets>>& frames, const float* d_feat, int W, int H,
-                  int rows_cap, hipEvent_t wait, const vc_frame_dims* frame_dims, const int* frame_tracker) {
-    TrackStage& s = e->tstage[st];
-    VC_CHECK(!s.busy, VC_ERR_STATE, "tracker staging slot %d is still in flight", st);
-    // tasks in (frame, class) order -- the order rows are handed back in
-    s.tasks.clear(); s.tracker_dets.clear(); s.last_task_of.clear();
-    std::vector<const FrameClassDets*> src;
+// ------------------------------------------------------------------------------------------------ track_enqueue, step by step
+// the tasks in (frame, class) order -- the order rows are handed back in -- and the detections each one brings
+static int batch_tasks(vc_engine* e, const std::vector<std::vector<FrameClassDets>>& frames, std::vector<TrackTaskHost>& tasks,
+                       std::vector<const FrameClassDets*>& src) {
+    tasks.clear();
     for (size_t f = 0; f < frames.size(); ++f)
         for (const FrameClassDets& g : frames[f]) {
             VC_CHECK(tracker_ok(e->trackers, g.tracker), VC_ERR_NOTFOUND, "bad tracker id %d", g.tracker);
-            s.tasks.push_back(TrackTaskHost{g.tracker, g.label, (int)f, 0, (int)g.dets.conf.size()});
+            tasks.push_back(TrackTaskHost{g.tracker, g.label, (int)f, 0, (int)g.dets.conf.size()});
             src.push_back(&g);
         }
-    const int n_tasks = (int)s.tasks.size();
-    s.n_tasks = n_tasks; s.rows_cap = rows_cap; s.b = (int)frames.size(); s.W = W; s.H = H; s.n_wg = 0; s.n_dets = 0;
-    // Overlay lists (live_overlay.hip): the counters of this batch's cameras whose overlay is enabled -- none unless vc_live_overlay_enable
-    // has run, and then the launch below is exactly what it was.  Lists are built for uniform batches only.
-    std::vector<LiveOverlayPlan> ov;
-    std::vector<int> frame_trk;
-    if (!frame_dims && !e->lives.empty()) {
-        frame_trk.resize(frames.size());
-        for (size_t f = 0; f < frames.size(); ++f) frame_trk[f] = frame_tracker ? frame_tracker[f] : frames[f].empty() ? -1 : frames[f][0].tracker;
-        VC_TRY(live_overlay_begin(e, frame_trk, e->stream, ov));
-    }
-    if (n_tasks == 0) {                                      // nothing to step; the frames still count for their cameras' live counters
-        std::vector<long long> fno(frames.size(), 0);
-        if (frame_tracker) for (size_t f = 0; f < frames.size(); ++f) fno[f] = live_next_frame(e, frame_tracker[f]);
-        if (!ov.empty()) {                                   // anno, text and frame number
-            ProfScope ps(e, VC_PROF_TRACK);
-            VC_TRY(live_overlay_finish(e, ov, frame_trk, fno.data(), nullptr, 0, (int)frames.size(), H, W, e->stream));
-        }
-        s.busy = true; VC_HIP(hipEventRecord(s.done, e->stream)); return VC_OK;
-    }
-    // device order: grouped by tracker, frames ascending inside a group (stable sort of the frame-major list); the detection arrays
-    // follow the same order, so every tracker's detections of the batch are one contiguous range
-    std::vector<int> order(n_tasks);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return s.tasks[a].tracker < s.tasks[b].tracker; });
-    s.dev_index.assign(n_tasks, 0);
-    for (int k = 0; k < n_tasks; ++k) s.dev_index[order[k]] = k;
-    std::vector<TrackWgPlan> plans;
-    int need = 8, n_dets = 0;
-    long long mat_need = 0;              // entries of the largest assignment problem a step of this batch is likely to pose (tracks x detections)
-    // Do the appearance tables of ALL trackers fit the arena for certain?  Bound from what the host knows: the tracks of the last
-    // collected batch (known_tracks) hold at most a full gallery each, and every detection of a batch still in flight (pending_dets)
-    // adds at most ONE gallery row -- it either extends one track's ring or starts a track with a single sample (tracker.py:82-91,
-    // 133-139).  (Round 2 charged a full gallery per pending detection: at 256 detections per frame that bound was 1.3 GB per tracker,
-    // nothing "fitted", and the batch ran on the fallback instance.)  Then the lean kernel instance (no fallback code, 8 waves) runs.
-    long long table_floats = 0, table_rows = 0;
-    bool all_tables = true;
-    for (int k = 0; k < n_tasks;) {
-        const int tr = s.tasks[order[k]].tracker;
-        int k1 = k, dets = 0, dmax = 0;
-        const int det_begin = n_dets;
-        while (k1 < n_tasks && s.tasks[order[k1]].tracker == tr) {
-            TrackTaskHost& t = s.tasks[order[k1]];
-            t.det_off = n_dets; n_dets += t.det_n;
-            dets += t.det_n; dmax = std::max(dmax, t.det_n);
-            ++k1;
-        }
-        plans.push_back(TrackWgPlan{tr, k, k1, det_begin, dets, 0, 0, 0});
-        {
-            const Tracker& tk = *e->trackers[tr];
-            const long long old_rows = (long long)tk.known_tracks * std::min(e->pool.budget_cap, tk.p.nn_budget) + tk.pending_dets;
-            const long long need_f = (old_rows + dets) * dets;
-            if (need_f >= (1ll << 31)) all_tables = false;
-            table_floats += need_f; table_rows += old_rows;
-        }
-        // LDS capacity from the tracker's recent size (the kernel falls back to global-memory work arrays for a larger step)
-        need = std::max(need, 2 * e->trackers[tr]->known_tracks + 2 * dmax + 16);
-        mat_need = std::max(mat_need, (long long)(e->trackers[tr]->known_tracks + 32) * dmax);
-        s.tracker_dets.emplace_back(tr, dets);
-        s.last_task_of.push_back(k1 - 1);
-        k = k1;
-    }
-    s.n_dets = n_dets;
-    // work-array capacity: 32, else the next multiple of 64 (a power of two, as before round 3, doubled the arrays' LDS for a 310-entry
-    // step and left no room for the assignment matrix next to them)
-    const int cap = need <= 32 ? 32 : std::min((int)TC_HARD_CAP, (need + 63) / 64 * 64);
-    const int n_wg = (int)plans.size();
-    s.n_wg = n_wg;
-    s.step_cap = cap;
-    // input block
-    size_t p = 0;
-    const size_t o_tasks = p; p = align16(p + (size_t)n_tasks * sizeof(TrackTask));
-    const size_t o_plans = p; p = align16(p + (size_t)n_wg * sizeof(TrackWgPlan));
-    const size_t o_tlwh = p; p = align16(p + (size_t)n_dets * 32);
-    const size_t o_xyah = p; p = align16(p + (size_t)n_dets * 32);
-    const size_t o_frow = p; p = align16(p + (size_t)n_dets * 4);
-    // live counters (live_count.hip): does one own a tracker of this batch?  Then the batch carries its frames' numbers, and the kernel
-    // writes the slot behind every row
+    return VC_OK;
+}
+
+// live counters (live_count.hip): does one own a tracker of this batch, or the camera of one of its frames?  Then the batch carries its
+// frames' numbers, and the kernel writes the slot behind every row
+static bool batch_is_live(const vc_engine* e, const std::vector<TrackTaskHost>& tasks, int b, const int* frame_tracker) {
     bool live = false;
-    for (const TrackWgPlan& pl : plans) live = live || e->trackers[pl.tracker]->live != nullptr;
-    if (frame_tracker) for (size_t f = 0; f < frames.size(); ++f) live = live || (tracker_ok(e->trackers, frame_tracker[f]) && e->trackers[frame_tracker[f]]->live);
-    const size_t o_fno = p;
-    if (live) p = align16(p + frames.size() * sizeof(long long));
-    // The kernel reserves rows in chunks: a workgroup that needs m rows and has fewer left abandons the rest of its chunk and grabs
-    // max(m, VC_ROW_CHUNK) fresh ones, so the rows it abandons are always fewer than the rows of the step that follows -- consumption
-    // is bounded by twice the rows emitted plus one unfinished chunk per workgroup (`cap + chunk` was a spurious TERR_ROWS
-    // for steady steps of 65..127 rows).
-    rows_cap = 2 * rows_cap + n_wg * VC_ROW_CHUNK;
-    s.rows_cap = rows_cap;
-    const OutLayout ol = out_layout(n_tasks, rows_cap);
-    VC_TRY(stage_reserve(e, s, p, ol.total));
-    if (live && (size_t)rows_cap > s.row_slot_cap) {            // like the staging blocks: the old one stays allocated, a batch in flight may use it
-        s.row_slot_cap = (size_t)rows_cap * 3 / 2;
+    if (e->lives.empty()) return live;
+    for (const TrackTaskHost& t : tasks) live = live || e->trackers[t.tracker]->live != nullptr;
+    if (frame_tracker) for (int f = 0; f < b; ++f) live = live || (tracker_ok(e->trackers, frame_tracker[f]) && e->trackers[frame_tracker[f]]->live);
+    return live;
+}
+
+// every buffer the planned batch needs, grown before anything is written or enqueued
+static int reserve_buffers(vc_engine* e, TrackStage& s) {
+    const TrackBatchPlan& bp = s.plan;
+    const size_t n_wg = (size_t)bp.n_wg(), n_dets = (size_t)bp.n_dets;
+    VC_TRY(stage_reserve(e, s, bp.in.total, bp.out.total));
+    if (bp.live && (size_t)bp.rows_cap > s.row_slot_cap) {      // like the staging blocks: the old one stays allocated, a batch in flight may use it
+        s.row_slot_cap = (size_t)bp.rows_cap * 3 / 2;
         VC_TRY(dev_alloc(e, (void**)&s.d_row_slot, s.row_slot_cap * sizeof(int)));
     }
-    TrackTask* ht = (TrackTask*)(s.h_in + o_tasks);
-    for (int k = 0; k < n_tasks; ++k) {
-        const TrackTaskHost& t = s.tasks[order[k]];
-        ht[k] = TrackTask{t.tracker, t.det_off, t.det_n, t.frame, t.label, frame_dims ? frame_dims[t.frame].w : 0, frame_dims ? frame_dims[t.frame].h : 0, 0};
-    }
-    memcpy(s.h_in + o_plans, plans.data(), (size_t)n_wg * sizeof(TrackWgPlan));
-    {
-        double* tl = (double*)(s.h_in + o_tlwh);
-        double* xy = (double*)(s.h_in + o_xyah);
-        int* fr = (int*)(s.h_in + o_frow);
-        for (int k = 0; k < n_tasks; ++k) {
-            const FrameClassDets& c = *src[order[k]];
-            int g = s.tasks[order[k]].det_off;
-            for (size_t i = 0; i < c.dets.conf.size(); ++i, ++g) {
-                const double* t = &c.dets.tlwh[i * 4];
-                memcpy(tl + (size_t)g * 4, t, 32);
-                double* o = xy + (size_t)g * 4;                           // sort/detection.py:42-50 to_xyah
-                o[0] = t[0] + t[2] / 2; o[1] = t[1] + t[3] / 2; o[2] = t[2] / t[3]; o[3] = t[3];
-                fr[g] = c.dets.feat_rows[i];
-            }
-        }
-    }
     // buffers of the hoisted appearance dots (engine-wide: the tracker stream runs one batch at a time)
-    if ((size_t)n_wg > e->dot_plans_cap || (size_t)n_dets > e->nfeat_cap) {
+    if (n_wg > e->dot_plans_cap || n_dets > e->nfeat_cap) {
         VC_TRY(track_idle(e));
         VC_HIP(hipStreamSynchronize(e->stream));
-        if ((size_t)n_wg > e->dot_plans_cap) { e->dot_plans_cap = (size_t)n_wg * 2; VC_TRY(dev_alloc(e, (void**)&e->d_dot_plans, e->dot_plans_cap * sizeof(TrackDotPlan))); }
-        if ((size_t)n_dets > e->nfeat_cap) {
-            e->nfeat_cap = (size_t)n_dets * 3 / 2 + 64;
+        if (n_wg > e->dot_plans_cap) { e->dot_plans_cap = n_wg * 2; VC_TRY(dev_alloc(e, (void**)&e->d_dot_plans, e->dot_plans_cap * sizeof(TrackDotPlan))); }
+        if (n_dets > e->nfeat_cap) {
+            e->nfeat_cap = n_dets * 3 / 2 + 64;
             VC_TRY(dev_alloc(e, (void**)&e->d_nfeat, e->nfeat_cap * VC_FEAT_DIM * sizeof(float)));
             VC_TRY(dev_alloc(e, (void**)&e->d_det_ss, e->nfeat_cap * sizeof(float)));
         }
     }
-    const size_t scratch = (size_t)n_wg * track_scratch_per_wg();
+    const size_t scratch = n_wg * track_scratch_per_wg();
     if (scratch > e->track_scratch_bytes) {
         VC_TRY(track_idle(e));                                                // the old block may still be in use
         const size_t bytes = scratch * 3 / 2;
         VC_TRY(dev_alloc(e, (void**)&e->d_track_scratch, bytes));
         e->track_scratch_bytes = bytes;
     }
-    // appearance-table arena: grown to what this batch needs (bounded by dot_arena_max_floats).  When every tracker's table fits for
-    // certain the lean kernel instance runs; otherwise the arena still grows towards the bound (it used to stay at its
-    // 16-byte initial size then, and the per-tracker fit check on the device sent EVERY tracker to the in-walk appearance rows although
-    // most tables would have fitted) and the general instance serves the trackers whose tables fit from it.
-    const bool tables_fit = all_tables && table_floats <= (long long)e->dot_arena_max_floats && table_rows <= (long long)e->row_src_cap;
-    const size_t want_now = (size_t)std::min<long long>(std::max<long long>(table_floats, 0), (long long)e->dot_arena_max_floats);
-    if (want_now > e->dot_arena_floats) {
+    // appearance-table arena: grown to what this batch can use (plan_track_batch: bounded by dot_arena_max_floats, also when not every table fits)
+    if (bp.arena_want > e->dot_arena_floats) {
         VC_TRY(track_idle(e));
         VC_HIP(hipStreamSynchronize(e->stream));
-        const size_t want = std::min(e->dot_arena_max_floats, std::max(want_now * 3 / 2, (size_t)1 << 22));
+        const size_t want = std::min(e->dot_arena_max_floats, std::max(bp.arena_want * 3 / 2, (size_t)1 << 22));
         VC_TRY(dev_realloc(e, (void**)&e->d_dot_arena, want * sizeof(float)));
         e->dot_arena_floats = want;
     }
-    std::vector<LiveCountArgs> live_args;
-    if (live) {
-        // a frame belongs to the camera of frame_tracker[f] (else of its first task) and takes that camera's next number, 1-based and
-        // continuing across batches (modules/datasets.py:61); a frame of a camera without a counter gets 0, no row of it is read
-        long long* fno = (long long*)(s.h_in + o_fno);
-        for (size_t f = 0; f < frames.size(); ++f)
-            fno[f] = live_next_frame(e, frame_tracker ? frame_tracker[f] : frames[f].empty() ? -1 : frames[f][0].tracker);
-        std::vector<int> used;
-        for (const TrackWgPlan& pl : plans) used.push_back(pl.tracker);
-        live_batch_args(e, used, (const long long*)(s.d_in + o_fno), live_args);
+    return VC_OK;
+}
+
+// tasks, plans and the detections (tlwh, xyah, feature row) in device order; the frame numbers are number_frames'
+static void fill_input_block(TrackStage& s, const std::vector<const FrameClassDets*>& src) {
+    const TrackBatchPlan& bp = s.plan;
+    memcpy(s.h_in + bp.in.tasks, bp.dev_tasks.data(), bp.dev_tasks.size() * sizeof(TrackTask));
+    memcpy(s.h_in + bp.in.plans, bp.wg.data(), bp.wg.size() * sizeof(TrackWgPlan));
+    double* tl = (double*)(s.h_in + bp.in.tlwh);
+    double* xy = (double*)(s.h_in + bp.in.xyah);
+    int* fr = (int*)(s.h_in + bp.in.frow);
+    for (int i : bp.order) {
+        const Prepared& d = src[i]->dets;
+        int g = bp.tasks[i].det_off;
+        for (size_t k = 0; k < d.conf.size(); ++k, ++g) {
+            const double* t = &d.tlwh[k * 4];
+            memcpy(tl + (size_t)g * 4, t, 32);
+            double* o = xy + (size_t)g * 4;                               // sort/detection.py:42-50 to_xyah
+            o[0] = t[0] + t[2] / 2; o[1] = t[1] + t[3] / 2; o[2] = t[2] / t[3]; o[3] = t[3];
+            fr[g] = d.feat_rows[k];
+        }
     }
-    for (auto& td : s.tracker_dets) e->trackers[td.first]->pending_dets += td.second;
+}
+
+// a frame takes the next number of its camera (track_frame_cameras), 1-based and continuing across batches (modules/datasets.py:61);
+// a frame of a camera without a counter gets 0, no row of it is read
+static void number_frames(vc_engine* e, const std::vector<int>& frame_trk, long long* fno) {
+    for (size_t f = 0; f < frame_trk.size(); ++f) fno[f] = live_next_frame(e, frame_trk[f]);
+}
+
+// the input block to the device, and the cursors of the launch cleared behind it
+static int upload_inputs(vc_engine* e, TrackStage& s, hipEvent_t wait) {
     hipStream_t ts = e->stream;
     if (wait) VC_HIP(hipStreamWaitEvent(ts, wait, 0));
-    VC_HIP(hipMemcpyAsync(s.d_in, s.h_in, p, hipMemcpyHostToDevice, ts));
+    VC_HIP(hipMemcpyAsync(s.d_in, s.h_in, s.plan.in.total, hipMemcpyHostToDevice, ts));
     VC_HIP(hipMemsetAsync(s.d_cursor, 0, 64, ts));           // [0] row cursor, [4..6] status
     VC_HIP(hipMemsetAsync(e->d_dot_ctl, 0, 64, ts));
-    VC_HIP(hipMemsetAsync(e->d_dot_plans, 0, (size_t)n_wg * sizeof(TrackDotPlan), ts));
+    VC_HIP(hipMemsetAsync(e->d_dot_plans, 0, (size_t)s.plan.n_wg() * sizeof(TrackDotPlan), ts));
+    return VC_OK;
+}
+
+static TrackBatchArgs batch_args(vc_engine* e, const TrackStage& s, int st, const float* d_feat, int W, int H) {
+    const TrackBatchPlan& bp = s.plan;
     TrackBatchArgs a{};
     a.pool = e->pool;
     a.hdrs = e->d_hdrs; a.lists = e->d_lists; a.list_cap = e->list_cap; a.recs = e->d_recs;
     a.free_top = e->d_free; a.freed_count = e->d_free + 1; a.free_stack = e->d_free_stack; a.freed = e->d_freed;
-    a.plans = (const TrackWgPlan*)(s.d_in + o_plans); a.tasks = (const TrackTask*)(s.d_in + o_tasks);
-    a.det_tlwh = (const double*)(s.d_in + o_tlwh); a.det_xyah = (const double*)(s.d_in + o_xyah); a.det_featrow = (const int*)(s.d_in + o_frow);
+    a.plans = (const TrackWgPlan*)(s.d_in + bp.in.plans); a.tasks = (const TrackTask*)(s.d_in + bp.in.tasks);
+    a.det_tlwh = (const double*)(s.d_in + bp.in.tlwh); a.det_xyah = (const double*)(s.d_in + bp.in.xyah); a.det_featrow = (const int*)(s.d_in + bp.in.frow);
     a.feat = d_feat;
     a.dot_plans = e->d_dot_plans; a.dot_arena = e->d_dot_arena; a.dot_arena_floats = (long long)e->dot_arena_floats;
     a.row_src = e->d_row_src; a.row_src_cap = e->row_src_cap; a.gal_row = e->d_gal_row; a.nfeat = e->d_nfeat; a.det_ss = e->d_det_ss;
-    a.dot_ctl = e->d_dot_ctl; a.n_det_total = n_dets;
-    a.rows = (long long*)(s.hd_out + ol.rows); a.rows_cap = rows_cap; a.row_cursor = s.d_cursor;
-    a.task_row_off = (int*)(s.hd_out + ol.row_off); a.task_row_n = (int*)(s.hd_out + ol.row_n);
-    a.task_ntracks = (int*)(s.hd_out + ol.ntracks); a.task_T = (int*)(s.hd_out + ol.tT);
-    a.status = s.d_cursor + 4;                               // device memory (atomics), copied next to the rows below
-    a.scratch = e->d_track_scratch; a.scratch_per_wg = track_scratch_per_wg(); a.cap = cap; a.frame_w = W; a.frame_h = H;
-    a.all_tables = tables_fit ? 1 : 0;
-    a.row_slot = live ? s.d_row_slot : nullptr;
-    // Dense steps (BASELINE.json configs[2]: ~90 tracks x ~70 detections): the matrix the assignment scans goes into LDS behind the work
-    // arrays -- as much as the kernel's dynamic LDS allows; light batches ask for none (their problems fit the 2 KB static buffers, and
-    // a small LDS footprint lets conv workgroups share the tracker's CUs).
-    a.lmat_doubles = 0;
-    if (mat_need > 256) {
-        const long long room = ((long long)VC_TRACK_DYN_LDS_BYTES - (long long)step_work_bytes(cap)) / 8;
-        a.lmat_doubles = (int)std::max(0ll, std::min(room, (mat_need + 63) / 64 * 64));
-    }
+    a.dot_ctl = e->d_dot_ctl; a.n_det_total = bp.n_dets;
+    a.rows = (long long*)(s.hd_out + bp.out.rows); a.rows_cap = bp.rows_cap; a.row_cursor = s.d_cursor;
+    a.task_row_off = (int*)(s.hd_out + bp.out.row_off); a.task_row_n = (int*)(s.hd_out + bp.out.row_n);
+    a.task_ntracks = (int*)(s.hd_out + bp.out.ntracks); a.task_T = (int*)(s.hd_out + bp.out.tT);
+    a.status = s.d_cursor + 4;                               // device memory (atomics), copied next to the rows behind the launch
+    a.scratch = e->d_track_scratch; a.scratch_per_wg = track_scratch_per_wg(); a.cap = bp.cap; a.frame_w = W; a.frame_h = H;
+    a.all_tables = bp.tables_fit ? 1 : 0;
+    a.row_slot = bp.live ? s.d_row_slot : nullptr;
+    a.lmat_doubles = bp.lmat_doubles;
     static const bool no_reg = getenv("VC_TRACK_NO_REG") != nullptr;
     a.no_reg = no_reg ? 1 : 0;
     a.dbg_costs = st == 3 ? 1 : 0;                               // blocking entry points: vc_tracker_debug_costs may read the rows back
-    static const bool dbg_on = getenv("VC_TRACK_DBG") != nullptr;        // diagnostics: phase times of every task, printed per batch
+    return a;
+}
+
+// diagnostics (VC_TRACK_DBG): phase times of every task, printed per batch.  dbg_begin: the kernel's timestamp buffer, null when off
+static long long* dbg_begin(int n_tasks, hipStream_t ts) {
+    static const bool dbg_on = getenv("VC_TRACK_DBG") != nullptr;
     long long* dbg = nullptr;
-    if (dbg_on && hipMalloc((void**)&dbg, (size_t)n_tasks * 128) == hipSuccess) { hipMemsetAsync(dbg, 0, (size_t)n_tasks * 128, ts); a.dbg = dbg; }
+    if (dbg_on && hipMalloc((void**)&dbg, (size_t)n_tasks * 128) == hipSuccess) hipMemsetAsync(dbg, 0, (size_t)n_tasks * 128, ts);
+    return dbg;
+}
+
+static void dbg_report(long long* dbg, const TrackBatchPlan& bp, hipStream_t ts) {
+    const int n_tasks = bp.n_tasks();
+    std::vector<long long> h((size_t)n_tasks * 16);
+    hipStreamSynchronize(ts);
+    hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost);
+    hipFree(dbg);
+    double acc[5] = {0, 0, 0, 0, 0}, sumT = 0, sumD = 0;
+    int maxwg = 0;
+    for (const TrackWgPlan& pl : bp.wg) maxwg = std::max(maxwg, pl.task_end - pl.task_begin);
+    for (int k = 0; k < n_tasks; ++k) {
+        for (int i = 0; i < 5; ++i) acc[i] += (double)(h[(size_t)k * 16 + i + 1] - h[(size_t)k * 16 + i]) / 100.0;
+        sumT += (double)h[(size_t)k * 16 + 6]; sumD += (double)h[(size_t)k * 16 + 7];
+    }
+    fprintf(stderr, "[vc track dbg] %d tasks in %d workgroups (longest %d tasks), LDS cap %d; us per task: predict %.1f cost %.1f match %.1f apply %.1f finish %.1f; mean T %.1f D %.1f\n",
+            n_tasks, bp.n_wg(), maxwg, bp.cap, acc[0] / n_tasks, acc[1] / n_tasks, acc[2] / n_tasks, acc[3] / n_tasks, acc[4] / n_tasks, sumT / n_tasks, sumD / n_tasks);
+    long long t_lo = INT64_MAX, t_hi = 0;
+    double worst = 0; const TrackWgPlan* wp = nullptr;
+    for (const TrackWgPlan& pl : bp.wg) {
+        const long long b0 = h[(size_t)pl.task_begin * 16], b1 = h[(size_t)(pl.task_end - 1) * 16 + 5];
+        t_lo = std::min(t_lo, b0); t_hi = std::max(t_hi, b1);
+        if ((double)(b1 - b0) > worst) { worst = (double)(b1 - b0); wp = &pl; }
+    }
+    if (!wp) return;
+    double a2[5] = {0, 0, 0, 0, 0}, sT = 0, sD = 0, gaps = 0, mp[3] = {0, 0, 0};
+    const int nt = wp->task_end - wp->task_begin;
+    for (int k = wp->task_begin; k < wp->task_end; ++k) {
+        for (int i = 0; i < 5; ++i) a2[i] += (double)(h[(size_t)k * 16 + i + 1] - h[(size_t)k * 16 + i]) / 100.0;
+        for (int i = 0; i < 3; ++i) mp[i] += (double)(h[(size_t)k * 16 + 9 + i] - h[(size_t)k * 16 + 8 + i]) / 100.0;
+        sT += (double)h[(size_t)k * 16 + 6]; sD += (double)h[(size_t)k * 16 + 7];
+        if (k > wp->task_begin) gaps += (double)(h[(size_t)k * 16] - h[(size_t)(k - 1) * 16 + 5]) / 100.0;
+    }
+    fprintf(stderr, "[vc track dbg]   match split of that workgroup, us per task: setup %.1f cascade %.1f iou stage %.1f\n", mp[0] / nt, mp[1] / nt, mp[2] / nt);
+    fprintf(stderr, "[vc track dbg]   kernel span %.0f us; slowest workgroup (tracker %d): %d tasks, %.0f us, per task predict %.1f cost %.1f match %.1f apply %.1f finish %.1f gap %.1f; mean T %.1f D %.1f\n",
+            (double)(t_hi - t_lo) / 100.0, wp->tracker, nt, worst / 100.0, a2[0] / nt, a2[1] / nt, a2[2] / nt, a2[3] / nt, a2[4] / nt, gaps / nt, sT / nt, sD / nt);
+}
+
+// Overlay lists (live_overlay.hip) for the counters live_overlay_begin found: behind the apply launch and in front of s.done -- the build
+// reads this stage's tasks and rows, which the stage's next batch overwrites.  a: null for a batch without a task (anno, text and frame
+// number only).  A launch of its own in the profile: a counter without the overlay shows none.
+static int overlay_build(vc_engine* e, std::vector<LiveOverlayPlan>& ov, const TrackStage& s, const long long* fno, const TrackBatchArgs* a, int H, int W) {
+    if (ov.empty()) return VC_OK;
+    ProfScope ps(e, VC_PROF_TRACK);
+    return live_overlay_finish(e, ov, s.frame_trk, fno, a, s.plan.n_tasks(), s.plan.n_frames, H, W, e->stream);
+}
+
+int track_enqueue(vc_engine* e, int st, const std::vector<std::vector<FrameClassDets>>& frames, const float* d_feat, int W, int H,
+                  int rows_cap, hipEvent_t wait, const vc_frame_dims* frame_dims, const int* frame_tracker) {
+    TrackStage& s = e->tstage[st];
+    VC_CHECK(!s.busy, VC_ERR_STATE, "tracker staging slot %d is still in flight", st);
+    TrackBatchPlan& bp = s.plan;
+    const int b = (int)frames.size();
+    hipStream_t ts = e->stream;
+    std::vector<const FrameClassDets*> src;
+    VC_TRY(batch_tasks(e, frames, bp.tasks, src));
+    plan_track_batch(bp, b, [&](int tr) { const Tracker& tk = *e->trackers[tr]; return TrackSizes{tk.known_tracks, tk.pending_dets, tk.p.nn_budget}; },
+                     TrackPlanLimits{e->pool.budget_cap, (long long)e->dot_arena_max_floats, e->row_src_cap}, rows_cap,
+                     batch_is_live(e, bp.tasks, b, frame_tracker), frame_dims);
+    // The counters of this batch's cameras whose overlay is enabled -- none unless vc_live_overlay_enable has run, and then the launch
+    // below is exactly what it was.  Lists are built for uniform batches only.
+    std::vector<LiveOverlayPlan> ov;
+    s.frame_trk.clear();
+    if (!e->lives.empty()) track_frame_cameras(bp.tasks, b, frame_tracker, s.frame_trk);
+    if (!frame_dims && !e->lives.empty()) VC_TRY(live_overlay_begin(e, s.frame_trk, ts, ov));
+    if (bp.wg.empty()) {                                     // nothing to step; the frames still count for their cameras' live counters
+        std::vector<long long> fno((size_t)b, 0);
+        if (bp.live) number_frames(e, s.frame_trk, fno.data());
+        VC_TRY(overlay_build(e, ov, s, fno.data(), nullptr, H, W));
+        s.busy = true; VC_HIP(hipEventRecord(s.done, ts)); return VC_OK;
+    }
+    VC_TRY(reserve_buffers(e, s));
+    fill_input_block(s, src);
+    long long* fno = (long long*)(s.h_in + bp.in.fno);
+    std::vector<LiveCountArgs> live_args;
+    if (bp.live) {
+        number_frames(e, s.frame_trk, fno);
+        std::vector<int> used;
+        for (const TrackWgPlan& pl : bp.wg) used.push_back(pl.tracker);
+        live_batch_args(e, used, (const long long*)(s.d_in + bp.in.fno), live_args);
+    }
+    for (auto& td : bp.tracker_dets) e->trackers[td.first]->pending_dets += td.second;
+    VC_TRY(upload_inputs(e, s, wait));
+    TrackBatchArgs a = batch_args(e, s, st, d_feat, W, H);
+    a.dbg = dbg_begin(bp.n_tasks(), ts);
     {
         ProfScope ps(e, VC_PROF_TRACK);
-        VC_TRY(launch_track_batch(a, n_wg, ts, live_args.data(), (int)live_args.size()));
+        VC_TRY(launch_track_batch(a, bp.n_wg(), ts, live_args.data(), (int)live_args.size()));
     }
-    // behind the apply launch and in front of s.done: the build reads this stage's tasks and rows, which the stage's next batch overwrites
-    if (!ov.empty()) {
-        ProfScope ps(e, VC_PROF_TRACK);                          // a launch of its own in the profile: a counter without the overlay shows none
-        VC_TRY(live_overlay_finish(e, ov, frame_trk, (const long long*)(s.h_in + o_fno), &a, n_tasks, (int)frames.size(), H, W, ts));
-    }
-    if (dbg) {
-        std::vector<long long> h((size_t)n_tasks * 16);
-        hipStreamSynchronize(ts);
-        hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost);
-        hipFree(dbg);
-        double acc[5] = {0, 0, 0, 0, 0}, sumT = 0, sumD = 0;
-        int maxwg = 0;
-        for (const TrackWgPlan& pl : plans) maxwg = std::max(maxwg, pl.task_end - pl.task_begin);
-        for (int k = 0; k < n_tasks; ++k) {
-            for (int i = 0; i < 5; ++i) acc[i] += (double)(h[(size_t)k * 16 + i + 1] - h[(size_t)k * 16 + i]) / 100.0;
-            sumT += (double)h[(size_t)k * 16 + 6]; sumD += (double)h[(size_t)k * 16 + 7];
-        }
-        fprintf(stderr, "[vc track dbg] %d tasks in %d workgroups (longest %d tasks), LDS cap %d; us per task: predict %.1f cost %.1f match %.1f apply %.1f finish %.1f; mean T %.1f D %.1f\n",
-                n_tasks, n_wg, maxwg, cap, acc[0] / n_tasks, acc[1] / n_tasks, acc[2] / n_tasks, acc[3] / n_tasks, acc[4] / n_tasks, sumT / n_tasks, sumD / n_tasks);
-        long long t_lo = INT64_MAX, t_hi = 0;
-        double worst = 0; const TrackWgPlan* wp = nullptr;
-        for (const TrackWgPlan& pl : plans) {
-            const long long b0 = h[(size_t)pl.task_begin * 16], b1 = h[(size_t)(pl.task_end - 1) * 16 + 5];
-            t_lo = std::min(t_lo, b0); t_hi = std::max(t_hi, b1);
-            if ((double)(b1 - b0) > worst) { worst = (double)(b1 - b0); wp = &pl; }
-        }
-        if (wp) {
-            double a2[5] = {0, 0, 0, 0, 0}, sT = 0, sD = 0, gaps = 0;
-            const int nt = wp->task_end - wp->task_begin;
-            for (int k = wp->task_begin; k < wp->task_end; ++k) {
-                for (int i = 0; i < 5; ++i) a2[i] += (double)(h[(size_t)k * 16 + i + 1] - h[(size_t)k * 16 + i]) / 100.0;
-                sT += (double)h[(size_t)k * 16 + 6]; sD += (double)h[(size_t)k * 16 + 7];
-                if (k > wp->task_begin) gaps += (double)(h[(size_t)k * 16] - h[(size_t)(k - 1) * 16 + 5]) / 100.0;
-            }
-            double mp[3] = {0, 0, 0};
-            for (int k = wp->task_begin; k < wp->task_end; ++k)
-                for (int i = 0; i < 3; ++i) mp[i] += (double)(h[(size_t)k * 16 + 9 + i] - h[(size_t)k * 16 + 8 + i]) / 100.0;
-            fprintf(stderr, "[vc track dbg]   match split of that workgroup, us per task: setup %.1f cascade %.1f iou stage %.1f\n", mp[0] / nt, mp[1] / nt, mp[2] / nt);
-            fprintf(stderr, "[vc track dbg]   kernel span %.0f us; slowest workgroup (tracker %d): %d tasks, %.0f us, per task predict %.1f cost %.1f match %.1f apply %.1f finish %.1f gap %.1f; mean T %.1f D %.1f\n",
-                    (double)(t_hi - t_lo) / 100.0, wp->tracker, nt, worst / 100.0, a2[0] / nt, a2[1] / nt, a2[2] / nt, a2[3] / nt, a2[4] / nt, gaps / nt, sT / nt, sD / nt);
-        }
-    }
-    VC_HIP(hipMemcpyAsync(s.h_out + ol.status, s.d_cursor + 4, 16, hipMemcpyDeviceToHost, ts));
+    VC_TRY(overlay_build(e, ov, s, fno, &a, H, W));
+    if (a.dbg) dbg_report(a.dbg, bp, ts);
+    VC_HIP(hipMemcpyAsync(s.h_out + bp.out.status, s.d_cursor + 4, 16, hipMemcpyDeviceToHost, ts));
     VC_HIP(hipEventRecord(s.done, ts));
     s.busy = true;
     return VC_OK;
@@ -375,18 +331,19 @@ int track_collect(vc_engine* e, int st, int64_t* out_rows6, int cap_rows_per_fra
     VC_CHECK(s.busy, VC_ERR_STATE, "no tracker batch in staging slot %d", st);
     VC_HIP(hipEventSynchronize(s.done));
     s.busy = false;
-    for (int f = 0; f < s.b; ++f) out_m[f] = 0;
-    if (s.n_tasks == 0) return VC_OK;
-    const OutLayout ol = out_layout(s.n_tasks, s.rows_cap);
+    const TrackBatchPlan& bp = s.plan;
+    const TrackOutLayout& ol = bp.out;
+    for (int f = 0; f < bp.n_frames; ++f) out_m[f] = 0;
+    if (bp.n_tasks() == 0) return VC_OK;
     const int* row_off = (const int*)(s.h_out + ol.row_off);
     const int* row_n = (const int*)(s.h_out + ol.row_n);
     const int* ntr = (const int*)(s.h_out + ol.ntracks);
     const int* status = (const int*)(s.h_out + ol.status);
     const long long* rows = (const long long*)(s.h_out + ol.rows);
-    for (size_t i = 0; i < s.tracker_dets.size(); ++i) {                        // size bounds for the next batches
-        Tracker& tk = *e->trackers[s.tracker_dets[i].first];
-        tk.pending_dets -= s.tracker_dets[i].second;
-        tk.known_tracks = ntr[s.last_task_of[i]];
+    for (size_t i = 0; i < bp.tracker_dets.size(); ++i) {                       // size bounds for the next batches
+        Tracker& tk = *e->trackers[bp.tracker_dets[i].first];
+        tk.pending_dets -= bp.tracker_dets[i].second;
+        tk.known_tracks = ntr[bp.last_task_of[i]];
     }
     if (status[0] != TERR_NONE) {
         const char* what = status[0] == TERR_TRACK_CAP ? "live tracks + detections exceed the per-tracker capacity (vc_engine_config.tracks_per_tracker)"
@@ -397,8 +354,8 @@ int track_collect(vc_engine* e, int st, int64_t* out_rows6, int cap_rows_per_fra
         set_error("tracker %d: %s; the tracker is stopped until vc_tracker_reset", status[1], what);
         return VC_ERR_CAPACITY;
     }
-    for (int i = 0; i < s.n_tasks; ++i) {                                       // (frame, class) order
-        const int k = s.dev_index[i], f = s.tasks[i].frame, m = row_n[k];
+    for (int i = 0; i < bp.n_tasks(); ++i) {                                    // (frame, class) order
+        const int k = bp.dev_index[i], f = bp.tasks[i].frame, m = row_n[k];
         VC_CHECK(out_m[f] + m <= cap_rows_per_frame, VC_ERR_CAPACITY, "frame %d needs room for %d rows", f, out_m[f] + m);
         memcpy(out_rows6 + ((size_t)f * cap_rows_per_frame + out_m[f]) * 6, rows + (size_t)row_off[k] * 6, (size_t)m * 6 * sizeof(int64_t));
         out_m[f] += m;
@@ -632,10 +589,9 @@ int vc_tracker_debug_costs(vc_engine* e, int cap_entries, double* app, double* i
     VC_HIP(hipSetDevice(e->cfg.device));
     VC_TRY(async_wait_all(e));
     const TrackStage& s = e->tstage[3];
-    VC_CHECK(s.n_tasks == 1 && s.n_wg == 1 && !s.busy, VC_ERR_STATE, "the last blocking call did not step exactly one tracker");
-    const OutLayout ol = out_layout(1, s.rows_cap);
-    *T = ((const int*)(s.h_out + ol.tT))[0];
-    *D = s.tasks[0].det_n;
+    VC_CHECK(s.plan.n_tasks() == 1 && s.plan.n_wg() == 1 && !s.busy, VC_ERR_STATE, "the last blocking call did not step exactly one tracker");
+    *T = ((const int*)(s.h_out + s.plan.out.tT))[0];
+    *D = s.plan.tasks[0].det_n;
     const size_t n = (size_t)*T * *D;
     VC_CHECK(n <= (size_t)cap_entries, VC_ERR_CAPACITY, "need room for %zu entries", n);
     VC_HIP(hipStreamSynchronize(e->stream));
