@@ -353,6 +353,40 @@ int vc_live_stats(vc_live* live, int* open_tracks, int* retired_tracks);
 /* ncclAllGather straight from the device tensor on the stream vc_allgather_counts uses (vc_comm_init first): out receives world x
  * n_cam x max_dir x n_labels values, rank-major; every rank's counter must have the same shape. */
 int vc_live_allgather(vc_engine* e, vc_live* live, int32_t* out);
+/* ---- live checkpoint: device-packed snapshot and resume of a counter and its trackers (csrc/live_ckpt.hip, format csrc/live_ckpt.h) ----
+ * One self-contained little-endian blob holds everything the counter and its n_cam x n_labels trackers read from now on: frames_done,
+ * zones and base per camera, the retired count, and per tracker its parameters, id counter and every track in list order with Kalman
+ * state (fp64, bit for bit), its 88-byte counter record and the valid gallery rows.  No pool slot, handle or engine setting is in it:
+ * restored onto another counter -- another engine, process or GPU -- and fed the same frames, the stream continues with identical
+ * rows, ids, counts and overlay lists.
+ *
+ * vc_live_checkpoint_enable allocates, once, a device staging buffer and a pinned host buffer of max_bytes, the offset table, two events
+ * and a copy stream (a second call: VC_ERR_STATE; max_bytes below the fixed sections: VC_ERR_CAPACITY).  Without it nothing about a
+ * tracker launch changes, and with it nothing does either: only vc_live_checkpoint_begin enqueues work.
+ * vc_live_checkpoint_begin enqueues, BEHIND everything enqueued so far on the tracker stream, a plan and a pack kernel that write the
+ * blob into the staging buffer, and on the copy stream, behind an event, its copy to pinned memory.  frames_done is taken as of this
+ * call.  It makes no synchronising call and does not touch batches in flight: their rows are collected as usual, before or after
+ * vc_live_checkpoint_end.  A second begin before end: VC_ERR_STATE.
+ * vc_live_checkpoint_end waits for the copy only.  buf == NULL reports *size and leaves the checkpoint ready; cap < *size is
+ * VC_ERR_CAPACITY and leaves it ready too.  A state larger than max_bytes is VC_ERR_CAPACITY (the message names the size needed) and
+ * drops the checkpoint; the stream itself is unaffected.  Without begin: VC_ERR_STATE.
+ * vc_live_checkpoint = begin (unless a size query left a checkpoint ready) + end.
+ * Every camera of the counter is in the blob; one camera migrates through cam_map of vc_live_restore.
+ *
+ * vc_live_restore replaces the state of the counter's cameras cam_map[i] (i = camera of the blob; -1: that camera is not restored;
+ * NULL: identity) and of their trackers.  The blob may hold fewer cameras than the counter, or more if cam_map picks some.  The whole blob is validated first; a malformed blob, n_labels other
+ * than the counter's, a bad cam_map, or a zone that is not bit-equal to the mapped camera's zone: VC_ERR_ARG; nn_budget above
+ * nn_budget_cap, more tracks of a tracker than tracks_per_tracker, too few free pool slots: VC_ERR_CAPACITY.  ANY refusal leaves the
+ * counter and its trackers untouched.  Batches that are enqueued but not collected: VC_ERR_STATE (vc_stream_collect them first: their
+ * collect would write the track counts of the state they ran on over the restored ones).  A tracker an error had stopped stays stopped.
+ * The retired count is kept per counter: it becomes the blob's when the whole blob restores the whole counter, and is left as it is by a
+ * partial restore.  vc_live_ckpt_validate_host: the validation alone, pure host code. */
+int vc_live_checkpoint_enable(vc_live* live, size_t max_bytes);
+int vc_live_checkpoint_begin(vc_live* live);
+int vc_live_checkpoint_end(vc_live* live, void* buf, size_t cap, size_t* size);
+int vc_live_checkpoint(vc_live* live, void* buf, size_t cap, size_t* size);
+int vc_live_restore(vc_live* live, const void* buf, size_t size, const int* cam_map);
+int vc_live_ckpt_validate_host(const void* buf, size_t size);
 /* One launch of live_count_apply_kernel and one of live_count_read_kernel on host arrays (parity tests): zones as for vc_live_create;
  * tracker_cam[n_trackers] = camera of a tracker, -1 = not attached; slots88 = max_tracks records of 88 bytes {int32 open, cam, label,
  * at_last; int64 last_frame, first[4], last[4]}, base and stats2 = {open, retired} as the previous batch left them (in / out); the batch:

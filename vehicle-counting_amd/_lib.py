@@ -194,6 +194,12 @@ SIGNATURES = {
     "vc_live_counts_dev": [_vp, _P(_vp)],
     "vc_live_stats": [_vp, _pi, _pi],
     "vc_live_allgather": [_vp, _vp, _pi],
+    "vc_live_checkpoint_enable": [_vp, C.c_size_t],
+    "vc_live_checkpoint_begin": [_vp],
+    "vc_live_checkpoint_end": [_vp, _vp, C.c_size_t, _P(C.c_size_t)],
+    "vc_live_checkpoint": [_vp, _vp, C.c_size_t, _P(C.c_size_t)],
+    "vc_live_restore": [_vp, _vp, C.c_size_t, _pi],
+    "vc_live_ckpt_validate_host": [_vp, C.c_size_t],
     "vc_live_count_host": [_i, _i, _pd, _pi, _pd, _pi, _i, _pi, _i, _pl, _pi, _i, _pi, _i, _pl, _i, _pi, _i, _vp, _pi, _pi, _pi],
     "vc_live_overlay_enable": [_vp, _pi, _i, _i, _i],
     "vc_live_overlay_lists": [_vp, _pi, _i, _pi, _i, _pi, _pi],

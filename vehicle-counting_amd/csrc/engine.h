@@ -326,7 +326,7 @@ struct vc_engine {
 };
 
 // A live counter (live_count.hip) and, once vc_live_overlay_enable has run, its overlay list builder (live_overlay.hip)
-namespace vc { struct LiveOverlay; }
+namespace vc { struct LiveOverlay; struct LiveCkpt; }
 struct vc_live {
     vc_engine* e = nullptr;
     int n_cam = 0, n_labels = 0, max_dir = 0;
@@ -337,6 +337,9 @@ struct vc_live {
     int32_t* h_out = nullptr;                // pinned: counts + stats
     std::vector<int> n_dir;                  // [n_cam]
     vc::LiveOverlay* ov = nullptr;           // null until vc_live_overlay_enable: then every uniform tracker launch builds its lists
+    std::vector<double> h_poly, h_dirs;      // the zones as the device holds them (padded): what vc_live_restore compares a blob's zones with
+    std::vector<int> poly_n;                 // [n_cam]
+    vc::LiveCkpt* ck = nullptr;              // null until vc_live_checkpoint_enable (live_ckpt.hip)
 };
 
 namespace vc {
@@ -445,6 +448,11 @@ int live_overlay_finish(vc_engine* e, std::vector<LiveOverlayPlan>& plans, const
 int live_overlay_take(vc_live* l, int b, int h, int w, const void** d_prims, const int** d_first, hipEvent_t* built, int* token);
 int live_overlay_release(vc_live* l, int token);      // VC_ERR_CAPACITY if a frame of that batch did not fit its arena
 void live_overlay_free(vc_live* l);
+// live_ckpt.hip: waits for a checkpoint in flight and frees what vc_live_checkpoint_enable allocated
+void live_ckpt_free(vc_live* l);
+// tracker.hip: the free-slot stack from the host (engine idle): take n slots / give slots back
+int host_take_slots(vc_engine* e, int n, std::vector<int>& out);
+int host_give_slots(vc_engine* e, const std::vector<int>& slots);
 // render.hip: before a counter's lists are freed -- waits for the contexts that read them and drops their references
 void render_forget_live(vc_engine* e, vc_live* l);
 // rows6 per frame: out_rows6[f * cap_rows_per_frame * 6 ...], out_m[f]

@@ -185,6 +185,7 @@ long long live_next_frame(vc_engine* e, int tracker_slot_) {
 
 static void live_free(vc_live* l) {
     live_overlay_free(l);                                // waits for the render contexts that still read its lists
+    live_ckpt_free(l);                                   // waits for a checkpoint in flight
     for (void* p : l->allocs) (void)hipFree(p);
     if (l->h_out) (void)hipHostFree(l->h_out);
     delete l;
@@ -232,6 +233,7 @@ int vc_live_create(vc_engine* e, int n_cam, int n_labels, const int* trackers, c
     l->e = e; l->n_cam = n_cam; l->n_labels = n_labels; l->max_dir = max_dir; l->trackers = slots;
     l->frames_done.assign(n_cam, 0);
     l->n_dir.assign(n_dir, n_dir + n_cam);
+    l->poly_n.assign(poly_n, poly_n + n_cam); l->h_poly = poly; l->h_dirs = dirs;
     const int n = n_cam * max_dir * n_labels, T = e->cfg.max_tracks;
     std::vector<int> owner((size_t)e->max_trackers, -1);
     for (size_t i = 0; i < slots.size(); ++i) owner[slots[i]] = (int)(i / n_labels);

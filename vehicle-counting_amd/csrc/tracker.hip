@@ -440,7 +440,7 @@ static int download_tracker(vc_engine* e, int id, HostTrackerState& st) {
 }
 
 // free-slot stack, host side (engine idle): take n slots / give slots back
-static int host_take_slots(vc_engine* e, int n, std::vector<int>& out) {
+int host_take_slots(vc_engine* e, int n, std::vector<int>& out) {
     int ctl[2];
     VC_HIP(hipMemcpy(ctl, e->d_free, sizeof(ctl), hipMemcpyDeviceToHost));
     VC_CHECK(ctl[0] >= n, VC_ERR_CAPACITY, "track pool too small for %d more tracks (max_tracks = %d)", n, e->cfg.max_tracks);
@@ -450,7 +450,7 @@ static int host_take_slots(vc_engine* e, int n, std::vector<int>& out) {
     VC_HIP(hipMemcpy(e->d_free, ctl, sizeof(int), hipMemcpyHostToDevice));
     return VC_OK;
 }
-static int host_give_slots(vc_engine* e, const std::vector<int>& slots) {
+int host_give_slots(vc_engine* e, const std::vector<int>& slots) {
     if (slots.empty()) return VC_OK;
     int ctl[2];
     VC_HIP(hipMemcpy(ctl, e->d_free, sizeof(ctl), hipMemcpyDeviceToHost));

@@ -574,12 +574,67 @@ class LiveCounter:
         L.check(L.lib().vc_live_overlay_lists(self._h, L.ptr(prims.reshape(-1), C.c_int), cap_prims, L.ptr(first, C.c_int), cap_frames, C.byref(b), C.byref(n)))
         return prims[:n.value].copy(), first[:b.value + 1].copy()
 
+    # ---- checkpoint (vc_live_checkpoint* / vc_live_restore; DESIGN.md 5 "Live checkpoint") ----
+    def enable_checkpoint(self, max_bytes):
+        """Reserve the staging buffers of a checkpoint of at most max_bytes, once.  Nothing about a tracker launch changes."""
+        L.check(L.lib().vc_live_checkpoint_enable(self._h, int(max_bytes)))
+
+    def checkpoint_begin(self):
+        """Enqueue the device pack of this counter and its trackers behind every batch enqueued so far, and its copy to pinned memory on
+        a stream of its own.  Does not wait and does not touch the batches in flight; VcError (VC_ERR_STATE) if one is in flight already."""
+        L.check(L.lib().vc_live_checkpoint_begin(self._h))
+
+    def _checkpoint_out(self, fn) -> bytes:
+        n = C.c_size_t()
+        L.check(fn(self._h, None, 0, C.byref(n)))
+        out = np.empty(max(n.value, 1), np.uint8)
+        L.check(fn(self._h, C.c_void_p(out.ctypes.data), n.value, C.byref(n)))
+        return out[:n.value].tobytes()
+
+    def checkpoint_end(self) -> bytes:
+        """The blob of the last `checkpoint_begin` (waits for its copy only).  VcError (VC_ERR_CAPACITY) if the state outgrew max_bytes."""
+        return self._checkpoint_out(L.lib().vc_live_checkpoint_end)
+
+    def checkpoint(self) -> bytes:
+        """`checkpoint_begin` + `checkpoint_end`."""
+        return self._checkpoint_out(L.lib().vc_live_checkpoint)
+
+    def restore(self, blob: bytes, cam_map=None):
+        """Replace the state of this counter's cameras cam_map[i] (i = camera of the blob; -1: that camera is not restored; None: identity) and of their
+        trackers by the blob's, possibly taken on another engine / GPU.  Any refusal (VcError) leaves the counter and its trackers untouched."""
+        buf = C.create_string_buffer(bytes(blob), max(len(blob), 1))
+        cm = None if cam_map is None else np.ascontiguousarray(cam_map, dtype=np.int32).reshape(-1)
+        if cm is not None and len(blob) >= CKPT_HEADER_BYTES and bytes(blob[:8]) == b"VCLIVE01" and len(cm) != checkpoint_dims(blob)[0]:
+            raise ValueError(f"cam_map has {len(cm)} entries, the checkpoint {checkpoint_dims(blob)[0]} cameras")   # the library reads one per camera of the blob
+        L.check(L.lib().vc_live_restore(self._h, buf, len(blob), L.ptr(cm, C.c_int)))
+
     def close(self):
         if self._h and self.engine._h:
             L.check(L.lib().vc_live_destroy(self._h))
         self._h = None
         if self in getattr(self.engine, "_lives", []):
             self.engine._lives.remove(self)
+
+
+CKPT_HEADER_BYTES, CKPT_CAMERA_BYTES = 64, 1552          # sizeof(ck::CkptHeader), sizeof(ck::CkptCamera) of csrc/live_ckpt.h (tests/test_live_ckpt_host.py)
+
+
+def checkpoint_dims(blob):
+    """(n_cam, n_labels, max_dir) from the header of a live checkpoint"""
+    import struct
+    if len(blob) < CKPT_HEADER_BYTES or bytes(blob[:8]) != b"VCLIVE01":
+        raise ValueError("not a live checkpoint")
+    return struct.unpack_from("<3i", blob, 16)
+
+
+def checkpoint_frames_done(blob):
+    """frames_done per camera of a live checkpoint (header, then one section per camera), as of its `checkpoint_begin`"""
+    import struct
+    n_cam, n_labels, max_dir = checkpoint_dims(blob)
+    cam_bytes = (CKPT_CAMERA_BYTES + 4 * max_dir * n_labels + 15) // 16 * 16
+    if len(blob) < CKPT_HEADER_BYTES + n_cam * cam_bytes:
+        raise ValueError("not a live checkpoint")
+    return np.array([struct.unpack_from("<q", blob, CKPT_HEADER_BYTES + c * cam_bytes)[0] for c in range(n_cam)], np.int64)
 
 
 def live_count(polygons, dir_lines, n_labels, tracker_cam, rows6, row_slot, tasks5, frame_no, freed, slots, base, stats):

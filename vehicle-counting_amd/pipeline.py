@@ -155,11 +155,19 @@ class PipelineLive:
     `live=`: the call attaches it to the trackers it creates (`engine.LiveCounter`), calls `on_counts(batch_index, counts)` after every
     collect -- counts int32 (n_cam, max_dir, n_labels) over the rows of batches 0..batch_index, the batches enqueued by then -- and
     detaches it before the trackers are given back; `counts()` then keeps returning the final tensor.  `direction_keys[c]` names the
-    rows of camera c ('01', ...); rows past them are zero."""
+    rows of camera c ('01', ...); rows past them are zero.
+    resume (a blob of `checkpoint_end`, possibly of another engine, process or GPU): the counter and its trackers are restored from it
+    right after the counter is attached, once; `frame_base[c]` is then the number of frames camera c had had, and the run numbers its
+    rows from `frame_base[c] + 1`.  on_checkpoint(batch_index, blob, frames_done): called by a run with `checkpoint_every=k` with the
+    checkpoint taken behind every k-th batch (`engine.LiveCounter.checkpoint_begin` / `checkpoint_end`; checkpoint_bytes = the largest
+    blob, reserved once on the device and in pinned memory)."""
 
-    def __init__(self, engine, cam_names, zone_paths, n_labels, on_counts=None):
+    def __init__(self, engine, cam_names, zone_paths, n_labels, on_counts=None, resume=None, on_checkpoint=None, checkpoint_bytes=256 << 20):
         from .counting import load_zone_anno
         self.engine, self.cam_names, self.n_labels, self.on_counts = engine, list(cam_names), n_labels, on_counts
+        self.resume, self.on_checkpoint, self.checkpoint_bytes = resume, on_checkpoint, checkpoint_bytes
+        self.frame_base = np.zeros(len(self.cam_names), np.int64)
+        self._ckpt_batch = None
         zones = [load_zone_anno(z) for z in zone_paths]
         self.polygons = [np.asarray(p, np.float64).reshape(-1, 2) for p, _ in zones]
         self.direction_keys = [list(d.keys()) for _, d in zones]
@@ -169,17 +177,46 @@ class PipelineLive:
     def attach(self, tracker_ids, annotate=None):
         """annotate: None, or the keyword arguments of `LiveCounter.enable_overlay` (max_batch, max_rows_per_frame, depth) -- every
         batch then also leaves its overlay lists on the device for `Renderer.submit_live`."""
-        from .engine import LiveCounter
+        from .engine import LiveCounter, checkpoint_frames_done
         if self.counter is not None:
             raise RuntimeError("the live counter is attached already")
         self.counter = LiveCounter(self.engine, tracker_ids, self.polygons, self.dir_lines)
-        if annotate is not None:
-            try:
+        self.frame_base[:] = 0
+        self._ckpt_batch = None
+        try:
+            if annotate is not None:
                 self.counter.enable_overlay(self.direction_keys, **annotate)
-            except BaseException:
-                self.counter.close()
-                self.counter = None
-                raise
+            if self.on_checkpoint is not None:
+                self.counter.enable_checkpoint(self.checkpoint_bytes)
+            if self.resume is not None:
+                self.counter.restore(self.resume)
+                self.frame_base[:] = checkpoint_frames_done(self.resume)
+                self.resume = None
+        except BaseException:
+            self.counter.close()
+            self.counter = None
+            raise
+
+    def checkpoint_begin(self, batch_index):
+        """Behind the run of batch `batch_index`: the device pack is enqueued, nothing waits.  A checkpoint whose batch has not been
+        collected yet (checkpoint_every=1: batch n + 1 runs before batch n is collected) is handed out first -- one is in flight at a time."""
+        self._hand_out()
+        self.counter.checkpoint_begin()
+        self._ckpt_batch = batch_index
+
+    def checkpoint_end(self, collected):
+        """Behind the collect of batch `collected`: once the rows of the checkpointed batch itself are in -- its tracker launch is over
+        then, the pack behind it all but certainly too, and nothing waits -- the blob of the last `checkpoint_begin` goes to on_checkpoint."""
+        if self._ckpt_batch is not None and collected >= self._ckpt_batch:
+            self._hand_out()
+
+    def _hand_out(self):
+        from .engine import checkpoint_frames_done
+        if self._ckpt_batch is None:
+            return
+        n, self._ckpt_batch = self._ckpt_batch, None
+        blob = self.counter.checkpoint_end()
+        self.on_checkpoint(n, blob, checkpoint_frames_done(blob))
 
     def counts(self):
         return self.counter.counts() if self.counter is not None else self.last
@@ -258,11 +295,27 @@ class CountingPipeline:
                 if t is not None:
                     t.close()
 
-    def open_live(self, cam_names, zone_paths, on_counts=None):
+    def open_live(self, cam_names, zone_paths, on_counts=None, resume=None, on_checkpoint=None, checkpoint_bytes=256 << 20):
         """A live counter for these cameras (one tracker per camera and label, as every driver creates them): hand it to `run_stream`
         (one camera) or `run_streams` as `live=`.  Its counts after any batch are the counts the call would return for the video cut
-        there; nothing of the stream is kept for them."""
-        return PipelineLive(self.engine, cam_names, zone_paths, len(self.class_names), on_counts)
+        there; nothing of the stream is kept for them.
+        resume=blob (a live checkpoint, DESIGN.md 5 "Live checkpoint"): the run restores the counter and its trackers from it right after
+        attaching them and goes on where the checkpointed stream stood -- rows of camera c are numbered from frames_done[c] + 1, with the
+        ids, boxes and counts the uninterrupted stream would give.  The (rows, counts) pair the run returns then covers ONLY the resumed
+        part (its CSV columns direction / fpoint / fframe are computed over those rows alone); `live.counts()` is the WHOLE stream's
+        counts.  on_checkpoint / checkpoint_bytes: see PipelineLive; used by a run with `checkpoint_every=k`."""
+        return PipelineLive(self.engine, cam_names, zone_paths, len(self.class_names), on_counts, resume, on_checkpoint, checkpoint_bytes)
+
+    @staticmethod
+    def _checkpoint_every(live, checkpoint_every):
+        """(after_run(n), after_collect(n)) of a run: begin behind the run of every k-th batch, end behind that batch's own collect; both
+        no-ops without k"""
+        if not checkpoint_every:
+            return (lambda n: None), (lambda n: None)
+        if live is None or live.on_checkpoint is None:
+            raise ValueError("checkpoint_every= needs live= opened with on_checkpoint=")
+        k = int(checkpoint_every)
+        return (lambda n: live.checkpoint_begin(n) if (n + 1) % k == 0 else None), live.checkpoint_end
 
     @contextlib.contextmanager
     def _live(self, live, trackers, annotate=None):
@@ -392,7 +445,8 @@ class CountingPipeline:
                 collect()
         return self._finish(counter, obj, cam_name)
 
-    def run_stream(self, source, cam_name, zone_path, batch=16, asynchronous=False, host_frames=False, live=None, annotate=None):
+    def run_stream(self, source, cam_name, zone_path, batch=16, asynchronous=False, host_frames=False, live=None, annotate=None,
+                   checkpoint_every=None):
         """asynchronous=True: the tracker kernel of batch n runs on the engine's tracker stream while batch n+1 is submitted and
         embedded (`stream_run_async` / `stream_collect`); rows are identical, they arrive one batch later.
         host_frames=True: the frames stay in (pinned) host memory, as the reference's loader delivers them, and cross PCIe batch by
@@ -405,8 +459,12 @@ class CountingPipeline:
         annotate (a `YuvFrameSink` of the stream's frame size, with `live`): the live annotated video in ONE pass -- every batch's
         overlay lists are built on the device behind its tracker launch (`overlay.LiveVisualizer` is the definition) and the batch is
         rendered into the sink's next frames through `Renderer.submit_live` while the following batches run, two batches in flight.
-        Rows, counts and the CSV are what they are without it."""
+        Rows, counts and the CSV are what they are without it.
+        checkpoint_every=k (with `live` opened with on_checkpoint=): behind the run of every k-th batch the counter and its trackers are
+        packed on the device (`checkpoint_begin`, no wait); behind the collect of that batch's own rows the blob goes to on_checkpoint
+        (`checkpoint_end`: the pack lies behind the batch's tracker launch, which is over by then).  The stream is unchanged."""
         import torch
+        ck_run, ck_collect = self._checkpoint_every(live, checkpoint_every)
         tracker, counter = self._stages(cam_name, source.video_info, zone_path)
         obj = {"frames": [], "tracks": [], "labels": [], "boxes": []}
         yuv = isinstance(source, YuvFrameSource)
@@ -430,7 +488,7 @@ class CountingPipeline:
             stage = lambda n: ptr.__setitem__(n, dev[starts[n]:starts[n] + size(n)].data_ptr())
 
         def record(f0, rows, fidx):
-            obj["frames"].extend((f0 + 1 + fidx).tolist())
+            obj["frames"].extend((f0 + 1 + fidx + (int(live.frame_base[0]) if live is not None else 0)).tolist())
             obj["tracks"].extend(rows[:, 4].tolist())
             obj["labels"].extend(rows[:, 5].tolist())
             obj["boxes"].extend(list(rows[:, :4].copy()))
@@ -450,10 +508,14 @@ class CountingPipeline:
                     self.engine.stream_submit(ptr[n + 1], size(n + 1), h, w)
                 if asynchronous:
                     self.engine.stream_run_async(tracker.tracker_ids, ptr[n], b, h, w)
+                    ck_run(n)
                     if n > 0:
                         record(starts[n - 1], *self.engine.stream_collect()[:2])
+                        ck_collect(n - 1)
                 else:
                     record(f0, *self.engine.stream_run_packed(tracker.tracker_ids, ptr[n], b, h, w)[:2])
+                    ck_run(n)
+                    ck_collect(n)
                 if paint is not None:                       # the batch's lists were built behind its tracker launch: rendered from the BGR frames it ran on
                     paint(f0, ptr[n], b)
                 if live is not None and (n > 0 or not asynchronous):
@@ -461,6 +523,7 @@ class CountingPipeline:
                 ptr.pop(n - 1, None)
             if asynchronous and starts:
                 record(starts[-1], *self.engine.stream_collect()[:2])
+                ck_collect(len(starts) - 1)
                 if live is not None:
                     live.notify(len(starts) - 1)
             drain()
@@ -517,7 +580,8 @@ class CountingPipeline:
                 rnd.collect()
         return sink
 
-    def run_streams(self, sources, cam_names, zone_paths, batch=16, host_frames=False, mixed_sizes=False, live=None, annotate=None):
+    def run_streams(self, sources, cam_names, zone_paths, batch=16, host_frames=False, mixed_sizes=False, live=None, annotate=None,
+                    checkpoint_every=None):
         """S videos at once on ONE engine (the reference runs them one after another, each with a new VideoTracker,
         modules/__init__.py:28-36): the frames of the cameras are interleaved round-robin into batches of `batch` frames, the
         detector and the ReID net see one batch, every camera's frames are stepped on that camera's own trackers
@@ -536,8 +600,10 @@ class CountingPipeline:
         live (`open_live(cam_names, zone_paths)`): the running counts of all cameras on the device, see PipelineLive.
         annotate (a `YuvFrameSink`, with `live`; not with mixed_sizes): as in `run_stream`, for all cameras into ONE sink in batch
         (interleaved) order; the call then returns (results, [(camera index, 1-based frame number) of every sink frame]).  Each sink
-        frame is a self-contained surface: an encoder per camera takes its frames by `sink.address(i)`."""
+        frame is a self-contained surface: an encoder per camera takes its frames by `sink.address(i)`.
+        checkpoint_every=k: as in `run_stream`, one blob for all cameras."""
         import torch
+        ck_run, ck_collect = self._checkpoint_every(live, checkpoint_every)
         if annotate is not None and mixed_sizes:
             raise ValueError("annotate= with mixed_sizes=True: overlay lists are built for uniform batches only")
         S = len(sources)
@@ -580,7 +646,7 @@ class CountingPipeline:
             for c in range(S):
                 sel = cams[g] == c
                 o = objs[c]
-                o["frames"].extend((fidx[g[sel]] + 1).tolist())
+                o["frames"].extend((fidx[g[sel]] + 1 + (int(live.frame_base[c]) if live is not None else 0)).tolist())
                 o["tracks"].extend(rows[sel, 4].tolist())
                 o["labels"].extend(rows[sel, 5].tolist())
                 o["boxes"].extend(list(rows[sel, :4].copy()))
@@ -601,14 +667,17 @@ class CountingPipeline:
                 if n + 1 < len(starts):
                     submit(n + 1)
                 frames_dev = run(n, tids, cams[f0:f0 + b])
+                ck_run(n)
                 if paint is not None:                       # sink frame f0 + i = frame i of the batch: interleaved order
                     paint(f0, frames_dev, b)
                 if n > 0:
                     record(starts[n - 1], *self.engine.stream_collect()[:2])
+                    ck_collect(n - 1)
                     if live is not None:
                         live.notify(n)                      # batches 0..n are enqueued: their rows are in the counts
             if starts:
                 record(starts[-1], *self.engine.stream_collect()[:2])
+                ck_collect(len(starts) - 1)
                 if live is not None:
                     live.notify(len(starts) - 1)
             drain()
