@@ -95,8 +95,9 @@ int vc_engine_finalize(vc_engine* e); /* packs + uploads weights; detector/ReID 
  * VC_FRONT_FUSED, VC_CROP_PER_PIXEL, VC_DOT_ARENA_MB).  Names: "c3_fused", "bneck_fused", "bneck_cv3" (0 / 1), "front_fused" (0 off, 1 stream path,
  * 2 always), "crop_per_pixel", "sparse_head", "reid_block_fused", "fuse_upsample", "sppf_sep", "fuse_s2_pw", "stem_direct", "head_side" (0 / 1; stem_direct: 0 sends
  * the bf16 detector stem through the implicit GEMM like any other layer, for every variant; head_side: the P3 / P4 Detect-head ops on their own stream
- * beside the neck layers that follow them), "dot_arena_mb" (largest appearance-table arena the tracker may allocate; 0 = compute the
- * appearance rows inside the walk).  The parity tests use it to compare a fused kernel with the launches it replaces.
+ * beside the neck layers that follow them), "dot_arena_mb" (largest appearance-table arena the tracker may allocate or, once
+ * it is allocated, use: lowering it on a live engine bounds the tables of the next launch; 0 = compute the appearance rows inside
+ * the walk).  The parity tests use it to compare a fused kernel with the launches it replaces.
  * "embed_kept_only" (default 1, environment VC_EMBED_KEPT_ONLY): crop and embed only the boxes DeepSort.update's own filter keeps
  * (conf > min_confidence, then DeepSORT's NMS per class, deep_sort.py:31-37).  The reference embeds every box first and drops the rest
  * afterwards; a dropped box never becomes a Detection, so its feature is never read and the rows are the same.  0 embeds every box. */
@@ -152,6 +153,10 @@ typedef struct vc_tracker_params {
 /* tracker_id is an opaque handle (slot | generation << 16): every entry point that takes one refuses (VC_ERR_NOTFOUND / VC_ERR_ARG) a handle
  * whose tracker has been destroyed, also after its slot has been handed to a later vc_tracker_create. */
 int vc_tracker_create(vc_engine* e, const vc_tracker_params* p, int* tracker_id);
+/* Drops every track (their pool slots return) and clears the error of a stopped tracker.  A tracker stops at its first capacity
+ * error -- more tracks + detections in a step than tracks_per_tracker (that step changes nothing), an exhausted track pool, more rows
+ * than the caller's room: the launch returns VC_ERR_CAPACITY naming it, the other trackers of the launch step as usual, and every later
+ * step asked of the stopped tracker is refused with the same error until this call. */
 int vc_tracker_reset(vc_engine* e, int tracker_id);
 /* Gives the tracker's tracks and its slot back.  The reference drops its VideoTracker after every video (modules/__init__.py:32-36); the
  * drop-in's DeepSort calls this when it is closed. */

@@ -455,7 +455,8 @@ __device__ __forceinline__ bool pool_take(const TrackBatchArgs& a, int n, int* o
 
 __device__ __forceinline__ void report_error(const TrackBatchArgs& a, TrackerHdr* hdr, int code, int tracker, int task) {
     hdr->err = code;                 // the workgroup's copy (sh.hdr); written back with the header when the walk ends
-    if (__hip_atomic_exchange(a.status, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) { a.status[1] = tracker; a.status[2] = task; }
+    int none = TERR_NONE;            // the launch's first error is the one the host reports: code, tracker and task of the same step
+    if (__hip_atomic_compare_exchange_strong(a.status, &none, code, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { a.status[1] = tracker; a.status[2] = task; }
 }
 
 extern __shared__ __attribute__((aligned(16))) char track_dyn_lds[];
@@ -515,11 +516,13 @@ __global__ __launch_bounds__(NW * 64) void track_batch_kernel(const TrackBatchAr
         const bool small_cost = T * D <= 512 && !a.dbg_costs;            // block-uniform
         double* cost_app = small_cost ? sh.cost_small[0] : cost_app_g;
         double* cost_iou = small_cost ? sh.cost_small[1] : cost_iou_g;
-        // every capacity check comes before anything is mutated: a refused step leaves the tracker exactly as it was
+        // every capacity check comes before anything is mutated: a refused step leaves the tracker exactly as it was.  A tracker an
+        // earlier error has stopped reports that error again for every step it is asked for (the first one of a launch reaches the
+        // host): its frames are refused, not dropped, until vc_tracker_reset
         if (prior != TERR_NONE || T + D > TC_HARD_CAP || T + D > a.list_cap) {
             __syncthreads();
             if (threadIdx.x == 0) {
-                if (prior == TERR_NONE) report_error(a, hdr, TERR_TRACK_CAP, plan.tracker, task);
+                report_error(a, hdr, prior != TERR_NONE ? prior : TERR_TRACK_CAP, plan.tracker, task);
                 a.task_row_n[task] = 0; a.task_row_off[task] = 0; a.task_ntracks[task] = T; a.task_T[task] = T;
             }
             __syncthreads();

@@ -206,7 +206,9 @@ static TrackBatchArgs batch_args(vc_engine* e, const TrackStage& s, int st, cons
     a.plans = (const TrackWgPlan*)(s.d_in + bp.in.plans); a.tasks = (const TrackTask*)(s.d_in + bp.in.tasks);
     a.det_tlwh = (const double*)(s.d_in + bp.in.tlwh); a.det_xyah = (const double*)(s.d_in + bp.in.xyah); a.det_featrow = (const int*)(s.d_in + bp.in.frow);
     a.feat = d_feat;
-    a.dot_plans = e->d_dot_plans; a.dot_arena = e->d_dot_arena; a.dot_arena_floats = (long long)e->dot_arena_floats;
+    // what the plan kernel may hand out: the block that is allocated, and no more than the option allows NOW -- a "dot_arena_mb" lowered on
+    // an engine whose arena had already grown used to bound the host's plan only, and the device went on fitting tables into the old block
+    a.dot_plans = e->d_dot_plans; a.dot_arena = e->d_dot_arena; a.dot_arena_floats = (long long)std::min(e->dot_arena_floats, e->dot_arena_max_floats);
     a.row_src = e->d_row_src; a.row_src_cap = e->row_src_cap; a.gal_row = e->d_gal_row; a.nfeat = e->d_nfeat; a.det_ss = e->d_det_ss;
     a.dot_ctl = e->d_dot_ctl; a.n_det_total = bp.n_dets;
     a.rows = (long long*)(s.hd_out + bp.out.rows); a.rows_cap = bp.rows_cap; a.row_cursor = s.d_cursor;
@@ -219,7 +221,10 @@ static TrackBatchArgs batch_args(vc_engine* e, const TrackStage& s, int st, cons
     a.lmat_doubles = bp.lmat_doubles;
     static const bool no_reg = getenv("VC_TRACK_NO_REG") != nullptr;
     a.no_reg = no_reg ? 1 : 0;
-    a.dbg_costs = st == 3 ? 1 : 0;                               // blocking entry points: vc_tracker_debug_costs may read the rows back
+    // a blocking single step of one tracker: vc_tracker_debug_costs may read the rows back, so they go to the scratch whatever their
+    // size.  Every other blocking launch (several classes, or vc_videotracker_run_features' run of frames) chooses per step like the
+    // stream path does, which is what lets the tests walk a tracker across that switch inside one launch.
+    a.dbg_costs = st == 3 && bp.n_tasks() == 1 && bp.n_wg() == 1 ? 1 : 0;
     return a;
 }
 
