@@ -131,6 +131,17 @@ int vc_detect_debug_layer(vc_engine* e, int layer /* 0..23, or -1 = preprocessed
                           int dims[4] /* B,H,W,C */);
 int vc_detect_debug_pred(vc_engine* e, float* out /* B * n_candidates * (5+nc) */, size_t cap_floats);
 
+/* Launch recorder (diagnostics): vc_record_arm makes the NEXT pass of `net` (VC_NET_YOLO: vc_detect, a stream submission; VC_NET_REID:
+ * vc_embed, vc_embed_tensor, the stream path's ReID) keep, for every launch of its op plan, the ops the launch covered with every
+ * launch-view field, the bytes of every buffer it reads (copied just before the launch) and of every buffer it writes (copied before
+ * and after), on the launch's own stream.  A launch made while the conv autotuner still times candidates sees their stores in its
+ * before-copy: run the shape once before arming.  vc_record_list returns the records as JSON text (buf == NULL: only the size);
+ * vc_record_read copies the arena the records' "before" / "after" offsets point into, after waiting for the engine's streams.
+ * Unarmed, a pass tests one pointer per launch; the arena is allocated by an armed pass and freed with the engine. */
+int vc_record_arm(vc_engine* e, int net);
+int vc_record_list(vc_engine* e, char* buf, size_t cap, size_t* size);
+int vc_record_read(vc_engine* e, void* out, size_t cap_bytes);
+
 /* ---- embed: Extractor.__call__ over DeepSort._get_features crops -------------------------------- */
 /* bgr: H x W x 3 uint8 (the `ori_img` the reference crops from).  boxes_cxcywh: k x 4 float64 centre boxes
  * (deep_sort.py:28 bbox_xywh).  out_feat: k x 512 float32, unit L2 norm. */

@@ -127,6 +127,9 @@ SIGNATURES = {
     "vc_detect_debug_layer": [_vp, _i, _pf, C.c_size_t, _pi],
     "vc_embed_debug_input": [_vp, _i, _pf, C.c_size_t, _pi],
     "vc_detect_debug_pred": [_vp, _pf, C.c_size_t],
+    "vc_record_arm": [_vp, _i],
+    "vc_record_list": [_vp, C.c_char_p, C.c_size_t, _P(C.c_size_t)],
+    "vc_record_read": [_vp, _vp, C.c_size_t],
     "vc_embed": [_vp, _pu8, _i, _i, _pd, _i, _pf],
     "vc_embed_tensor": [_vp, _pf, _i, _pf],
     "vc_tracker_create": [_vp, _P(TrackerParams), _pi],

@@ -58,6 +58,8 @@ struct Op {
 struct YoloPlan { std::vector<Op> ops; View layer_view[24]; bool sparse = false; };
 struct ReidPlan { std::vector<Op> ops; View out{}; };
 
+struct LaunchRecorder;              // engine_record.hip
+
 struct Net {
     std::vector<ConvParam> params;
     std::map<std::string, int> index;
@@ -318,6 +320,9 @@ struct vc_engine {
     bool tuned_dirty = false;
     std::string op_log;                          // per-launch lines "name M N K tile ms" while profiling
     double last_ms = 0;
+    // launch recorder (engine_record.hip, diagnostics): null until a pass is recorded; rec_armed = 1 + the net whose next pass is (0: none)
+    vc::LaunchRecorder* rec = nullptr;
+    int rec_armed = 0;
 
     // ---- stream injection -----------------------------------------------------------------------------
     std::vector<float> inject_det;
@@ -387,6 +392,12 @@ int run_detector_dev_sized(vc_engine* e, const uint8_t* d_frames, int B, const v
 int run_reid_dev(vc_engine* e, const uint8_t* d_frames, int H, int W, int k);                      // crops in e->d_crops -> e->d_feat
 int run_reid_on(vc_engine* e, const uint8_t* d_frames, int H, int W, int k, const int* d_crops, float* feat_out, hipStream_t rs,
                 const CropFrame* d_ftab = nullptr);     // d_ftab: per-frame {offset, pitch} of a sized batch (device)
+// engine_record.hip: *out = the recorder if the next pass of `net` (this one, over `ops`) is armed, else null; the copies around one launch
+// of op[0 .. n_ops) on its stream (cp: this pass's copy of op[0].conv, null for the other kinds); what vc_engine_destroy calls
+int record_begin(vc_engine* e, int net, const std::vector<Op>& ops, LaunchRecorder** out);
+int record_before(LaunchRecorder* r, vc_engine* e, const Op* op, int n_ops, int cfg, const ConvP* cp, bool u8_src, bool side, hipStream_t s);
+int record_after(LaunchRecorder* r, hipStream_t s);
+void record_free(vc_engine* e);
 // stream.hip: the slot rules of vc_stream_stage_host (shared with the YUV staging calls): checks, creates the copy stream and the four
 // slots on first use, and hands out the next slot round-robin.  The caller enqueues its work on e->cstream, then calls ingest_publish.
 int ingest_take_slot(vc_engine* e, int b, int h, int w, int* slot);

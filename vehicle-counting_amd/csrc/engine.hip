@@ -253,6 +253,7 @@ int vc_engine_destroy(vc_engine* e) {
     if (e->dstream) hipStreamSynchronize(e->dstream);
     if (e->rstream) hipStreamSynchronize(e->rstream);
     if (e->cstream) hipStreamSynchronize(e->cstream);
+    record_free(e);
     for (void* p : e->allocs) hipFree(p);
     for (void* p : e->host_allocs) hipHostFree(p);
     for (auto& pp : e->prof_pairs) { hipEventDestroy(pp.a); hipEventDestroy(pp.b); }

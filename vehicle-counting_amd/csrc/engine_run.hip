@@ -226,7 +226,8 @@ static int conv_select(ConvCtx& c, double fl, double by, ConvLaunch& L) {
     return VC_OK;
 }
 
-static int run_ops_body(vc_engine* e, std::vector<Op>& ops, int aux_cat, hipStream_t s_main, bool& side_used) {
+// rec: the launch recorder of an armed pass (engine_record.hip), null otherwise -- one pointer test per launch
+static int run_ops_body(vc_engine* e, std::vector<Op>& ops, int aux_cat, hipStream_t s_main, bool& side_used, LaunchRecorder* rec) {
     // Op::side ops go to the head stream (detector passes only; not while every launch is bracketed by blocking events): the first of a run
     // of them waits for everything the main stream has been given so far, the caller joins the head stream before it reads their results
     const bool side_ok = s_main == e->dstream && e->hstream && e->opt.head_side && !e->profiling;
@@ -260,11 +261,13 @@ static int run_ops_body(vc_engine* e, std::vector<Op>& ops, int aux_cat, hipStre
                 ConvLaunch L;
                 VC_TRY(conv_select(cx, fl, by, L));
                 cp.cfg = L.cfg;
+                if (rec) VC_TRY(record_before(rec, e, &op, L.n_ops, L.cfg, &cp, cx.u8_src, on_side, s));
                 conv_timer_arm(e, cp, L.flops, L.bytes, op);
                 {
                     ProfScope ps(e, VC_PROF_CONV, L.flops, L.bytes, s);
                     VC_TRY(L.launch(cx));
                 }
+                if (rec) VC_TRY(record_after(rec, s));
                 double fl_exec = L.flops;                                     // executed FLOPs: differ where the row count lives on the device
                 if (e->profiling && (op.rows_level >= 0 || op.dense_flops >= 0)) {   // sparse head, blocking profile: the scope has synchronised
                     ProfCat& pc = e->prof[VC_PROF_CONV];
@@ -289,7 +292,12 @@ static int run_ops_body(vc_engine* e, std::vector<Op>& ops, int aux_cat, hipStre
                 oi += L.n_ops - 1;                                            // the ops the launch swallowed are done
                 break;
             }
-            case Op::SPPF: { ProfScope ps(e, aux_cat, 0, 0, s); VC_TRY(launch_sppf_pool(op.a, op.C, e->prec, e->opt.sppf_sep, s)); break; }
+            case Op::SPPF: {
+                if (rec) VC_TRY(record_before(rec, e, &op, 1, -1, nullptr, false, on_side, s));
+                { ProfScope ps(e, aux_cat, 0, 0, s); VC_TRY(launch_sppf_pool(op.a, op.C, e->prec, e->opt.sppf_sep, s)); }
+                if (rec) VC_TRY(record_after(rec, s));
+                break;
+            }
             case Op::UPSAMPLE: {
                 // bf16: when the consumer is the pointwise conv over [upsampled | skip] (C3.cv1 | cv2 of layers 13 / 17) it reads the half-size
                 // map itself; the slice of the concat buffer stays unwritten (vc_detect_debug_layer produces it on demand)
@@ -299,17 +307,32 @@ static int run_ops_body(vc_engine* e, std::vector<Op>& ops, int aux_cat, hipStre
                                   nx->conv.in_cs == op.b.cs && nx->conv.H == 2 * op.a.H && nx->conv.W == 2 * op.a.W && op.a.C % 64 == 0 && nx->conv.Cin % 64 == 0 &&
                                   op.a.C < nx->conv.Cin && op.a.cs % 8 == 0 && op.a.co % 8 == 0;
                 if (fold) { pending_up = &op; e->up_folded.push_back({op.a, op.b}); break; }
-                ProfScope ps(e, aux_cat, 0, 0, s);
-                VC_TRY(launch_upsample2x(op.a, op.b, e->prec, s));
+                if (rec) VC_TRY(record_before(rec, e, &op, 1, -1, nullptr, false, on_side, s));
+                { ProfScope ps(e, aux_cat, 0, 0, s); VC_TRY(launch_upsample2x(op.a, op.b, e->prec, s)); }
+                if (rec) VC_TRY(record_after(rec, s));
                 break;
             }
-            case Op::MAXPOOL: { ProfScope ps(e, aux_cat, 0, 0, s); VC_TRY(launch_maxpool3s2(op.a, op.b, e->aux_prec, s)); break; }   // ReID only
-            case Op::TO_FP8: { ProfScope ps(e, aux_cat, 0, 0, s); VC_TRY(launch_bf16_to_fp8(op.a, op.b, 1.0f / e->act_scale, s)); break; }
+            case Op::MAXPOOL: {                                                   // ReID only
+                if (rec) VC_TRY(record_before(rec, e, &op, 1, -1, nullptr, false, on_side, s));
+                { ProfScope ps(e, aux_cat, 0, 0, s); VC_TRY(launch_maxpool3s2(op.a, op.b, e->aux_prec, s)); }
+                if (rec) VC_TRY(record_after(rec, s));
+                break;
+            }
+            case Op::TO_FP8: {
+                if (rec) VC_TRY(record_before(rec, e, &op, 1, -1, nullptr, false, on_side, s));
+                { ProfScope ps(e, aux_cat, 0, 0, s); VC_TRY(launch_bf16_to_fp8(op.a, op.b, 1.0f / e->act_scale, s)); }
+                if (rec) VC_TRY(record_after(rec, s));
+                break;
+            }
             case Op::HEAD_COMPACT: {
-                ProfScope ps(e, aux_cat, 0, 0, s);
-                const int i = op.level, M = op.a.B * op.a.H * op.a.W;
-                VC_TRY(launch_head_compact(e->d_obj[i], op.a, M, op.a.H * op.a.W, e->cfg.conf_thres, e->hc_cap[i], e->d_hc_count + i, e->d_hc_list[i], e->d_hc_x[i],
-                                           e->post.overflow, s));
+                if (rec) VC_TRY(record_before(rec, e, &op, 1, -1, nullptr, false, on_side, s));
+                {
+                    ProfScope ps(e, aux_cat, 0, 0, s);
+                    const int i = op.level, M = op.a.B * op.a.H * op.a.W;
+                    VC_TRY(launch_head_compact(e->d_obj[i], op.a, M, op.a.H * op.a.W, e->cfg.conf_thres, e->hc_cap[i], e->d_hc_count + i, e->d_hc_list[i], e->d_hc_x[i],
+                                               e->post.overflow, s));
+                }
+                if (rec) VC_TRY(record_after(rec, s));
                 break;
             }
         }
@@ -319,9 +342,9 @@ static int run_ops_body(vc_engine* e, std::vector<Op>& ops, int aux_cat, hipStre
 
 // The join (head stream -> main stream) of the ops that forked onto the head stream is recorded HERE, on the error path too:
 // a pass that failed after the fork must not leave head ops running beside the next pass's memset of the counters they write.
-static int run_ops(vc_engine* e, std::vector<Op>& ops, int aux_cat, hipStream_t s_main) {
+static int run_ops(vc_engine* e, std::vector<Op>& ops, int aux_cat, hipStream_t s_main, LaunchRecorder* rec) {
     bool forked = false;
-    const int st = run_ops_body(e, ops, aux_cat, s_main, forked);
+    const int st = run_ops_body(e, ops, aux_cat, s_main, forked, rec);
     if (forked) {                                            // the P3 / P4 head ops ran on the head stream: whatever follows on the main stream waits for them
         const hipError_t e1 = hipEventRecord(e->ev_join, e->hstream);
         const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(s_main, e->ev_join, 0) : e1;
@@ -366,7 +389,9 @@ int yolo_forward(vc_engine* e, int B, int nh, int nw) {
         e->hc_ring_cur = (int)(e->hc_ring_seq++ % vc_engine::HC_RING);
         VC_HIP(hipMemsetAsync(e->d_zero, 0, e->zero_bytes, ds));
     }
-    VC_TRY(run_ops(e, plan.ops, VC_PROF_DETECT_AUX, ds));          // (joins the head stream before it returns: the decode reads the head ops' rows)
+    LaunchRecorder* rec = nullptr;
+    if (e->rec_armed) VC_TRY(record_begin(e, VC_NET_YOLO, plan.ops, &rec));
+    VC_TRY(run_ops(e, plan.ops, VC_PROF_DETECT_AUX, ds, rec));     // (joins the head stream before it returns: the decode reads the head ops' rows)
     if (sparse && e->prof_async && e->h_hc_ring)     // executed-work accounting: this pass's gathered-row counts, next to the event pairs
         VC_HIP(hipMemcpyAsync(e->h_hc_ring + (size_t)e->hc_ring_cur * 4, e->d_hc_count, 4 * sizeof(int), hipMemcpyDeviceToHost, ds));
     // decode + NMS
@@ -473,7 +498,9 @@ static int reid_forward_chunk(vc_engine* e, int k0, int k, hipStream_t rs, float
     ReidPlan transient;
     ReidPlan& plan = k <= VC_REID_PLAN_CACHE_MAX_K ? e->reid_plans[{k0, k}] : transient;
     if (plan.ops.empty()) VC_TRY(reid_build_ops(e, k0, k, plan));
-    VC_TRY(run_ops(e, plan.ops, VC_PROF_REID_AUX, rs));
+    LaunchRecorder* rec = nullptr;
+    if (e->rec_armed) VC_TRY(record_begin(e, VC_NET_REID, plan.ops, &rec));
+    VC_TRY(run_ops(e, plan.ops, VC_PROF_REID_AUX, rs, rec));
     ProfScope ps(e, VC_PROF_REID_AUX, 0, 0, rs);
     return launch_avgpool_l2norm(plan.out, feat_out, e->aux_prec, rs);               // model.py:70,93
 }

@@ -155,6 +155,23 @@ class Engine:
         L.check(L.lib().vc_detect_debug_pred(self._h, L.ptr(buf, C.c_float), buf.size))
         return buf.reshape(self.cfg.max_batch, nt.value, no)
 
+    # ---------------------------------------------------------------- launch recorder (diagnostics)
+    def record_arm(self, net="yolo"):
+        """Record every launch of the next detector ("yolo") or ReID ("reid") pass (`vc_record_arm`)."""
+        L.check(L.lib().vc_record_arm(self._h, L.NET_YOLO if net == "yolo" else L.NET_REID))
+
+    def record_read(self):
+        """(records, arena) of the recorded pass: the parsed JSON of `vc_record_list` and the uint8 array its offsets point into."""
+        import json
+        size = C.c_size_t()
+        L.check(L.lib().vc_record_list(self._h, None, 0, C.byref(size)))
+        text = C.create_string_buffer(size.value)
+        L.check(L.lib().vc_record_list(self._h, text, size.value, C.byref(size)))
+        rec = json.loads(text.value.decode())
+        arena = np.zeros(max(rec["arena_bytes"], 1), np.uint8)
+        L.check(L.lib().vc_record_read(self._h, arena.ctypes.data_as(C.c_void_p), arena.size))
+        return rec["launches"], arena
+
     # ---------------------------------------------------------------- embed (Extractor)
     def embed(self, bgr, boxes_cxcywh):
         bgr = np.ascontiguousarray(bgr, dtype=np.uint8)
